@@ -18,9 +18,12 @@ One JSON line on rank 0 with the contract's keys plus
   c5            BASELINE configs[4]: Swin-B on 64x256x256 clips, fp16 (video = 16 clips)
 (the extra legs run at N = 1; ``--legs c2`` skips them).
 
-Timing: the K-step block (barrier + sync, K steps, sync + barrier, max over ranks) is REPEATED until about a second of steps has been
-timed; ``ms_per_step`` / ``value`` are the MEDIAN block, ``repeats`` / ``ms_per_step_min`` / ``ms_per_step_max`` say how the blocks
+Timing: the K-step block (barrier + sync, K steps, sync + barrier, max over ranks) is timed once, so ``--steps`` is the number of timed
+steps and ``ms_per_step`` is the block's time over K.  ``--min-timed-s S`` REPEATS the block until about S seconds of steps have been
+timed; ``ms_per_step`` / ``value`` are then the MEDIAN block, ``repeats`` / ``ms_per_step_min`` / ``ms_per_step_max`` say how the blocks
 spread (a single 20-step block is 30 ms: box-to-box and clock noise are larger than most kernel changes).
+``--dump-outputs DIR`` writes what the timed path returned in its last timed step (rank 0) as ``DIR/scores.npy`` (float32); the
+inputs (weights, frames, sampler draws) are seeded, so two builds run with the same arguments can be compared output for output.
 HBM traffic (``roofline.traffic``, ``whole_step_traffic``): measured in this run by two child passes per leg under
 ``rocprofv3 --pmc FETCH_SIZE`` / ``--pmc WRITE_SIZE`` (``bench.py --probe LEG``: a few serial steps of the leg, nothing else), FETCH_SIZE
 doubled as the gfx950 guide prescribes; ``--no-pmc`` skips them (null).
@@ -77,7 +80,10 @@ def parse():
     ap.add_argument("--legs", default="all", help="comma list of extra legs at N=1: no_sampler,two_launch,fp16_stress,bf16_stress,batch8,one_stream,latency,in_mix,c3,c5,ksvqe ('all', 'c2' = none)")
     ap.add_argument("--src-pool", type=int, default=64, help="distinct uint8 source clips kept in HBM (49.8 MB each)")
     ap.add_argument("--profile-steps", type=int, default=3)
-    ap.add_argument("--min-timed-s", type=float, default=1.0, help="repeat the K-step block until this many seconds are timed")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="repeat the K-step block until this many seconds are timed (default 0: one block of exactly --steps steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the scores of the last timed step as DIR/scores.npy (float32)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (traffic fields = null)")
     ap.add_argument("--probe", default=None, choices=["c2", "c2mix", "c3", "c5", "ksvqe", "ksvqe96"],
                     help="internal: run --probe-steps serial steps of one leg and exit (the command the --pmc passes profile)")
@@ -1065,6 +1071,10 @@ def main():
     clips = args.steps * B * world
     value = clips / CLIPS_PER_VIDEO / dt
     fp_scores = torch.cat([o.reshape(-1) for o in outs]).float().cpu()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), outs[-1].float().cpu().numpy())
 
     out = None
     if rank == 0:

@@ -157,6 +157,36 @@ def test_bench_two_ranks_on_one_gpu_gloo(tmp_path):
     assert d["repeats"] >= 1 and d["ms_per_step_min"] <= d["ms_per_step"] <= d["ms_per_step_max"]
 
 
+def test_bench_times_steps_once_and_dumps_last_step(tmp_path):
+    """``bench.py --steps K`` times one block of exactly K steps, and ``--dump-outputs DIR`` writes the scores of the last timed step:
+    the same in a second run with the same arguments (seeded inputs) and the same as one forward of that step's clips."""
+    import importlib.util
+    import json
+    B, W, K = 2, 1, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(B),
+           "--legs", "c2", "--no-cpu-baseline", "--no-pmc", "--profile-steps", "0"]
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run(cmd + ["--dump-outputs", str(out)], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == K and d["repeats"] == 1
+        assert abs(d["ms_per_step"] * K / 1e3 - d["timed_s"]) <= 1e-9 * d["timed_s"]
+        dumps.append(np.load(str(out / "scores.npy")))
+        assert dumps[-1].dtype == np.float32 and dumps[-1].size == B and np.isfinite(dumps[-1]).all()
+    assert np.array_equal(dumps[0], dumps[1])
+    spec = importlib.util.spec_from_file_location("kvq_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = torch.device("cuda", 0)
+    net, *_ = bench.build_net("bf16", dev, "init")
+    src = bench.Source((W + K) * B, dev, 1234)
+    with torch.no_grad():
+        ref = net(inputs={"technical": src.fragments((W + K - 1) * B, B)}, reduce_scores=True).float().cpu().numpy()
+    assert np.abs(ref.reshape(-1) - dumps[0].reshape(-1)).max() <= 1e-5
+
+
 def _fake_kvq_tree(tmp_path, n=2, T=96, H=120, W=160):
     g = np.random.Generator(np.random.PCG64(91))
     vids = []
