@@ -33,7 +33,7 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (need ROCm's hipcc to build libkvq_hip.so)")
 
 
-# sources compiled several times with -D<macro>=<part> (their instantiations split over translation units: tailmm.hip's 42 kernels take ~5
+# sources compiled several times with -D<macro>=<part> (their instantiations split over translation units: tailmm.hip's 36 kernels take
 # minutes in one unit, ~1.5 in four)
 PARTS = {"tailmm.hip": ("KVQ_TAILMM_PART", 4)}
 

@@ -98,7 +98,8 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
     __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + q * 1024 + lane * 16), (lds_ptr_t)(lds + q * 1024), 16, 0, 0);
 
   // a workgroup walks tiles of 128 tokens blockIdx.x, + gridDim.x, ... (round 5: a launch of fewer, longer-lived workgroups — the weights
-  // reach LDS once per workgroup, and in the multi-lane mix the launch holds fewer CU slots while it streams its 200 MB)
+  // reach LDS once per workgroup, and in the multi-lane mix the launch holds fewer CU slots while it streams its 200 MB).  The launch gives
+  // one workgroup per tile: fewer gained nothing (profiles/r05_embed_wgs.txt)
   const long L0 = (long)p.D0 * p.H0 * p.W0, total = (long)p.B * L0;
   for (long tile = blockIdx.x; tile * 128 < total; tile += gridDim.x) {
   const bool first_tile = tile == (long)blockIdx.x;
@@ -293,10 +294,7 @@ template <typename E_, int CM, int KS>
 static int launch_embed(const EmbedParams& p, hipStream_t st) {
   const int lds = embed_stage_off(CM, KS) + (embed_staged(CM, p.x == nullptr) ? 4 * 32 * (32 * CM * 4 + 16) : 0);
   const long total = (long)p.B * p.D0 * p.H0 * p.W0;
-  // KVQ_EMBED_WGS: workgroups of the launch (each walks tiles of 128 tokens); 0 = one per tile (rounds 1-4)
-  static const long wgs = getenv("KVQ_EMBED_WGS") ? atol(getenv("KVQ_EMBED_WGS")) : 0;
-  const long ntile = (total + 127) / 128;
-  dim3 grid((unsigned)(wgs > 0 && wgs < ntile ? wgs : ntile)), block(256);
+  dim3 grid((unsigned)((total + 127) / 128)), block(256);      // one workgroup per tile of 128 tokens
   auto go = [&](auto k) -> int {
     LdsOptIn opt;                             // the opt-in is remembered per (kernel, device) in common.cpp
     if (int rc = opt.ensure(reinterpret_cast<const void*>(k), lds)) return rc;

@@ -491,15 +491,23 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
   // the last stage keeps fp32 (its stream comes out of a GEMM epilogue and feeds the final LayerNorm and the fp32 feature output).
   // KVQ_RESID16=0: fp32 everywhere (rounds 1-5).
   static const bool resid16_on = !(getenv("KVQ_RESID16") && atoi(getenv("KVQ_RESID16")) == 0);
-  static const int resid16_maxc = getenv("KVQ_RESID16_MAXC") ? atoi(getenv("KVQ_RESID16_MAXC")) : 1 << 30;      // 192: the token-per-lane stages only (A/B)
-  static const int tail_maxc_x = getenv("KVQ_TAIL_MAXC") ? atoi(getenv("KVQ_TAIL_MAXC")) : 1 << 30;
-  static const int merge_maxc_x = getenv("KVQ_MERGE_MAXC") ? atoi(getenv("KVQ_MERGE_MAXC")) : 192;
   bool any_tap = false;
   for (float* t : pl->taps) any_tap = any_tap || t != nullptr;
-  auto fused_merge = [&](int i) -> bool {                      // stage i -> i + 1 is the one-launch merge (csrc/merge.hip)
-    return i >= 0 && i < cfg.num_stages - 1 && w->merges[i].merge_pack && kvq_patch_merge_supported(pl->st[i].C) && pl->st[i].C <= merge_maxc_x;
+  // Which launches the forward takes, each decided in ONE place: the fp16-stream rule below and the launch sites ask the same predicates.
+  // By geometry and weights only, never by the batch.
+  // stage i -> i + 1 is the one-launch merge (csrc/merge.hip), up to C = 192 (see the merge's launch site)
+  auto fused_merge = [&](int i) -> bool {
+    return i >= 0 && i < cfg.num_stages - 1 && w->merges[i].merge_pack && kvq_patch_merge_supported(pl->st[i].C) && pl->st[i].C <= 192;
   };
   const bool embed_fused = w->embed_pack && kvq_patch_embed_supported(cfg.in_chans, cfg.patch[0], cfg.patch[1], cfg.patch[2], cfg.embed_dim, pl->T, pl->H, pl->W);
+  // block `bk` (index into w->blocks) of stage i: proj + norm2 + MLP (+ the next block's norm1 or q | k | v) as one launch
+  auto fused_tail = [&](int i, int bk) -> bool { return w->blocks[bk].tail_pack && kvq_block_tail_supported(pl->st[i].C, cfg.mlp_ratio * pl->st[i].C); };
+  // block `bk` of stage i: its attention launch computes its own q | k | v from the norm1 rows (C = 96, un-padded partitions, bias image)
+  auto attn_fuses_qkv = [&](int i, int bk) -> bool {
+    const StageGeom& g = pl->st[i];
+    const KvqSwinBlockW& bw = w->blocks[bk];
+    return bw.bias_dense && bw.qkv_b && g.Lp == g.L && g.C == 96 && g.N <= 400;
+  };
   bool x16[KVQ_MAX_STAGES] = {false, false, false, false};
   if (resid16_on && !any_tap) {
     // a stage-split call (KSVQE: stages 0-1, modulation, stage 2, modulation, stage 3) takes its entry stream from `io` in fp32 and hands the
@@ -511,11 +519,11 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
       // the producer writes fp16: the embedding, the fused merge, or — fp16 OPERANDS only: its 16-bit store is then the stream's type — the
       // reduction GEMM of an un-fused merge (Swin-B's stage 2, 18 of its 24 blocks, sits behind one)
       const bool produced16 = i == 0 ? (stage_lo == 0 && embed_fused) : (i > stage_lo && (fused_merge(i - 1) || pl->dtype == KVQ_DT_FP16));
-      bool ok = g.C <= tail_maxc_x && g.C <= resid16_maxc && produced16;
+      bool ok = produced16;
       for (int b = 0; ok && b < g.depth; ++b) {
         const KvqSwinBlockW& bw = w->blocks[blk0 + b];
         const int par = (b & 1) && g.shifted_any ? 1 : 0;
-        ok = bw.tail_pack && kvq_block_tail_supported(g.C, cfg.mlp_ratio * g.C) && bw.norm1_w && bw.norm1_b && g.d_dst[par];
+        ok = fused_tail(i, blk0 + b) && bw.norm1_w && bw.norm1_b && g.d_dst[par];
       }
       x16[i] = ok;
     }
@@ -534,7 +542,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
   if (stage_lo > 0) {
     const StageGeom& g0 = pl->st[stage_lo];
     KVQ_CHECK_HIP(hipMemcpyAsync(xa, io, (size_t)B * g0.L * g0.C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else if (w->embed_pack && kvq_patch_embed_supported(cfg.in_chans, cfg.patch[0], cfg.patch[1], cfg.patch[2], E, pl->T, pl->H, pl->W)) {
+  } else if (embed_fused) {
     KvqPatchEmbedArgs ea{};
     ea.x = x; ea.frag = frag; ea.B = B; ea.in_chans = cfg.in_chans; ea.T = pl->T; ea.H = pl->H; ea.W = pl->W;
     ea.pd = cfg.patch[0]; ea.ph = cfg.patch[1]; ea.pw = cfg.patch[2]; ea.embed_dim = E; ea.pack = w->embed_pack;
@@ -595,7 +603,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
       // back): the attention workgroup of a (window, head) computes its own q | k | v from the norm1 rows (attn.hip,
       // fused_qkv_prologue).  Un-padded partitions on the dense bias only.  Measured (bench.py --legs c2,no_sampler, two runs each,
       // same box): 300.4 -> 314.6 videos/s with the sampler in the step, 315.5 -> 330.1 without; stage-0 launch 133.5 -> 117.3 us.
-      const bool fuse_qkv = bw.bias_dense && bw.qkv_b && g.Lp == g.L && C == 96 && g.N <= 400;      // by geometry only, never by batch
+      const bool fuse_qkv = attn_fuses_qkv(i, blk);
       // attn32.hip (bias image) keeps its scores in log2 units: q is scaled by head_dim^-0.5 * log2(e) there; the gather path takes
       // head_dim^-0.5.  Which one a block takes depends on its weights and geometry only, never on the batch.
       const float qs = bw.bias_dense ? kQScaleLog2 : kQScale;
@@ -643,9 +651,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
                                      st));
       }
       const int hidden = cfg.mlp_ratio * C;
-      // KVQ_TAIL_MAXC: widest stage that takes the fused tail launch (wider ones run proj / norm2 / fc1 / fc2 as a GEMM chain)
-      static const int tail_maxc = getenv("KVQ_TAIL_MAXC") ? atoi(getenv("KVQ_TAIL_MAXC")) : 1 << 30;
-      if (bw.tail_pack && C <= tail_maxc && kvq_block_tail_supported(C, hidden)) {
+      if (fused_tail(i, blk)) {
         // proj + window_reverse + roll back + crop + residual + norm2 + Mlp + residual [+ the next block's norm1]
         KvqBlockTailArgs ta{};
         ta.attn = bo; ta.x = cur; ta.scatter_map = g.d_src[par]; ta.map_rows = g.Lp; ta.out_rows = g.L;
@@ -660,9 +666,8 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
         // Round 5: a padded partition takes the next block's q | k | v from this launch too (token -> window row of the NEXT partition,
         // rows of Lp per clip; the padding rows are written by the attention launch, pad_mask) — the LayerNorm launch, the qkv GEMM and
         // the norm1 round trip of every block of Swin-B at 64 x 256 x 256 are gone (C5 23.8 -> 25.05 videos/s, +5.2 %, same box alternating: profiles/r05_padded_qkv_ab.txt);
-        // the C = 512 tail in hidden chunks of 128 emits without the spills the comment above met.  KVQ_TAIL_QKV_PADDED=0: the old sequence.
-        static const bool tail_qkv_padded = !(getenv("KVQ_TAIL_QKV_PADDED") && atoi(getenv("KVQ_TAIL_QKV_PADDED")) == 0);
-        const bool padded_qkv = g.Lp != g.L && tail_qkv_padded && b + 1 < g.depth && g.d_dst[npar] && g.d_padmask[npar] && w->blocks[blk + 1].bias_dense;
+        // the C = 512 tail in hidden chunks of 128 emits without the spills the comment above met.
+        const bool padded_qkv = g.Lp != g.L && b + 1 < g.depth && g.d_dst[npar] && g.d_padmask[npar] && w->blocks[blk + 1].bias_dense;
         const int32_t* nmap = (g.Lp == g.L || padded_qkv) ? g.d_dst[npar] : nullptr;
         if (b + 1 < g.depth && nmap) {
           const KvqSwinBlockW& nb = w->blocks[blk + 1];
@@ -670,10 +675,8 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
           ta.next_norm_w = nb.norm1_w; ta.next_norm_b = nb.norm1_b; ta.next_dst = nmap;
           ta.next_rows = g.Lp;
           // the next block's q | k | v straight from this launch (C = 128 / 192 / 256 / 384 / 512, un-padded partitions, the image path's q scale):
-          // no norm1 rows, no qkv GEMM launch.  By geometry and weights only, never by batch.  KVQ_TAIL_QKV=0: rounds 1-4's sequence.
-          static const bool tail_qkv = !(getenv("KVQ_TAIL_QKV") && atoi(getenv("KVQ_TAIL_QKV")) == 0);
-          const bool next_fuses = nb.bias_dense && nb.qkv_b && g.Lp == g.L && C == 96 && g.N <= 400;      // its attention launch projects q | k | v itself
-          if (tail_qkv && !next_fuses && nb.qkv_pack && nb.qkv_b && nb.bias_dense && (g.Lp == g.L || padded_qkv) && kvq_block_tail_qkv_pack_bytes(C, hidden) > 0) {
+          // no norm1 rows, no qkv GEMM launch (unless its attention launch projects q | k | v itself).  By geometry and weights only, never by batch.
+          if (!attn_fuses_qkv(i, blk + 1) && nb.qkv_pack && nb.qkv_b && nb.bias_dense && (g.Lp == g.L || padded_qkv) && kvq_block_tail_qkv_pack_bytes(C, hidden) > 0) {
             ta.next_qkv_pack = nb.qkv_pack; ta.next_qkv_b = nb.qkv_b; ta.qkv_out = bbig; ta.q_scale = kQScaleLog2; ta.num_heads = g.nH;
             qkv_ready = true;
           } else if (g.Lp == g.L) {
@@ -713,12 +716,11 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
       const KvqSwinMergeW& mw = w->merges[i];
       KVQ_REQUIRE(mw.norm_w && mw.norm_b && mw.red_w, KVQ_ERR_NULL, "kvq_swin3d_forward: merge %d weights missing", i);
       const int Ln = g.Dn * g.Hn * g.Wn;
-      static const int merge_maxc = getenv("KVQ_MERGE_MAXC") ? atoi(getenv("KVQ_MERGE_MAXC")) : 192;      // 128 = rounds 4's gate (the C = 192 merge as three launches)
-      if (mw.merge_pack && kvq_patch_merge_supported(C) && C <= merge_maxc) {
+      if (fused_merge(i)) {
         // concat + LayerNorm(4C) + reduction [+ the next stage's first norm1 in its window order] as one launch (csrc/merge.hip).
         // C = 96: 37.5 us against 26.3 + 25.6 + 15.9 (Swin-T, 4 clips); C = 128: +0.5-1 % on C5.  C = 192 exists and is tested, but
         // the 576 KB matrix streams through LDS for 98 workgroups of one wave per SIMD: 66.9 us against 16.2 + 24.8 + 15.3 alone on the chip;
-        // taken since round 5 (merge_maxc = 192): level on the 4-lane line with two launches fewer (profiles/r05_lane_experiments.txt)
+        // taken since round 5: level on the 4-lane line with two launches fewer (profiles/r05_lane_experiments.txt)
         KvqPatchMergeArgs ma{};
         ma.x = cur; ma.merge_map = g.d_merge; ma.B = B; ma.L = g.L; ma.Ln = Ln; ma.C = C; ma.pack = mw.merge_pack; ma.out = oth;
         ma.eps = 1e-5f; ma.dtype = pl->dtype; ma.x_f16 = x16_cur ? 1 : 0; ma.out_f16 = x16[i + 1] ? 1 : 0;

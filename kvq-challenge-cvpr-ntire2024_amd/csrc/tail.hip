@@ -47,12 +47,6 @@ __host__ __device__ constexpr int tail_bpc(int C, int NW) { return (C == 96 ? 12
 __host__ __device__ constexpr int tail_ring(int C, int NW) {                            // ring slots: what LDS allows, <= 4
   return (163840 / tail_bpc(C, NW) - 8192) / tail_slot_bytes(C) >= 4 ? 4 : 3;
 }
-// Row staging (round 5): the x / attention / norm1 rows of a wave travel global <-> LDS as 128-byte row segments (8 rows per wave-load:
-// 8 cache lines per access instead of 32 lane-rows) through a 4 KB tile per wave and are transposed there to the token-per-lane layout.
-// Prologue: the tile lives in the LAST ring slot (empty until the first item is consumed) + TAIL_STAGE_EXTRA bytes behind the ring where
-// a slot is smaller than the four tiles; epilogue: in the slots the ring has left.
-constexpr int TAIL_STG = 4096;
-__host__ __device__ constexpr int tail_stage_extra(int C, int NW) { return NW * TAIL_STG > tail_slot_bytes(C) ? NW * TAIL_STG - tail_slot_bytes(C) : 0; }
 static size_t tail_items(int C, int hidden) { return (size_t)tail_proj_items(C) + 1 + hidden / 32; }
 static size_t tail_param_bytes(int C, int hidden) { return (((size_t)(4 * C + hidden) * 4) + 4095) & ~(size_t)4095; }
 
@@ -123,7 +117,7 @@ __global__ void tail_pack_kernel(const uint16_t* wp, const uint16_t* w1, const u
 // 82 / 76, NW = 6 136 / -, NW = 8 - / 76, NW = 12 124 / -: the L2 -> LDS weight stream (1.7 KB per token at NW = 4) is
 // NOT the bound — the wider barrier domain costs more than the halved stream saves — so workgroups stay at 4 waves,
 // 3 (C = 96, <= 168 VGPRs) or 2 of them per CU.
-template <typename E, int CM, int NW, int MODE, bool STAGED>      // MODE 0: x only; 1: + the next block's norm1 rows; 2: + the next block's q | k | v
+template <typename E, int CM, int NW, int MODE>      // MODE 0: x only; 1: + the next block's norm1 rows; 2: + the next block's q | k | v
 __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_kernel(TailParams p) {
   constexpr bool EMIT = MODE != 0, QKV = MODE == 2;
   fp16_saturate_mode();
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   static_assert(NST == 3 || NST == 4, "wait ladder below");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   using V8 = typename E::v8;
-  constexpr int XTRA = STAGED ? tail_stage_extra(C, NW) : 0, PRM_OFF = NST * SLOT + XTRA;      // the lane-per-row form asks for no staging bytes
+  constexpr int PRM_OFF = NST * SLOT;
   float* prm = reinterpret_cast<float*>(lds + PRM_OFF);
   const float* s_pb = prm;
   const float* s_g2 = prm + C;
@@ -188,13 +182,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   const long orig = (long)tb * p.out_rows + tloc;
   V8 bx[KS];
   f32x16 acc[CM];
-  // row-major role of this lane in a staged 128-byte-per-row tile: row 8 g + rrow (g = 0..3), 16-byte piece rp; piece p of row r sits
-  // in slot 8 r + (p ^ ((r >> 1) & 7)) — both the row-major and the token-per-lane accesses are bank-conflict-free
-  const int rrow = lane >> 3, rp = lane & 7, tj = lane & 31;
-  auto stg_at = [](unsigned char* base, int row, int piece) __attribute__((always_inline)) -> unsigned char* {
-    return base + ((row * 8 + (piece ^ ((row >> 1) & 7))) << 4);
-  };
-  if (!STAGED) {
+  {
     const uint16_t* ar = p.attn + (size_t)rc * C + 8 * h;
 #pragma unroll
     for (int s = 0; s < KS; ++s) bx[s] = *reinterpret_cast<const V8*>(ar + 16 * s);
@@ -245,62 +233,6 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
 #pragma unroll
   for (int i = 0; i < NST - 1; ++i) issue(i, i);
   if (EMIT && tid < C / 2) *reinterpret_cast<f32x4*>(s_nn + 4 * tid) = nn_reg;
-  if (STAGED) {
-    // the wave's 4 KB tile in the last ring slot (+ the extra bytes behind the ring): free until the first item has been consumed — the
-    // first next_item() below fills that slot only after its barrier, which every wave reaches with its prologue behind it
-    unsigned char* stg = lds + (NST - 1) * SLOT + wave * TAIL_STG;
-    int rowx[4], rowa[4];          // residual-stream row / attention row of the tile rows 8 g + rrow
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      rowx[g] = __shfl((int)orig, 8 * g + rrow);
-      rowa[g] = __shfl((int)rc, 8 * g + rrow);
-    }
-    // ---- attention rows (16-bit): 64 channels = 128 bytes of a row per tile = 4 k-steps; C % 64 == 32: a last half tile ----
-    constexpr int AT = C / 64, AH = (C % 64) / 32;
-    u32x4 va[AT + AH][4];
-#pragma unroll
-    for (int t = 0; t < AT + AH; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        va[t][g] = (u32x4){0u, 0u, 0u, 0u};
-        if (t < AT || rp < 4) va[t][g] = *reinterpret_cast<const u32x4*>(p.attn + (size_t)rowa[g] * C + 64 * t + 8 * rp);
-      }
-    // ---- residual rows (fp32): 32 channels = 128 bytes per tile ----
-    const float* pbg = reinterpret_cast<const float*>(p.pack + (size_t)NI * SLOT) + 4 * h;
-    constexpr int XB = CM > 3 ? 3 : CM;                 // tiles requested at once (12 x 16 B per lane in flight)
-#pragma unroll
-    for (int i0 = 0; i0 < CM; i0 += XB) {
-      f32x4 vx[XB][4];
-#pragma unroll
-      for (int i = i0; i < i0 + XB && i < CM; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          vx[i - i0][g] = *reinterpret_cast<const f32x4*>(p.x + (size_t)rowx[g] * C + 32 * i + 4 * rp);
-        }
-      if (i0 == 0) {
-#pragma unroll
-        for (int t = 0; t < AT + AH; ++t) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) *reinterpret_cast<u32x4*>(stg_at(stg, 8 * g + rrow, rp)) = va[t][g];
-#pragma unroll
-          for (int k = 0; k < (t < AT ? 4 : 2); ++k)
-            bx[4 * t + k] = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(stg_at(stg, tj, 2 * k + h)));
-        }
-      }
-#pragma unroll
-      for (int i = i0; i < i0 + XB && i < CM; ++i) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(stg_at(stg, 8 * g + rrow, rp)) = vx[i - i0][g];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(stg_at(stg, tj, 2 * q + h));
-          const f32x4 b = *reinterpret_cast<const f32x4*>(pbg + 32 * i + 8 * q);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[i][4 * q + e] = v[e] + b[e];
-        }
-      }
-    }
-  }
   int it = 0, slot = 0;
   // item `it` visible to every wave; everybody has left item it-1, whose slot takes item it+NST-1
 #ifdef KVQ_TAIL_TRACE
@@ -466,26 +398,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
       for (int e = 0; e < 4; ++e) acc[i][4 * q + e] += fb[e];
       if (q & 1) __builtin_amdgcn_sched_barrier(0);
     }
-  // STAGED: the wave's tile in slots the ring has left — the last item sits in slot (NI - 1) % NST, every other slot is free (the barrier
-  // of the last next_item() lies behind every wave's last read of the item before it); launch_tail checks that four tiles fit
-  const int s_last = (NI - 1) % NST;
-  unsigned char* stg2 = lds + ((NST - 1 - s_last) * SLOT + XTRA >= NW * TAIL_STG ? (s_last + 1) * SLOT : 0) + wave * TAIL_STG;
-  if (STAGED) {
-    int rowx[4];                   // residual-stream row of the tile rows 8 g + rrow, < 0: not stored (re-derived: nothing of the prologue stays live)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) rowx[g] = __shfl(live ? (int)orig : -1, 8 * g + rrow);
-#pragma unroll
-    for (int i = 0; i < CM; ++i) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f32x4*>(stg_at(stg2, tj, 2 * q + h)) = (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(stg_at(stg2, 8 * g + rrow, rp));
-        if (rowx[g] >= 0) *reinterpret_cast<f32x4*>(p.x + (size_t)rowx[g] * C + 32 * i + 4 * rp) = t;
-      }
-    }
-  } else if (live && p.x16) {
+  if (live && p.x16) {
     uint16_t* xr = reinterpret_cast<uint16_t*>(p.x) + (size_t)orig * C + 4 * h;
 #pragma unroll
     for (int i = 0; i < CM; ++i)
@@ -583,11 +496,6 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
       }
     }
     uint16_t* o = p.next_ln + (size_t)drow * C;
-    int rowd[4];
-    if (STAGED) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) rowd[g] = __shfl(live ? (int)drow : -1, 8 * g + rrow);
-    }
 #pragma unroll
     for (int i = 0; i < (QKV ? 0 : CM); ++i) {
 #pragma unroll
@@ -607,16 +515,8 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
         const auto s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
         const u32x4 piece = {s0[0], s1[0], s0[1], s1[1]};
-        if (STAGED) *reinterpret_cast<u32x4*>(stg_at(stg2, tj, 4 * (i & 1) + 2 * t + h)) = piece;      // 128-byte row tile = channel tiles (i, i + 1)
-        else if (live) *reinterpret_cast<u32x4*>(o + 32 * i + 8 * (2 * t + h)) = piece;
+        if (live) *reinterpret_cast<u32x4*>(o + 32 * i + 8 * (2 * t + h)) = piece;
         __builtin_amdgcn_sched_barrier(0);
-      }
-      if (STAGED && ((i & 1) || i == CM - 1)) {          // a row tile is complete: 8 rows x 128 (or a last 64) bytes per wave-store
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const u32x4 v = *reinterpret_cast<const u32x4*>(stg_at(stg2, 8 * g + rrow, rp));
-          if (rowd[g] >= 0 && ((i & 1) || rp < 4)) *reinterpret_cast<u32x4*>(p.next_ln + (size_t)rowd[g] * C + 64 * (i >> 1) + 8 * rp) = v;
-        }
       }
     }
   }
@@ -632,17 +532,9 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
 
 template <typename E, int CM, int NW>
 static int launch_tail(const TailParams& p, hipStream_t st) {
-  constexpr int C = 32 * CM, NST = tail_ring(C, NW), SLOT = tail_slot_bytes(C), XTRA = tail_stage_extra(C, NW);
-  // KVQ_TAIL_STAGED=1: the x / attention / norm1 rows travel as 128-byte row segments through an LDS transpose (round 5, the review's
-  // "coalesced row traffic"; bit-identical results).  Built, tested and measured — and OFF by default: the C = 96 launches take 97.6 /
-  // 88.5 us against 93.1 / 87.5, the C = 192 ones 86.3 / 77.6 against 87.4 / 80.3, the 4-lane C2 line 355.7 / 358.6 against 360.0 /
-  // 360.7 videos/s (profiles/r05_tail_staged_ab.txt): a quarter of the row-divergent global accesses per wave buys nothing, so the
-  // lane-per-row accesses are NOT what these launches wait for (round 4's reading of the merge launch does not carry over).
-  static const bool staged_on = getenv("KVQ_TAIL_STAGED") && atoi(getenv("KVQ_TAIL_STAGED")) == 1;
-  // the epilogue's four tiles need NW * 4 KB of ring slots (+ the extra bytes) that do not hold the last item
-  const int NI = tail_proj_items(C) + 1 + p.hidden / 32, s_last = (NI - 1) % NST;
-  const bool staged = staged_on && !p.x16 && ((NST - 1 - s_last) * SLOT + XTRA >= NW * TAIL_STG || s_last * SLOT >= NW * TAIL_STG);
-  const size_t lds = (size_t)NST * SLOT + (staged ? XTRA : 0) + ((((size_t)(4 * C + p.hidden) * 4) + 1023) & ~(size_t)1023) + (size_t)2 * C * 4;
+  constexpr int C = 32 * CM, NST = tail_ring(C, NW), SLOT = tail_slot_bytes(C);
+  // (the rows are read and written lane per row: an LDS-transposed form of round 5 bought nothing, profiles/r05_tail_staged_ab.txt)
+  const size_t lds = (size_t)NST * SLOT + ((((size_t)(4 * C + p.hidden) * 4) + 1023) & ~(size_t)1023) + (size_t)2 * C * 4;
   KVQ_REQUIRE(lds <= (size_t)163840 / tail_bpc(C, NW), KVQ_ERR_UNSUPPORTED, "kvq_block_tail: %zu B of LDS", lds);
   dim3 grid((unsigned)ceil_div(p.gather ? p.n_tok : p.M, 32 * NW)), block(64 * NW);
   auto go = [&](auto k) -> int {
@@ -652,10 +544,10 @@ static int launch_tail(const TailParams& p, hipStream_t st) {
   };
   int rc;
   if (p.qkv_out) {
-    KVQ_REQUIRE(!staged && (3 * C / 32) % 2 == 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: q | k | v emission with staged rows / an odd panel count");
-    rc = go(block_tail_kernel<E, CM, NW, 2, false>);
-  } else if (p.next_ln) rc = staged ? go(block_tail_kernel<E, CM, NW, 1, true>) : go(block_tail_kernel<E, CM, NW, 1, false>);
-  else rc = staged ? go(block_tail_kernel<E, CM, NW, 0, true>) : go(block_tail_kernel<E, CM, NW, 0, false>);
+    KVQ_REQUIRE((3 * C / 32) % 2 == 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: q | k | v emission with an odd panel count");
+    rc = go(block_tail_kernel<E, CM, NW, 2>);
+  } else if (p.next_ln) rc = go(block_tail_kernel<E, CM, NW, 1>);
+  else rc = go(block_tail_kernel<E, CM, NW, 0>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("block_tail_kernel");
   return KVQ_OK;

@@ -30,10 +30,13 @@
 #include "common.hpp"
 #include "tail.hpp"
 
-// The 42 instantiations of the kernel take ~5 minutes in one translation unit: the build (_build.py) compiles this file FOUR times with
+// The 36 instantiations of the kernel take minutes in one translation unit: the build (_build.py) compiles this file FOUR times with
 // -DKVQ_TAILMM_PART=0..3 — part 0 holds the host side (packing, dispatch) and the C = 384 product form, parts 1-3 the other forms —
 // and links the four objects; without the macro (study builds, a plain `hipcc -c`) everything is one unit.
 #ifdef KVQ_TAILMM_PART
+#if KVQ_TAILMM_PART < 0 || KVQ_TAILMM_PART > 3
+#error "KVQ_TAILMM_PART must be 0, 1, 2 or 3 (the four translation units of _build.py's PARTS)"
+#endif
 #define MM_PART_HERE(k) (KVQ_TAILMM_PART == (k))
 #else
 #define MM_PART_HERE(k) 1
@@ -55,12 +58,11 @@ typedef __attribute__((address_space(1))) const void* mm_gbl_t;
 //   HC = 128: 32 units (one tile) and a 12-fragment ring: <= 256 VGPRs, 77 KB of LDS at C = 384 — TWO workgroups per CU, i.e. two
 //             independent instruction streams per SIMD: one workgroup's serial phases (row loads, LayerNorm exchanges, GELU, barriers,
 //             the store tail) run under the other's MFMAs (round 5; the per-CU weight stream per token is unchanged).
-//   TT = 4 (round 6): 128 tokens per workgroup — every weight fragment of the register ring feeds FOUR MFMAs (token tiles) instead of two, which
-//             halves the L1 -> VGPR weight stream per MFMA (1 KB per two 32x32x16 is 64 B / clk per CU, the path's limit, at full matrix rate).
-//             192 + 64 accumulator registers: ONE wave per SIMD, 142 KB of LDS at C = 384 (HC = 128).
-template <int CF, int HC_ = 256, int TT_ = 2>
+// A workgroup is 64 tokens (two token tiles of 32).  The 128-token form of round 6 (every weight fragment feeding four MFMAs, one wave per
+// SIMD) lost 3-4 % on the line and was removed: profiles/r06_tailmm_study.txt, profiles/r06_knob_sweep.txt.
+template <int CF, int HC_ = 256>
 struct MMc {
-  static constexpr int TT = TT_, TOK = 32 * TT_;                        // token tiles of 32, tokens per workgroup
+  static constexpr int TT = 2, TOK = 32 * TT;                           // token tiles of 32, tokens per workgroup
   static constexpr int C = 128 * CF, H = 4 * C, W = 32 * CF;            // channels, hidden units, features per wave
   static constexpr int HC = HC_, KS_H = HC / 16, HT = HC / 128;         // hidden chunk, its k-steps, fc1 tiles per wave
   static constexpr int NCH = H / HC, KS_C = C / 16;                     // hidden chunks, k-steps over C
@@ -75,7 +77,7 @@ struct MMc {
   static constexpr int WG_PER_CU = HC == 128 && 2 * LDS <= 163840 ? 2 : 1;
   // register budget in waves per SIMD: the HC = 128 forms up to C = 512 keep to 256 VGPRs so that another workgroup (C = 384: of this launch;
   // C = 512, 97 KB of LDS: of another lane's launch) fits beside them; C = 768 needs 192 accumulator registers and takes the whole file
-  static constexpr int REG_WAVES = HC == 128 && CF <= 4 && TT == 2 ? 2 : 1;
+  static constexpr int REG_WAVES = HC == 128 && CF <= 4 ? 2 : 1;
 #ifndef KVQ_TAILMM_KU1
 #define KVQ_TAILMM_KU1 1
 #endif
@@ -91,34 +93,19 @@ struct MMc {
 };
 
 #if MM_PART_HERE(0)
-// KVQ_TAILMM_HC=256 takes rounds 2-4's one-workgroup-per-CU form at C = 384 (A/B runs); read once — the packed image and the launch
-// must agree.  C = 512 (Swin-B stage 2, the C5 line) takes HC = 128 too: 2 x 97 KB of LDS do not fit, so it is still one workgroup of
-// this launch per CU, but at 256 registers and no spills (HC = 256 at C = 512: 512 registers, 8 / 17 / 115 spilled by MODE) a workgroup
-// of another lane's launch fits beside it — C5 22.98 -> 23.46 videos/s, same box, alternating (profiles/r05_hc512_ab.txt);
-// KVQ_TAILMM_HC512=256 is the old form.  C = 256 keeps HC = 256 (not on any benchmarked path).
-static int tailmm_hc(int C) {
-  static const int env = getenv("KVQ_TAILMM_HC") ? atoi(getenv("KVQ_TAILMM_HC")) : (latency_mode() ? 256 : 128);
-  static const int env512 = getenv("KVQ_TAILMM_HC512") ? atoi(getenv("KVQ_TAILMM_HC512")) : (latency_mode() ? 256 : 128);
-  if (C == 512) return env512 == 128 ? 128 : 256;
-  return C == 384 && env == 128 ? 128 : 256;
-}
-
-// KVQ_TAILMM_TOK=128 (round 6): the 128-token workgroup at C = 384, HC = 128 (same packed image: the fragment lists do not depend on it)
-static int tailmm_tok(int C) {
-  static const int env = getenv("KVQ_TAILMM_TOK") ? atoi(getenv("KVQ_TAILMM_TOK")) : 64;
-  return C == 384 && env == 128 ? 128 : 64;
-}
+// C = 384 takes HC = 128 (two workgroups per CU; rounds 2-4's one-workgroup-per-CU HC = 256 form is the latency form, KVQ_LATENCY=1).  The
+// packed image and the launch must agree: both ask this function.  C = 512 (Swin-B stage 2, the C5 line) takes HC = 128 too: 2 x 97 KB of
+// LDS do not fit, so it is still one workgroup of this launch per CU, but at 256 registers and no spills (HC = 256 at C = 512: 512 registers,
+// 8 / 17 / 115 spilled by MODE) a workgroup of another lane's launch fits beside it — C5 22.98 -> 23.46 videos/s, same box, alternating
+// (profiles/r05_hc512_ab.txt).  C = 256 keeps HC = 256 (not on any benchmarked path).
+static int tailmm_hc(int C) { return (C == 384 || C == 512) && !latency_mode() ? 128 : 256; }
 
 // C = 768 (round 5: stage 3 of Swin-T / -S; CF = 6, HC = 128, one workgroup per CU: 137 KB of LDS, 192 accumulator registers per wave).  At
 // 4 clips it is a launch of 49 workgroups that takes 193-254 us where the GEMM / LayerNorm launches it replaces take 115 us ALONE on the
 // chip — and the 4-lane bench line gains 4.5 % (370.9 / 373.3 / 368.3 -> 389.5 / 386.4 / 386.1 videos/s, same box, alternating;
 // profiles/r05_tail768_ab.txt): in the mix what a launch costs is CU x time, not its latency, and 49 busy CUs for 250 us are a third of
-// five thin launches spread over the chip.  KVQ_TAILMM_768=0: the GEMM chain.
-static bool tailmm_768() {
-  static const bool on = getenv("KVQ_TAILMM_768") ? atoi(getenv("KVQ_TAILMM_768")) != 0 : !latency_mode();
-  return on;
-}
-bool tailmm_supported(int C, int hidden) { return (C == 256 || C == 384 || C == 512 || (C == 768 && tailmm_768())) && hidden == 4 * C; }
+// five thin launches spread over the chip.  KVQ_LATENCY=1: the GEMM chain.
+bool tailmm_supported(int C, int hidden) { return (C == 256 || C == 384 || C == 512 || (C == 768 && !latency_mode())) && hidden == 4 * C; }
 size_t tailmm_pack_bytes(int C, int hidden) {
   if (!tailmm_supported(C, hidden)) return 0;
   const size_t frag = C == 384 ? (tailmm_hc(C) == 128 ? MMc<3, 128>::PACK_FRAG_BYTES : MMc<3>::PACK_FRAG_BYTES)
@@ -251,11 +238,11 @@ int tailmm_qkv_pack(const uint16_t* qkv_w, int C, int hidden, unsigned char* out
 // no MFMAs 57, neither 43 of 78 — removed in round 3: 79 -> 73 us with the next norm1, 73 -> 64 without, bit-identical.)
 template <int N> struct TokVec { float v[N]; __device__ __forceinline__ float operator[](int i) const { return v[i]; } };
 
-template <typename E, int MODE, int CF = 3, int HC = 256, int TT = 2>      // MODE 0: x only; 1: + the next block's norm1 rows; 2: + the next block's q | k | v
-__global__ __launch_bounds__(256, (MMc<CF, HC, TT>::REG_WAVES)) void block_tailmm_kernel(TailParams p) {
+template <typename E, int MODE, int CF = 3, int HC = 256>      // MODE 0: x only; 1: + the next block's norm1 rows; 2: + the next block's q | k | v
+__global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_kernel(TailParams p) {
   constexpr bool EMIT = MODE == 1, QKV = MODE == 2;
-  using K = MMc<CF, HC, TT>;
-  constexpr int MM_TOK = K::TOK;
+  using K = MMc<CF, HC>;
+  constexpr int MM_TOK = K::TOK, TT = K::TT;
   using TV = TokVec<TT>;                             // one value per token tile of the lane
   constexpr int MM_C = K::C, MM_H = K::H, MM_NCH = K::NCH, MM_KS_C = K::KS_C, MM_NF = K::NF, VR_R = K::VR_R, VR_PF = K::VR_PF, FW = K::W;
   constexpr int MM_HC = K::HC, MM_KS_H = K::KS_H, HT = K::HT;
@@ -574,7 +561,6 @@ __global__ __launch_bounds__(256, (MMc<CF, HC, TT>::REG_WAVES)) void block_tailm
       MM_T1(t_fc2);
     }
   } else {
-    static_assert(TT == 2, "the software-pipelined chunks are the 64-token form");
     fc1(0);
   #pragma unroll
     for (int pi = 0; pi < 16 * HT; ++pi) gelu_pair(pi);
@@ -708,10 +694,10 @@ __global__ __launch_bounds__(256, (MMc<CF, HC, TT>::REG_WAVES)) void block_tailm
   MM_STAMP(4);
 }
 
-template <typename E, int CF, int HC = 256, int TT = 2>
+template <typename E, int CF, int HC = 256>
 static int launch_mm_cf(const TailParams& p, hipStream_t st) {
-  constexpr int LDS = MMc<CF, HC, TT>::LDS;
-  dim3 grid((unsigned)ceil_div(p.gather ? p.n_tok : p.M, MMc<CF, HC, TT>::TOK)), block(256);
+  constexpr int LDS = MMc<CF, HC>::LDS;
+  dim3 grid((unsigned)ceil_div(p.gather ? p.n_tok : p.M, MMc<CF, HC>::TOK)), block(256);
   auto go = [&](auto k) -> int {
     LdsOptIn opt;
     if (int rc = opt.ensure(reinterpret_cast<const void*>(k), LDS)) return rc;
@@ -719,9 +705,9 @@ static int launch_mm_cf(const TailParams& p, hipStream_t st) {
     return KVQ_OK;
   };
   int rc;
-  if (p.qkv_out) rc = go(block_tailmm_kernel<E, 2, CF, HC, TT>);
-  else if (p.next_ln) rc = go(block_tailmm_kernel<E, 1, CF, HC, TT>);
-  else rc = go(block_tailmm_kernel<E, 0, CF, HC, TT>);
+  if (p.qkv_out) rc = go(block_tailmm_kernel<E, 2, CF, HC>);
+  else if (p.next_ln) rc = go(block_tailmm_kernel<E, 1, CF, HC>);
+  else rc = go(block_tailmm_kernel<E, 0, CF, HC>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("block_tailmm_kernel");
   return KVQ_OK;
@@ -732,39 +718,38 @@ int tailmm_launch_part0(int form, const TailParams& p, int dtype, hipStream_t st
 int tailmm_launch_part1(int form, const TailParams& p, int dtype, hipStream_t st);
 int tailmm_launch_part2(int form, const TailParams& p, int dtype, hipStream_t st);
 int tailmm_launch_part3(int form, const TailParams& p, int dtype, hipStream_t st);
-enum { MM_F_C512_H128, MM_F_C512_H256, MM_F_C768, MM_F_C256, MM_F_C384_T128, MM_F_C384_H128, MM_F_C384_H256 };
-#define MM_GO(CF, HC, TT) (dtype == KVQ_DT_FP16 ? launch_mm_cf<Fp16, CF, HC, TT>(p, st) : launch_mm_cf<Bf16, CF, HC, TT>(p, st))
+enum { MM_F_C512_H128, MM_F_C512_H256, MM_F_C768, MM_F_C256, MM_F_C384_H128, MM_F_C384_H256 };
+#define MM_GO(CF, HC) (dtype == KVQ_DT_FP16 ? launch_mm_cf<Fp16, CF, HC>(p, st) : launch_mm_cf<Bf16, CF, HC>(p, st))
 #ifndef KVQ_TAILMM_FOCUS
 #if MM_PART_HERE(0)
-int tailmm_launch_part0(int form, const TailParams& p, int dtype, hipStream_t st) { return MM_GO(3, 128, 2); }                                 // C = 384: the C2 line's form
+int tailmm_launch_part0(int form, const TailParams& p, int dtype, hipStream_t st) { return MM_GO(3, 128); }                                 // C = 384: the C2 line's form
 #endif
 #if MM_PART_HERE(1)
-int tailmm_launch_part1(int form, const TailParams& p, int dtype, hipStream_t st) { return form == MM_F_C384_H256 ? MM_GO(3, 256, 2) : MM_GO(2, 256, 2); }
+int tailmm_launch_part1(int form, const TailParams& p, int dtype, hipStream_t st) { return form == MM_F_C384_H256 ? MM_GO(3, 256) : MM_GO(2, 256); }
 #endif
 #if MM_PART_HERE(2)
-int tailmm_launch_part2(int form, const TailParams& p, int dtype, hipStream_t st) { return form == MM_F_C512_H128 ? MM_GO(4, 128, 2) : MM_GO(4, 256, 2); }
+int tailmm_launch_part2(int form, const TailParams& p, int dtype, hipStream_t st) { return form == MM_F_C512_H128 ? MM_GO(4, 128) : MM_GO(4, 256); }
 #endif
 #if MM_PART_HERE(3)
-int tailmm_launch_part3(int form, const TailParams& p, int dtype, hipStream_t st) { return form == MM_F_C768 ? MM_GO(6, 128, 2) : MM_GO(3, 128, 4); }
+int tailmm_launch_part3(int form, const TailParams& p, int dtype, hipStream_t st) { return MM_GO(6, 128); }                                   // C = 768
 #endif
 #endif
 
 #if MM_PART_HERE(0)
 int tailmm_geometry_code(int C, int hidden) {
   if (!tailmm_supported(C, hidden)) return 0;
-  const int hc = C == 768 ? 128 : (C == 384 || C == 512) ? tailmm_hc(C) : 256;
-  return (hc / 128) * 10 + (hc == 128 && tailmm_tok(C) == 128 ? 4 : 2);
+  const int hc = C == 768 ? 128 : tailmm_hc(C);
+  return (hc / 128) * 10 + 2;
 }
 
 int tailmm_launch(const TailParams& p, int C, int dtype, hipStream_t st) {
   KVQ_REQUIRE(tailmm_supported(C, p.hidden), KVQ_ERR_UNSUPPORTED, "kvq_block_tail: C=%d hidden=%d", C, p.hidden);
-#ifdef KVQ_TAILMM_FOCUS     // compile-time study builds (register / ISA inspection of one form in seconds instead of minutes), e.g. 3102: CF 3, HC 128, TT 2
-  return launch_mm_cf<Fp16, KVQ_TAILMM_FOCUS / 1000, (KVQ_TAILMM_FOCUS / 10) % 100 * 128 / 10, KVQ_TAILMM_FOCUS % 10>(p, st);
+#ifdef KVQ_TAILMM_FOCUS     // compile-time study builds (register / ISA inspection of one form in seconds instead of minutes), e.g. 310: CF 3, HC 128
+  return launch_mm_cf<Fp16, KVQ_TAILMM_FOCUS / 100, KVQ_TAILMM_FOCUS % 100 * 128 / 10>(p, st);
 #else
   if (C == 512) return tailmm_launch_part2(tailmm_hc(C) == 128 ? MM_F_C512_H128 : MM_F_C512_H256, p, dtype, st);
   if (C == 768) return tailmm_launch_part3(MM_F_C768, p, dtype, st);
   if (C == 256) return tailmm_launch_part1(MM_F_C256, p, dtype, st);
-  if (tailmm_hc(C) == 128 && tailmm_tok(C) == 128) return tailmm_launch_part3(MM_F_C384_T128, p, dtype, st);
   if (tailmm_hc(C) == 128) return tailmm_launch_part0(MM_F_C384_H128, p, dtype, st);
   return tailmm_launch_part1(MM_F_C384_H256, p, dtype, st);
 #endif

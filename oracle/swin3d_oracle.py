@@ -364,7 +364,7 @@ def swin3d_trunk(x: torch.Tensor, params, cfg, return_stages: bool = False, oper
             y = swin_block(y, p, f"layers.{i}.blocks.{b}.", cfg.num_heads[i], cfg.window,
                            (0, 0, 0) if b % 2 == 0 else shift, q, kernel_order and operand_dtype is not None, adaptive_window)
         if i < len(cfg.depths) - 1:
-            if kernel_order and operand_dtype is not None and y.shape[-1] <= merge_fold_max_c:      # csrc/merge.hip (plan.hip KVQ_MERGE_MAXC)
+            if kernel_order and operand_dtype is not None and y.shape[-1] <= merge_fold_max_c:      # csrc/merge.hip (plan.hip: the fused merge up to C = 192)
                 y = patch_merge_kernel_order(y, p, f"layers.{i}.downsample.", q)
             else:
                 y = patch_merge(y, p, f"layers.{i}.downsample.", q)

@@ -26,6 +26,15 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
 
 
+def test_library_reads_only_the_documented_environment_switches():
+    """The library's kernel choice follows its arguments, not the process environment, except for these switches (README.md): the bench's
+    latency leg, the fp32 residual-stream escape hatch, the GEMM tile mode's initial value and three probes of -DKVQ_DIAG builds."""
+    names = set()
+    for f in sorted(os.listdir(_build.CSRC)):
+        names |= set(re.findall(r'getenv\(\s*"(KVQ_[A-Z0-9_]+)"', open(os.path.join(_build.CSRC, f)).read()))
+    assert names == {"KVQ_LATENCY", "KVQ_RESID16", "KVQ_GEMM8P", "KVQ_SKIP", "KVQ_IMAGE_ONE_TYPE", "KVQ_NO_Q_STORE"}, sorted(names)
+
+
 def test_struct_layouts_match_header_sizes():
     import ctypes as C
     assert C.sizeof(_abi.KvqSwinCfg) == 4 * (3 + 1 + 1 + 1 + 4 + 4 + 3 + 1 + 4 + 3)

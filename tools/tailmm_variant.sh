@@ -1,6 +1,6 @@
 #!/bin/bash
 # A tagged study build of the library that differs from the product build in csrc/tailmm.hip only, in seconds:
-#   tools/tailmm_variant.sh <tag> [-DKVQ_TAILMM_FOCUS=3102] [-DKVQ_TAIL_TRACE] [other -D flags]
+#   tools/tailmm_variant.sh <tag> [-DKVQ_TAILMM_FOCUS=310] [-DKVQ_TAIL_TRACE] [other -D flags]
 # every other object is taken from kvq-challenge-cvpr-ntire2024_amd/build/ (the product build must be fresh); the result is
 # libkvq_hip_<tag>.so, loaded with KVQ_BUILD_TAG=<tag>.  With KVQ_TAILMM_FOCUS only ONE form of the kernel exists in the variant.
 set -e
