@@ -518,6 +518,17 @@ int kvq_fragment_gather_batch(const KvqFragmentSource* src, int C, int T, float*
 int kvq_resize_bilinear(const void* video, int src_is_u8, int C, int T, int H, int W, int rh, int rw, int cy,
                         int cx, int oh, int ow, int round_u8, const float* host_mean, const float* host_std,
                         float* out, void* stream);
+/* The same with antialiasing (torchvision >= 0.17's tensor Resize = F.interpolate(bilinear, align_corners=False,
+ * antialias=True)): a separable triangle filter whose support is max(in/out, 1) per axis, width first, fp32.  Same
+ * arguments and output as kvq_resize_bilinear; one launch, no workspace, no host synchronisation.  KVQ_ERR_UNSUPPORTED
+ * for a source row wider than 16 KiB - 15 B or a geometry whose band does not fit the LDS. */
+int kvq_resize_bilinear_aa(const void* video, int src_is_u8, int C, int T, int H, int W, int rh, int rw, int cy,
+                           int cx, int oh, int ow, int round_u8, const float* host_mean, const float* host_std,
+                           float* out, void* stream);
+/* Host evaluation of the tap tables kvq_resize_bilinear_aa builds on the device (the same fp32 code) for one axis
+ * in_size -> out_size: *kmax = the tap capacity per output index; when start / size / weights are given they receive
+ * start[out], size[out] and the normalised weights[out][*kmax] (zero past size). */
+int kvq_resize_aa_taps(int in_size, int out_size, int32_t* kmax, int32_t* start, int32_t* size, float* weights);
 
 /* get_spatial_fragments' fallback for sources smaller than the canvas (fusion_datasets.py:43-50): F.interpolate(video / 255.0,
  * scale_factor = s, mode = "bilinear") * 255.0 cast back to the frame type (uint8: truncation), with ATen's CPU arithmetic to the

@@ -222,6 +222,9 @@ SYMBOLS = {
                                   p_void]),
     "kvq_resize_bilinear": (i32, [p_void, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32),
                                   C.POINTER(f32), p_void, p_void]),
+    "kvq_resize_bilinear_aa": (i32, [p_void, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32),
+                                     C.POINTER(f32), p_void, p_void]),
+    "kvq_resize_aa_taps": (i32, [i32, i32, C.POINTER(i32), p_void, p_void, p_void]),
     "kvq_upsample_frames_out_dims": (i32, [i32, i32, C.c_double, C.POINTER(i32 * 2)]),
     "kvq_upsample_frames": (i32, [p_void, i32, i32, i32, i32, i32, C.c_double, p_void, p_void]),
     "kvq_im2col_nd": (i32, [p_void, i32, i32, C.POINTER(i64 * 5), C.POINTER(i32 * 5), C.POINTER(i32 * 3),

@@ -81,8 +81,10 @@ def get_spatial_fragments(video, fragments_h=7, fragments_w=7, fsize_h=32, fsize
                                    fragments_w, fsize_h, fsize_w, aligned, mean=mean, std=std)
 
 
-def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=False, mean=None, std=None, **kwargs):
-    """Reference ``get_resized_video`` (:244-252) on the GPU: (C,T,H,W) -> (C,T,size_h,size_w), bilinear."""
+def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=False, mean=None, std=None, antialias=False,
+                      **kwargs):
+    """Reference ``get_resized_video`` (:244-252) on the GPU: (C,T,H,W) -> (C,T,size_h,size_w), bilinear; ``antialias``:
+    torchvision >= 0.17's Resize (antialiased) instead of the plain bilinear of earlier releases."""
     if random_crop:
         raise NotImplementedError("RandomResizedCrop is a training augmentation")
     if arp:
@@ -91,27 +93,28 @@ def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=Fals
             size_h = int(ratio * size_w)
         elif ratio < 1:
             size_w = int(size_h / ratio)
-    return kernels.resize_bilinear(video.contiguous(), size_h, size_w, mean=mean, std=std)
+    return kernels.resize_bilinear(video.contiguous(), size_h, size_w, mean=mean, std=std, antialias=antialias)
 
 
-def get_resizecrop_video(video, resize=520, crop=448, phase="test", mean=None, std=None, **kwargs):
+def get_resizecrop_video(video, resize=520, crop=448, phase="test", mean=None, std=None, antialias=False, **kwargs):
     """Reference ``get_resizecrop_video`` (:299-316), test phase: resize to (resize,resize) then the centre
     crop [r//2-crop//2 : r//2+crop//2] — fused with the normalisation in one kernel."""
     if phase == "train":
         raise NotImplementedError("random crop is a training augmentation")
     o = resize // 2 - crop // 2
     n = (resize // 2 + crop // 2) - o
-    return kernels.resize_bilinear(video.contiguous(), resize, resize, crop=(o, o, n, n), mean=mean, std=std)
+    return kernels.resize_bilinear(video.contiguous(), resize, resize, crop=(o, o, n, n), mean=mean, std=std,
+                                   antialias=antialias)
 
 
-def get_single_view(video, sample_type="aesthetic", **kwargs):
-    """Reference ``get_single_view`` (:350-361)."""
+def get_single_view(video, sample_type="aesthetic", antialias=False, **kwargs):
+    """Reference ``get_single_view`` (:350-361); ``antialias`` reaches the two resize views (the fragments have no resize)."""
     if sample_type.startswith("aesthetic"):
-        return get_resized_video(video, **kwargs)
+        return get_resized_video(video, antialias=antialias, **kwargs)
     if sample_type.startswith("technical"):
         return get_spatial_fragments(video, **kwargs)
     if sample_type.startswith("simpleVQA"):
-        return get_resizecrop_video(video, **kwargs)
+        return get_resizecrop_video(video, antialias=antialias, **kwargs)
     raise NotImplementedError
 
 
@@ -169,7 +172,7 @@ class SyntheticSimpleVQADataset(torch.utils.data.Dataset):
         inds = self.sampler(self.frames)
         clip = frames[:, torch.from_numpy(inds.astype(np.int64))].to(self.device)
         view = get_resizecrop_video(clip, self.sopt["resize"], self.sopt["crop"], "test", mean=SIMPLEVQA_MEAN,
-                                    std=SIMPLEVQA_STD)
+                                    std=SIMPLEVQA_STD, antialias=bool(self.sopt.get("antialias", False)))
         return {"simpleVQA": view, "feat": self._feat(i, frames).unsqueeze(0), "num_clips": {"simpleVQA": self.sopt["num_clips"]},
                 "frame_inds": inds, "label": float(self.labels[i]), "name": f"synthetic_{i:05d}",
                 "video_name": f"synthetic_{i:05d}.mp4"}
@@ -524,7 +527,7 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
             data[stype] = get_single_view(video[stype], stype, mean=KVQ_MEAN, std=KVQ_STD, **kw)
             resize = get_resized_video(video[stype], mean=tuple(255.0 * m for m in self.CLIP_MEAN),
                                        std=tuple(255.0 * s for s in self.CLIP_STD),
-                                       **{a: b for a, b in kw.items() if a in ("size_h", "size_w", "random_crop", "arp")})
+                                       **{a: b for a, b in kw.items() if a in ("size_h", "size_w", "random_crop", "arp", "antialias")})
             ori = get_spatial_fragments(video[stype], **{a: b for a, b in kw.items() if a in (
                 "fragments_h", "fragments_w", "fsize_h", "fsize_w", "aligned", "nfrags")})
             k = stype

@@ -784,8 +784,10 @@ def conv_implicit(x: torch.Tensor, W: torch.Tensor, bias, kernel, stride, pad, r
     return (out, out32) if want_f32 else out
 
 
-def resize_bilinear(video: torch.Tensor, rh: int, rw: int, crop=None, mean=None, std=None, round_u8=None):
-    """video u8|fp32 (C,T,H,W) -> bilinear resize to (rh,rw) [-> crop (cy,cx,oh,ow)] [-> (v-mean)/std], fp32."""
+def resize_bilinear(video: torch.Tensor, rh: int, rw: int, crop=None, mean=None, std=None, round_u8=None, antialias=False):
+    """video u8|fp32 (C,T,H,W) -> bilinear resize to (rh,rw) [-> crop (cy,cx,oh,ow)] [-> (v-mean)/std], fp32.
+    ``antialias=True``: F.interpolate(..., antialias=True), what torchvision >= 0.17's Resize does to tensors
+    (``kvq_resize_bilinear_aa``); False: the plain bilinear of torchvision < 0.17 (``kvq_resize_bilinear``)."""
     _need_gpu(video)
     assert video.dtype in (torch.uint8, torch.float32) and video.is_contiguous()
     Cc, T, H, W = video.shape
@@ -794,9 +796,24 @@ def resize_bilinear(video: torch.Tensor, rh: int, rw: int, crop=None, mean=None,
     m = (C.c_float * Cc)(*mean) if mean is not None else None
     s = (C.c_float * Cc)(*std) if std is not None else None
     rnd = int(video.dtype == torch.uint8) if round_u8 is None else int(round_u8)
-    check(lib().kvq_resize_bilinear(ptr(video), int(video.dtype == torch.uint8), Cc, T, H, W, rh, rw, cy, cx, oh, ow,
-                                    rnd, m, s, ptr(out), stream_of(video)), "kvq_resize_bilinear")
+    fn, name = (lib().kvq_resize_bilinear_aa, "kvq_resize_bilinear_aa") if antialias else (lib().kvq_resize_bilinear,
+                                                                                           "kvq_resize_bilinear")
+    check(fn(ptr(video), int(video.dtype == torch.uint8), Cc, T, H, W, rh, rw, cy, cx, oh, ow, rnd, m, s, ptr(out),
+             stream_of(video)), name)
     return out
+
+
+def resize_aa_taps(in_size: int, out_size: int):
+    """The tap tables of one axis of ``resize_bilinear(antialias=True)``, evaluated on the host by the code the kernel runs:
+    (start int32 [out], size int32 [out], weights fp32 [out, kmax]; zero past size)."""
+    import numpy as np
+    k = C.c_int32()
+    check(lib().kvq_resize_aa_taps(in_size, out_size, C.byref(k), None, None, None), "kvq_resize_aa_taps")
+    start, size = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
+    w = np.zeros((out_size, k.value), np.float32)
+    check(lib().kvq_resize_aa_taps(in_size, out_size, C.byref(k), start.ctypes.data, size.ctypes.data, w.ctypes.data),
+          "kvq_resize_aa_taps")
+    return start, size, w
 
 
 def upsample_frames(video: torch.Tensor, scale_factor: float):
