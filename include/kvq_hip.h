@@ -180,6 +180,18 @@ int kvq_swin3d_forward_fragments(const KvqSwinPlan* plan, const KvqSwinWeights* 
 int kvq_swin3d_set_taps(KvqSwinPlan* plan, float* const* taps);
 int kvq_swin3d_tap_dims(const KvqSwinPlan* plan, int index, int32_t out4[4]);
 
+/* Range of the fp16 residual stream (additive in ABI 31).  Where every producer and consumer of a stage's stream takes fp16 rows, the
+ * forward keeps that stage's stream x in fp16, and a value past +-65504 is stored as +-65504: the score is then wrong.
+ * dev_word is NULL (the default: nothing is recorded) or a caller-owned, 4-byte aligned uint32_t in device memory.  Every following
+ * kvq_swin3d_forward, kvq_swin3d_forward_fragments and kvq_swin3d_forward_stages on the plan ORs bit i (i = 0..3) into it, on the
+ * forward's stream, when stage i's fp16 stream held a value whose magnitude reached 65504 (a saturated value, +-inf or NaN).  Stages
+ * whose stream is fp32 never set their bit.  The word is sticky: the library never clears it; the caller zeroes it (on the stream)
+ * before the forwards it wants to judge, and re-runs a flagged input on a plan with kvq_swin3d_plan_set_resid16(plan, 0). */
+int kvq_swin3d_set_range_flags(KvqSwinPlan* plan, uint32_t* dev_word);
+/* on = 0: the plan keeps the residual stream in fp32 in every stage (bit-identical to a process with KVQ_RESID16=0); on = 1 (the
+ * default): the fp16 stream where the rule above allows it.  KVQ_RESID16=0 forces fp32 whatever the plan says. */
+int kvq_swin3d_plan_set_resid16(KvqSwinPlan* plan, int on);
+
 /* F.interpolate(mode="trilinear", align_corners=False) on a channels-last fp32 volume, written into channels
  * [c_off, c_off + C) of a channels-last destination with c_total channels (the torch.cat of multi=True,
  * swin_backbone.py:1070-1075).  src (B, D, H, W, C) -> dst (B, Do, Ho, Wo, c_total). */

@@ -177,6 +177,8 @@ SYMBOLS = {
     "kvq_swin3d_forward_stages": (i32, [p_void, p_void, p_void, i32, i32, p_void, p_void, p_void, sz, p_void]),
     "kvq_swin3d_set_taps": (i32, [p_void, C.POINTER(p_void)]),
     "kvq_swin3d_tap_dims": (i32, [p_void, i32, C.POINTER(i32 * 4)]),
+    "kvq_swin3d_set_range_flags": (i32, [p_void, p_void]),
+    "kvq_swin3d_plan_set_resid16": (i32, [p_void, i32]),
     "kvq_resize_trilinear_cl": (i32, [p_void, i32, i32, i32, i32, i32, p_void, i32, i32, i32, i32, i32, p_void]),
     "kvq_swin3d_forward": (i32, [p_void, C.POINTER(KvqSwinWeights), p_void, p_void, p_void, sz, p_void]),
     "kvq_swin3d_forward_fragments": (i32, [p_void, C.POINTER(KvqSwinWeights), C.POINTER(KvqFragmentSource), p_void, p_void, sz,

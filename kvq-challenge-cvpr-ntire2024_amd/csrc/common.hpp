@@ -115,6 +115,34 @@ struct Fp16 {
   }
 };
 
+// ---- range detector of the fp16 residual stream (kvq_swin3d_set_range_flags).  With MODE.FP16_OVFL a value past +-65504 is stored
+// as +-65504, so a stored half h is out of range when (h & 0x7fff) >= 0x7bff (a saturated value, +-inf and NaN alike).  A writer folds
+// every stored pair into a packed u16 magnitude max in one register (v_and_b32 + v_pk_max_u16 per pair: no compare per element) and
+// tests it once per wave after its stores; only a wave that saw such a value touches memory — one lane ORs the stage bit into the
+// caller's word with a vector global atomic.  word == NULL (every exported per-kernel entry): no detection, a uniform branch.
+struct RangeFlag {
+  uint32_t* word;
+  uint32_t bit;
+};
+typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
+// m: the running max (0 or a previous range_fold result — never a raw stored pair: only h2 is masked, and a raw half with its sign
+// bit set would win the u16 max and hide the magnitudes behind it); h2: the next stored pair
+__device__ __forceinline__ uint32_t range_fold(uint32_t m, uint32_t h2) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, m), __builtin_bit_cast(u16x2, h2 & 0x7fff7fffu)));
+}
+// every lane of the wave that is still running calls this (converged control flow)
+__device__ __forceinline__ void range_flush(uint32_t m, uint32_t* word, uint32_t bit) {
+  const uint32_t mx = (m & 0xffffu) > (m >> 16) ? (m & 0xffffu) : (m >> 16);
+  const unsigned long long hit = __ballot(mx >= 0x7bffu);
+  if (hit && __lane_id() == (unsigned)__builtin_ctzll(hit)) __hip_atomic_fetch_or(word, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The launches that write the fp16 stream, with the detector (plan.hip).  The exported kvq_patch_embed / kvq_patch_merge / kvq_gemm_bf16
+// (and kvq_block_tail, tail.hpp) are these with {NULL, 0}: the public argument structs stay as they are.
+int patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStream_t st);
+int patch_merge_launch(const KvqPatchMergeArgs* a, RangeFlag range, hipStream_t st);
+int gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t st);
+
 // exact GELU (erf), as nn.GELU() default (swin_backbone.py:72, head.py:56)
 __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

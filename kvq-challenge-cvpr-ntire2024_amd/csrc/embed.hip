@@ -37,6 +37,7 @@ struct EmbedParams {
   int has_ln;                // patch_embed.norm present
   float* out;                // [B*L0][E] fp32
   int out16;                 // round 6: the residual stream leaves as fp16 rows of 2 E bytes (same pointer)
+  RangeFlag range;           // out16: range detector of the stream rows written (common.hpp), word NULL = off
   const float* nn_w;         // first block's norm1 (EMIT)
   const float* nn_b;
   const int32_t* next_dst;   // token -> window row
@@ -207,6 +208,7 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
     rstd = rsqrtf(sq / (float)E + p.eps);
     asm volatile("" : "+v"(mean));     // opaque: no CSE of (acc - mean) between the variance and the normalise pass
   };
+  uint32_t rmax = 0;                   // out16: range detector, packed magnitude max of the stored halves
   if (p.has_ln) {
     float mean, rstd;
     stats(mean, rstd);
@@ -247,9 +249,11 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
 #pragma unroll
     for (int i = 0; i < CM; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<u32x2*>(o + 32 * i + 8 * q) =
-            (u32x2){Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
+      for (int q = 0; q < 4; ++q) {
+        const u32x2 v = {Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
+        *reinterpret_cast<u32x2*>(o + 32 * i + 8 * q) = v;
+        rmax = range_fold(range_fold(rmax, v[0]), v[1]);
+      }
   } else if (live) {
     float* o = p.out + (size_t)rc * E + 4 * h;
 #pragma unroll
@@ -259,6 +263,7 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
         *reinterpret_cast<f32x4*>(o + 32 * i + 8 * q) =
             (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
   }
+  if (p.out16 && p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   if (EMIT) {
     float mean, rstd;
     stats(mean, rstd);
@@ -345,6 +350,10 @@ extern "C" int kvq_patch_embed_fragments_supported(const KvqFragmentSource* f, i
 }
 
 extern "C" int kvq_patch_embed(const KvqPatchEmbedArgs* a, void* stream) {
+  return kvq::patch_embed_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream);
+}
+
+int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStream_t st) {
   using namespace kvq;
   KVQ_REQUIRE(a && (a->x || a->frag) && a->pack && a->out, KVQ_ERR_NULL, "kvq_patch_embed: NULL pointer");
   KVQ_REQUIRE(!(a->x && a->frag), KVQ_ERR_UNSUPPORTED, "kvq_patch_embed: both a clip and a fragment source");
@@ -374,7 +383,7 @@ extern "C" int kvq_patch_embed(const KvqPatchEmbedArgs* a, void* stream) {
   p.D0 = a->T / a->pd; p.H0 = a->H / 4; p.W0 = a->W / 4;
   p.pack = (const unsigned char*)a->pack; p.has_ln = a->has_norm; p.out = a->out; p.out16 = a->out_f16; p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b;
   p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln; p.next_rows = a->next_rows; p.eps = a->eps;
-  hipStream_t st = (hipStream_t)stream;
+  if (a->out_f16) p.range = range;
   if (a->embed_dim == 96)
     return a->dtype == KVQ_DT_FP16 ? launch_embed<Fp16, 3, 6>(p, st) : launch_embed<Bf16, 3, 6>(p, st);
   return a->dtype == KVQ_DT_FP16 ? launch_embed<Fp16, 4, 6>(p, st) : launch_embed<Bf16, 4, 6>(p, st);

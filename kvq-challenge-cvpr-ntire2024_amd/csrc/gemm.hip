@@ -289,6 +289,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 #pragma unroll
   for (int i = 0; i < MI; ++i)
     ep.tile(p, m0 + wm * 32 * MI + i * 32, ksl, [&](int j, int r) { return acc[i][j][r]; });
+  ep.finish(p);
   if (tr) {
     p.trace[blockIdx.x * 8 + 3] = __builtin_readcyclecounter();
     unsigned xcc;
@@ -560,6 +561,10 @@ extern "C" size_t kvq_gemm_splitk_bytes(int M, int N, int K) {
 }
 
 extern "C" int kvq_gemm_bf16(const KvqGemmArgs* a, void* stream) {
+  return kvq::gemm_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream);
+}
+
+int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream) {
   using namespace kvq;
   KVQ_REQUIRE(a && a->A && a->W, KVQ_ERR_NULL, "kvq_gemm_bf16: NULL A/W");
   KVQ_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->N % 8 == 0 && a->K % 32 == 0, KVQ_ERR_SHAPE,
@@ -573,6 +578,9 @@ extern "C" int kvq_gemm_bf16(const KvqGemmArgs* a, void* stream) {
   KVQ_REQUIRE(!p.sk_ws || ((size_t)p.sk_ws & 15) == 0, KVQ_ERR_SHAPE, "kvq_gemm_bf16: splitk_ws must be 16-byte aligned");
   p.ldc = a->ldc; p.col_off = a->col_off;
   p.a_gather = a->a_gather; p.a_rows = a->a_rows; p.a_phys_rows = a->a_phys_rows;
+  KVQ_REQUIRE(!range.word || (a->epilogue == KVQ_EPI_BIAS_BF16 && a->dtype == KVQ_DT_FP16 && !a->splitk_ws), KVQ_ERR_UNSUPPORTED,
+              "kvq_gemm_bf16: the range detector needs the fp16 bias epilogue without split-K");
+  p.range = range;
   KVQ_REQUIRE(!a->a_gather || (a->a_rows > 0 && a->a_phys_rows >= a->a_rows && a->M % a->a_rows == 0 && !a->splitk_ws), KVQ_ERR_SHAPE,
               "kvq_gemm_bf16: a_gather needs M = n_batch * a_rows, a_phys_rows >= a_rows, no split-K");
   KVQ_REQUIRE(a->ldc != 0 || a->col_off == 0, KVQ_ERR_SHAPE, "kvq_gemm_bf16: col_off = %d without ldc (the epilogue would write outside the row)",

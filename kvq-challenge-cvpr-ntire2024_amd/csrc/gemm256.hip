@@ -52,6 +52,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmParams p) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
       ep.tile(p, m0 + wr * 128 + i * 64 + mi * 32, ksl, [&](int j, int r) { return acc[i][mi][j][r]; });
+  ep.finish(p);
 }
 
 template <typename E, int EPI>

@@ -36,6 +36,8 @@ struct GemmParams {
   size_t sk_bytes;
   const int32_t* a_gather;     // plain GEMM: row m reads A row (m / a_rows) * a_phys_rows + a_gather[m % a_rows]
   int a_rows, a_phys_rows;
+  RangeFlag range;             // fp16 KVQ_EPI_BIAS_BF16 writing the residual stream (an un-fused merge's reduction): the range detector
+                               // of common.hpp over the stored halves; word NULL = off (the split-K reduction does not take it)
 };
 
 // ---- epilogue.  C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
@@ -52,6 +54,7 @@ struct GemmEpilogue {
   static constexpr int CPRW = SW / CW;                           // lane chunks per slab row
   static constexpr int ROWS_PER_IT = 64 / CPRW;
   static constexpr int SLAB_FLOATS = 32 * SW;                    // per wave
+  static constexpr bool RANGE = EPI == KVQ_EPI_BIAS_BF16 && __is_same(E, Fp16);   // instantiations that can write an fp16 stream
 
   float* slab;
   int col_in, row_hi, ch, rsub, n;
@@ -59,6 +62,7 @@ struct GemmEpilogue {
   float bias[CW];
   int which, head, e0;
   float scale;
+  uint32_t rmax;                                                 // RANGE: packed magnitude max of the stored halves
 
   // n_wave0: first output column of this wave's 32*NI-wide strip
   __device__ __forceinline__ void init(const GemmParams& p, float* slab_of_wave, int n_wave0, int lane) {
@@ -78,6 +82,7 @@ struct GemmEpilogue {
       }
     }
     which = 0; head = 0; e0 = 0; scale = 1.f;
+    rmax = 0;
     if (EPI == KVQ_EPI_QKV_BF16 && col_live) {                   // a 32-column tile = one head of q|k|v
       const int C = p.N / 3;
       which = n / C;
@@ -156,6 +161,7 @@ struct GemmEpilogue {
         const u32x4 o = {E::pack2(v[0], v[1]), E::pack2(v[2], v[3]), E::pack2(v[4 % CW], v[5 % CW]),
                          E::pack2(v[6 % CW], v[7 % CW])};
         *reinterpret_cast<u32x4*>(dst) = o;
+        if (RANGE) rmax = range_fold(range_fold(range_fold(range_fold(rmax, o[0]), o[1]), o[2]), o[3]);   // in sequence: see range_fold
       } else if (EPI == KVQ_EPI_RESID_F32) {
         long orow = m;
         if (p.scatter_map) {
@@ -174,6 +180,11 @@ struct GemmEpilogue {
       }
     }
     __builtin_amdgcn_wave_barrier();
+  }
+
+  // after the last tile, every lane of the wave
+  __device__ __forceinline__ void finish(const GemmParams& p) {
+    if (RANGE && p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   }
 };
 

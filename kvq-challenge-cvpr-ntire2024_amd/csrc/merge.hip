@@ -26,6 +26,7 @@ struct MergeParams {
   const unsigned char* pack;
   float* out;                // [B*Ln][2C]
   int x16, out16;            // round 6: x / out are fp16 residual streams (rows of 2 C / 4 C bytes behind the same pointers)
+  RangeFlag range;           // out16: range detector of the stream rows written (common.hpp), word NULL = off
   const float* nn_w;         // next block's norm1 (EMIT)
   const float* nn_b;
   const int32_t* next_dst;   // merged token -> window row
@@ -219,16 +220,21 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
   float t1 = 0.f;
   {
     float* o = p.out + (size_t)rc * N + 4 * h;
+    uint32_t rmax = 0;                 // out16: range detector, packed magnitude max of the stored halves
 #pragma unroll
     for (int i = 0; i < CM; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const f32x4 v = outv(i, q);
-        if (live && p.out16) *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(p.out) + (size_t)rc * N + 4 * h + 32 * i + 8 * q) = (u32x2){Fp16::pack2(v[0], v[1]), Fp16::pack2(v[2], v[3])};
-        else if (live) *reinterpret_cast<f32x4*>(o + 32 * i + 8 * q) = v;
+        if (live && p.out16) {
+          const u32x2 hv = {Fp16::pack2(v[0], v[1]), Fp16::pack2(v[2], v[3])};
+          *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(p.out) + (size_t)rc * N + 4 * h + 32 * i + 8 * q) = hv;
+          rmax = range_fold(range_fold(rmax, hv[0]), hv[1]);
+        } else if (live) *reinterpret_cast<f32x4*>(o + 32 * i + 8 * q) = v;
         if (EMIT) t1 += (v[0] + v[1]) + (v[2] + v[3]);
         if (q == 3) __builtin_amdgcn_sched_barrier(0);
       }
+    if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   }
   if (EMIT) {
     // LayerNorm over the 2C channels of the merged token: in-lane sums + one exchange with lane ^ 32 (two-pass, as ln.hip)
@@ -340,6 +346,10 @@ extern "C" int kvq_patch_merge_pack(const float* red_w, const float* norm_w, con
 }
 
 extern "C" int kvq_patch_merge(const KvqPatchMergeArgs* a, void* stream) {
+  return kvq::patch_merge_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream);
+}
+
+int kvq::patch_merge_launch(const KvqPatchMergeArgs* a, RangeFlag range, hipStream_t stream) {
   using namespace kvq;
   KVQ_REQUIRE(a && a->x && a->merge_map && a->pack && a->out, KVQ_ERR_NULL, "kvq_patch_merge: NULL pointer");
   KVQ_REQUIRE(kvq_patch_merge_supported(a->C), KVQ_ERR_UNSUPPORTED, "kvq_patch_merge: C=%d is not a fused width", a->C);
@@ -352,5 +362,6 @@ extern "C" int kvq_patch_merge(const KvqPatchMergeArgs* a, void* stream) {
   p.x = a->x; p.map = a->merge_map; p.B = a->B; p.L = a->L; p.Ln = a->Ln; p.pack = (const unsigned char*)a->pack; p.out = a->out; p.x16 = a->x_f16; p.out16 = a->out_f16;
   p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b; p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln; p.next_rows = a->next_rows;
   p.eps = a->eps;
-  return a->dtype == KVQ_DT_FP16 ? launch_merge_c<Fp16>(a->C, p, (hipStream_t)stream) : launch_merge_c<Bf16>(a->C, p, (hipStream_t)stream);
+  if (a->out_f16) p.range = range;
+  return a->dtype == KVQ_DT_FP16 ? launch_merge_c<Fp16>(a->C, p, stream) : launch_merge_c<Bf16>(a->C, p, stream);
 }

@@ -75,6 +75,8 @@ struct KvqSwinPlan {
   unsigned char* run_ws;         // workspace of the forward in progress (for the GEMM helper)
   int table_len, center;
   std::vector<float*> taps;      // feats[i] destinations (kvq_swin3d_set_taps), empty = none
+  uint32_t* range_word;          // kvq_swin3d_set_range_flags: bit i = stage i's fp16 stream held a value past +-65504; NULL = none
+  bool resid16;                  // kvq_swin3d_plan_set_resid16: false = fp32 stream rows in every stage
   // profiling
   bool profile;
   std::vector<kvq::ProfEvent> events;
@@ -240,6 +242,7 @@ extern "C" int kvq_swin3d_plan_create(const KvqSwinCfg* cfg, int B, int T, int H
   KvqSwinPlan* pl = new KvqSwinPlan();
   pl->cfg = *cfg; pl->B = B; pl->T = T; pl->H = H; pl->W = W; pl->dtype = dtype;
   pl->profile = false; pl->ev_used = 0;
+  pl->range_word = nullptr; pl->resid16 = true;
   pl->D0 = ceil_div(T, cfg->patch[0]); pl->H0 = ceil_div(H, cfg->patch[1]); pl->W0 = ceil_div(W, cfg->patch[2]);
   pl->K0 = cfg->in_chans * cfg->patch[0] * cfg->patch[1] * cfg->patch[2];
   const int Wd = cfg->window[0], Wh = cfg->window[1], Ww = cfg->window[2];
@@ -395,7 +398,7 @@ struct Bracket {
 
 static int gemm(KvqSwinPlan* pl, hipStream_t st, int kind, const uint16_t* A, const uint16_t* Wt, const float* bias,
                 int M, int N, int K, int epi, uint16_t* obf, float* of32, int nH = 0, float qs = 1.f,
-                const int32_t* map = nullptr, int map_rows = 0, int out_rows = 0) {
+                const int32_t* map = nullptr, int map_rows = 0, int out_rows = 0, RangeFlag range = RangeFlag{nullptr, 0}) {
   KvqGemmArgs a{};
   a.A = A; a.W = Wt; a.bias = bias; a.M = M; a.N = N; a.K = K; a.epilogue = epi; a.out_bf16 = obf; a.out_f32 = of32;
   a.num_heads = nH; a.q_scale = qs; a.scatter_map = map; a.map_rows = map_rows; a.out_rows = out_rows;
@@ -407,7 +410,7 @@ static int gemm(KvqSwinPlan* pl, hipStream_t st, int kind, const uint16_t* A, co
   const double out_b = (epi == KVQ_EPI_RESID_F32) ? 8.0 : (epi == KVQ_EPI_STORE_F32 ? 4.0 : 2.0);
   Bracket br(pl, st, kind, (gemm8p_wanted(M, N, K) ? 4464 : gemm_variant(M, N, K)) * 10 + epi, 2.0 * M * N * K,
              2.0 * ((double)M * K + (double)N * K) + out_b * M * N);
-  return kvq_gemm_bf16(&a, st);
+  return gemm_launch(&a, range, st);
 }
 
 static int ln(KvqSwinPlan* pl, hipStream_t st, const float* x, const int32_t* map, int nparts, int rows_in,
@@ -435,6 +438,19 @@ extern "C" int kvq_swin3d_set_taps(KvqSwinPlan* pl, float* const* taps) {
   KVQ_REQUIRE(pl, KVQ_ERR_NULL, "kvq_swin3d_set_taps: NULL plan");
   pl->taps.clear();
   if (taps) pl->taps.assign(taps, taps + pl->cfg.num_stages + 1);
+  return KVQ_OK;
+}
+
+extern "C" int kvq_swin3d_set_range_flags(KvqSwinPlan* pl, uint32_t* dev_word) {
+  KVQ_REQUIRE(pl, KVQ_ERR_NULL, "kvq_swin3d_set_range_flags: NULL plan");
+  KVQ_REQUIRE(((size_t)dev_word & 3) == 0, KVQ_ERR_SHAPE, "kvq_swin3d_set_range_flags: the word must be 4-byte aligned");
+  pl->range_word = dev_word;
+  return KVQ_OK;
+}
+
+extern "C" int kvq_swin3d_plan_set_resid16(KvqSwinPlan* pl, int on) {
+  KVQ_REQUIRE(pl, KVQ_ERR_NULL, "kvq_swin3d_plan_set_resid16: NULL plan");
+  pl->resid16 = on != 0;
   return KVQ_OK;
 }
 
@@ -489,8 +505,11 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
   // Consumers that take an fp16 stream: the fused tails of every width (padded partitions too), the fused merge, every LayerNorm launch
   // (a first block's norm1, the gather-LayerNorm of an un-fused merge);
   // the last stage keeps fp32 (its stream comes out of a GEMM epilogue and feeds the final LayerNorm and the fp32 feature output).
-  // KVQ_RESID16=0: fp32 everywhere (rounds 1-5).
-  static const bool resid16_on = !(getenv("KVQ_RESID16") && atoi(getenv("KVQ_RESID16")) == 0);
+  // KVQ_RESID16=0: fp32 everywhere (rounds 1-5); so does a plan with kvq_swin3d_plan_set_resid16(plan, 0).
+  static const bool resid16_env = !(getenv("KVQ_RESID16") && atoi(getenv("KVQ_RESID16")) == 0);
+  const bool resid16_on = resid16_env && pl->resid16;
+  // the range detector of the launches that write an fp16 stream: stage i's writers OR bit i into the caller's word
+  auto range_of = [&](int stage) -> RangeFlag { return RangeFlag{pl->range_word, 1u << stage}; };
   bool any_tap = false;
   for (float* t : pl->taps) any_tap = any_tap || t != nullptr;
   // Which launches the forward takes, each decided in ONE place: the fp16-stream rule below and the launch sites ask the same predicates.
@@ -557,7 +576,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
     const double px = (double)B * L0 * pl->K0;
     Bracket br(pl, st, KVQ_K_EMBED, (first_ln1_ready ? 1 : 0) + (frag ? 2 : 0), 2.0 * B * L0 * (double)E * pl->K0,
                px * (frag ? 1.0 : 4.0) + (double)B * L0 * E * ((x16[0] ? 2.0 : 4.0) + (first_ln1_ready ? 2.0 : 0.0)));
-    KVQ_TRY_UNLESS(64, kvq_patch_embed(&ea, st));
+    KVQ_TRY_UNLESS(64, patch_embed_launch(&ea, range_of(0), st));
   } else {
     KVQ_REQUIRE(!frag, KVQ_ERR_UNSUPPORTED, "kvq_swin3d_forward_fragments: this plan does not take the fused patch-embedding launch");
     {
@@ -688,7 +707,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
         }
         Bracket br(pl, st, KVQ_K_TAIL, kvq::tailmm_geometry_code(C, hidden) * 1000 + (C / 32) * 10 + (ln1_ready ? 1 : 0) + (qkv_ready ? 2 : 0), 2.0 * M * C * C + 4.0 * (double)ML * C * hidden + (qkv_ready ? 6.0 * M * C * C : 0.0),
                    (double)M * C * 2.0 + (double)ML * C * ((x16_cur ? 4.0 : 8.0) + (ln1_ready ? 2.0 : 0.0) + (qkv_ready ? 6.0 : 0.0)));
-        KVQ_TRY_UNLESS(C <= 192 ? 2 : 4, kvq_block_tail(&ta, st));
+        KVQ_TRY_UNLESS(C <= 192 ? 2 : 4, block_tail_launch(&ta, range_of(i), st));
         continue;
       }
       KVQ_TRY(f32_only("the proj / MLP GEMM chain"));
@@ -734,12 +753,13 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
         }
         Bracket br(pl, st, KVQ_K_MERGE, merged_ln1_ready ? 1 : 0, 2.0 * B * Ln * (double)(2 * C) * (4 * C),
                    (double)B * Ln * 4 * C * (x16_cur ? 2.0 : 4.0) + (double)B * Ln * 2 * C * ((x16[i + 1] ? 2.0 : 4.0) + (merged_ln1_ready ? 2.0 : 0.0)));
-        KVQ_TRY_UNLESS(128, kvq_patch_merge(&ma, st));
+        KVQ_TRY_UNLESS(128, patch_merge_launch(&ma, range_of(i + 1), st));
         x16_cur = x16[i + 1];
       } else {
         KVQ_TRY(ln(pl, st, cur, g.d_merge, 4, g.L, Ln, C, mw.norm_w, mw.norm_b, bln, nullptr, x16_cur));
         x16_cur = x16[i + 1];                                  // the reduction GEMM writes the next stage's stream: fp32, or fp16 rows (fp16 operands)
-        if (x16_cur) KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, KVQ_EPI_BIAS_BF16, reinterpret_cast<uint16_t*>(oth), nullptr));
+        if (x16_cur) KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, KVQ_EPI_BIAS_BF16, reinterpret_cast<uint16_t*>(oth), nullptr,
+                                               0, 1.f, nullptr, 0, 0, range_of(i + 1)));
         else KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, KVQ_EPI_STORE_F32, nullptr,
                      oth));
       }

@@ -398,14 +398,20 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
       for (int e = 0; e < 4; ++e) acc[i][4 * q + e] += fb[e];
       if (q & 1) __builtin_amdgcn_sched_barrier(0);
     }
-  if (live && p.x16) {
+  if (p.x16) {
     uint16_t* xr = reinterpret_cast<uint16_t*>(p.x) + (size_t)orig * C + 4 * h;
+    uint32_t rmax = 0;                 // range detector: packed magnitude max of the stored halves
 #pragma unroll
     for (int i = 0; i < CM; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<u32x2*>(xr + 32 * i + 8 * q) =
-            (u32x2){Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
+      for (int q = 0; q < 4; ++q) {
+        const u32x2 v = {Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
+        if (live) {
+          *reinterpret_cast<u32x2*>(xr + 32 * i + 8 * q) = v;
+          rmax = range_fold(range_fold(rmax, v[0]), v[1]);
+        }
+      }
+    if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   } else if (live) {
     float* xr = p.x + (size_t)orig * C + 4 * h;
 #pragma unroll
@@ -638,6 +644,10 @@ extern "C" int kvq_block_tail_qkv_pack(const void* qkv_w, int C, int hidden, voi
 }
 
 extern "C" int kvq_block_tail(const KvqBlockTailArgs* a, void* stream) {
+  return kvq::block_tail_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream);
+}
+
+int kvq::block_tail_launch(const KvqBlockTailArgs* a, RangeFlag range, hipStream_t stream) {
   using namespace kvq;
   KVQ_REQUIRE(a && a->attn && a->x && a->pack, KVQ_ERR_NULL, "kvq_block_tail: NULL pointer");
   KVQ_REQUIRE(kvq_block_tail_supported(a->C, a->hidden), KVQ_ERR_UNSUPPORTED, "kvq_block_tail: C=%d hidden=%d", a->C,
@@ -651,6 +661,7 @@ extern "C" int kvq_block_tail(const KvqBlockTailArgs* a, void* stream) {
   p.M = a->M; p.hidden = a->hidden; p.pack = (const unsigned char*)a->pack;
   p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b; p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln;
   p.next_rows = a->next_rows; p.eps = a->eps; p.trace = g_trace; p.trace_blocks = g_trace_blocks;
+  if (a->x_f16) p.range = range;
   if (a->qkv_out) {
     KVQ_REQUIRE(kvq_block_tail_qkv_pack_bytes(a->C, a->hidden) > 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: C=%d cannot emit q | k | v", a->C);
     KVQ_REQUIRE(!a->next_ln && a->next_qkv_pack && a->next_qkv_b && a->next_norm_w && a->next_norm_b && a->next_dst && a->next_rows > 0 &&
@@ -663,7 +674,6 @@ extern "C" int kvq_block_tail(const KvqBlockTailArgs* a, void* stream) {
     KVQ_REQUIRE(a->map_rows > 0 && a->M % a->map_rows == 0, KVQ_ERR_SHAPE, "kvq_block_tail: attn_gather needs M = n_batch * map_rows");
     p.gather = a->attn_gather; p.n_tok = a->M / a->map_rows * a->out_rows; p.map = nullptr;
   }
-  if (use_tailmm(a->C, a->hidden)) return tailmm_launch(p, a->C, a->dtype, (hipStream_t)stream);
-  return a->dtype == KVQ_DT_FP16 ? launch_tail_e<Fp16>(p, a->C, (hipStream_t)stream)
-                                 : launch_tail_e<Bf16>(p, a->C, (hipStream_t)stream);
+  if (use_tailmm(a->C, a->hidden)) return tailmm_launch(p, a->C, a->dtype, stream);
+  return a->dtype == KVQ_DT_FP16 ? launch_tail_e<Fp16>(p, a->C, stream) : launch_tail_e<Bf16>(p, a->C, stream);
 }

@@ -584,6 +584,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
   MM_STAMP(3);
   // ---- write the residual stream back; optionally the next block's norm1 rows in ITS window order ----------------------
   if (p.x16) {
+    uint32_t rmax = 0;                 // range detector: packed magnitude max of the stored halves
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
       if (live[tt]) {
@@ -591,9 +592,13 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
 #pragma unroll
         for (int ft = 0; ft < CF; ++ft)
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<u32x2*>(xr + 32 * ft + 8 * q) = (u32x2){Fp16::pack2(acc[ft][tt][4 * q], acc[ft][tt][4 * q + 1]), Fp16::pack2(acc[ft][tt][4 * q + 2], acc[ft][tt][4 * q + 3])};
+          for (int q = 0; q < 4; ++q) {
+            const u32x2 v = {Fp16::pack2(acc[ft][tt][4 * q], acc[ft][tt][4 * q + 1]), Fp16::pack2(acc[ft][tt][4 * q + 2], acc[ft][tt][4 * q + 3])};
+            *reinterpret_cast<u32x2*>(xr + 32 * ft + 8 * q) = v;
+            rmax = range_fold(range_fold(rmax, v[0]), v[1]);
+          }
       }
+    if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   } else
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt)

@@ -129,6 +129,10 @@ class SwinTransformer3D(nn.Module):
         self.dense_bias_max_abs = 16.0
         self.dense_bias_bytes_per_clip = 2 * 2 ** 30
         self._dense = {}
+        # residual stream x in fp16 where every producer and consumer of a stage takes fp16 rows; False: fp32 rows in
+        # every stage — the exact re-score of an input whose fp16 stream left the +-65504 range (range_flags below)
+        self.residual16 = True
+        self._range_words: Dict[Tuple, torch.Tensor] = {}
         if isinstance(window_size, list) and window_size and isinstance(window_size[0], (list, tuple)):
             raise NotImplementedError("per-stage window sizes are not used by any reference config")
         if qk_scale is not None or any(jump_attention) or not qkv_bias:
@@ -378,7 +382,7 @@ class SwinTransformer3D(nn.Module):
 
     def _plan(self, B, T, H, W, device, aw=None):
         # one plan + workspace per (shape, stream): forwards issued on different streams may overlap
-        key = (B, T, H, W, str(device), self.operand_dtype, current_stream(), aw)
+        key = (B, T, H, W, str(device), self.operand_dtype, current_stream(), aw, bool(self.residual16))
         hit = self._plans.get(key)
         if hit is not None:
             return hit
@@ -386,6 +390,10 @@ class SwinTransformer3D(nn.Module):
         cfg = self.cfg_struct(aw)
         check(lib().kvq_swin3d_plan_create(C.byref(cfg), B, T, H, W, self.operand_dtype, C.byref(handle)),
               "kvq_swin3d_plan_create")
+        if not self.residual16:
+            check(lib().kvq_swin3d_plan_set_resid16(handle, 0), "kvq_swin3d_plan_set_resid16")
+        check(lib().kvq_swin3d_set_range_flags(handle, ptr(self._range_word(torch.cuda.current_stream(torch.device(device))))),
+              "kvq_swin3d_set_range_flags")
         dims = (C.c_int32 * 4)()
         check(lib().kvq_swin3d_out_dims(handle, C.byref(dims)), "kvq_swin3d_out_dims")
         nbytes = lib().kvq_swin3d_workspace_bytes(handle)
@@ -393,6 +401,30 @@ class SwinTransformer3D(nn.Module):
         entry = (handle, tuple(dims), ws)
         self._plans[key] = entry
         return entry
+
+    # ------------------------------------------------------------------ range of the fp16 residual stream
+    def _range_word(self, stream) -> torch.Tensor:
+        """The int32 device word of ``stream`` that every plan of this module ORs its stage bits into (created zeroed on first use,
+        before any forward of that stream is captured into a graph)."""
+        key = (str(stream.device), stream.cuda_stream)
+        word = self._range_words.get(key)
+        if word is None:
+            word = torch.zeros(1, dtype=torch.int32, device=stream.device)
+            self._range_words[key] = word
+        return word
+
+    def range_flags(self, stream=None) -> torch.Tensor:
+        """The range word of ``stream`` (default: the current stream) as a 1-element int32 device tensor, without synchronising.
+        Bit i set: stage i's fp16 residual stream held a value that reached +-65504 (clamped there, or inf / NaN) in a forward on
+        that stream since the last ``clear_range_flags``, so that forward's output is not exact; re-run it with
+        ``residual16 = False``.  Sticky: only ``clear_range_flags`` zeroes it."""
+        return self._range_word(stream if stream is not None else torch.cuda.current_stream())
+
+    def clear_range_flags(self, stream=None) -> None:
+        """Zero the range word of ``stream`` (default: the current stream), enqueued on that stream."""
+        stream = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(stream):
+            self._range_word(stream).zero_()
 
     def __del__(self):
         try:

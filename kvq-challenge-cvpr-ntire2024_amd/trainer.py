@@ -12,6 +12,7 @@ Training (optimizer, losses, EMA, checkpoints) is out of scope: this is an infer
 from __future__ import annotations
 
 import os
+import sys
 
 import numpy as np
 import torch
@@ -144,12 +145,23 @@ class Trainer:
         if use_graph:
             from .graph import LaneGraphs
             cached = getattr(self, "_lane_graphs", None)           # recordings outlive one call (inferece_test + inferece_val)
-            if cached is None or len(cached.lanes) != nstream:
+            # ... but not a change of a Swin trunk's residual16: a recording replays the plans (fp16 or fp32 stream) it was made with
+            r16 = tuple(bool(m.residual16) for m in self._swin_trunks())
+            if cached is None or len(cached.lanes) != nstream or getattr(self, "_lane_graphs_r16", r16) != r16:
                 cached = self._lane_graphs = LaneGraphs(self._run_model, [torch.cuda.Stream(device=self.device) for _ in range(nstream)])
+            self._lane_graphs_r16 = r16
             graphs, lanes = cached, cached.lanes
         else:
             lanes = [main] + [torch.cuda.Stream(device=self.device) for _ in range(nstream - 1)]
             graphs = None
+        # range guard (yml `range_guard`, default on): every Swin trunk ORs a bit per stage into a word of the lane's stream when its fp16
+        # residual stream left the +-65504 range; after each video the lane moves the OR of its words into flags[j] and clears them, and
+        # the flagged videos are scored again below with fp32 streams
+        swins = self._swin_trunks() if self._range_guard() else []
+        flags = torch.zeros(len(mine), dtype=torch.int32, device=self.device) if swins else None
+        for st in lanes:
+            for m in swins:
+                m.clear_range_flags(st)
         for st in lanes:
             if st != main:
                 st.wait_stream(main)
@@ -171,6 +183,8 @@ class Trainer:
                     inputs = self._model_inputs(item)
                     pred = graphs.run(lane, inputs) if graphs is not None else self._run_model(inputs)
                     local[j] = pred.float().mean()                # pred.mean(0) over clips (trainer.py:282)
+                    if swins:
+                        self._take_range_flags(swins, lanes[lane], flags, j)
                 if j == 0 and graphs is None and nstream > 1:
                     # the first forward (re)builds the lazily cached weight images (16-bit copies, packed panels, folded
                     # BatchNorms, bias images) on ITS stream; the other lanes read them — they must be complete first
@@ -183,7 +197,57 @@ class Trainer:
                 main.wait_stream(st)
         if graphs is not None:
             self.graph_stats = (graphs.replays, graphs.eager_runs)
+        self.range_flags = None                 # this rank's per-video stage bits of the last call (None: range_guard off)
+        if swins:
+            self.range_flags = flags.cpu().numpy()
+            self._rescore_flagged(swins, self.range_flags, mine, local)
         return kd.gather_scores(local, n, self.rank, self.world).cpu().numpy()
+
+    # ---- range guard of the fp16 residual stream ----------------------------------------------------------------------------
+    def _range_guard(self) -> bool:
+        v = self.config.get("range_guard", True)
+        return v if isinstance(v, bool) else str(v).lower() not in ("0", "false", "off", "no")
+
+    def _swin_trunks(self):
+        from .models.backbones.swin_backbone import SwinTransformer3D
+        return [m for m in self.model.modules() if isinstance(m, SwinTransformer3D)]
+
+    @staticmethod
+    def _take_range_flags(swins, stream, flags, j):
+        """on `stream`, behind the video's forward (eager or a graph replay): flags[j] = OR of the trunks' words; the words are cleared"""
+        words = [m.range_flags(stream) for m in swins]
+        acc = words[0]
+        for w in words[1:]:
+            acc = acc | w
+        flags[j:j + 1].copy_(acc)
+        for m in swins:
+            m.clear_range_flags(stream)
+
+    @staticmethod
+    def rescore_indices(flags) -> list:
+        """positions j of the shard whose forward set any stage bit"""
+        return [j for j, f in enumerate(np.asarray(flags).reshape(-1).tolist()) if int(f) != 0]
+
+    def _rescore_flagged(self, swins, flags, mine, local):
+        """score the flagged videos of this shard again on the current stream, eagerly, with fp32 residual streams in every trunk"""
+        redo = self.rescore_indices(flags)
+        if not redo:
+            return
+        saved = [m.residual16 for m in swins]
+        try:
+            for m in swins:
+                m.residual16 = False
+            for j in redo:
+                local[j] = self._run_model(self._model_inputs(self.val_dataset[mine[j]])).float().mean()
+        finally:
+            for m, s in zip(swins, saved):
+                m.residual16 = s
+        bits = 0
+        for j in redo:
+            bits |= int(flags[j])
+        stages = ",".join(str(i) for i in range(4) if bits >> i & 1)
+        print(f"range guard: {len(redo)} video(s) re-scored with fp32 residual streams (fp16 stream out of range in stage(s) {stages})",
+              file=sys.stderr)
 
     def inferece_test(self):
         scores = self._score_all()
