@@ -7,7 +7,8 @@
 Headline leg = C2 (BASELINE.json configs[1]): a "step" = one pass of the hot path over one batch of ``--batch`` clips per
 GPU (default 4): K1 (``kvq_fragment_gather``: 7x7 grid of 32x32 mini-patches + normalisation) out of a
 uint8 frame stack resident in HBM -> Swin3D-T(GRPB) trunk -> VQAHead.  Every step reads DIFFERENT source clips.
-One JSON line on rank 0 with the contract's keys plus
+A plain run sets up, warms up, times the steps, writes ``--dump-outputs`` and prints one JSON line on rank 0: the contract's keys, the
+run's configuration and timing statistics; ``roofline``, ``cpu_baseline`` and ``config.parity`` are null.  ``--full`` adds
   roofline      dominant kernel of the C2 step: algorithmic flops / hipEvent-measured launch time vs the dense MFMA peak
   cpu_baseline  the CPU oracle timed on this box's host cores (N = 1 only)
   no_sampler    the same steps on pre-sampled fp32 clips (K1 outside the timed region; the round-1 definition)
@@ -16,7 +17,7 @@ One JSON line on rank 0 with the contract's keys plus
                 type, which holds the 1e-3 gate on those weights too) — and bf16_stress (bf16 on them: does not)
   c3            BASELINE configs[2]: Swin3D-T + SlowFast-R50 on the same 8 clips (1 video per step)
   c5            BASELINE configs[4]: Swin-B on 64x256x256 clips, fp16 (video = 16 clips)
-(the extra legs run at N = 1; ``--legs c2`` skips them).
+(the extra legs run at N = 1; ``--full --legs c2`` skips them; ``--legs`` naming an extra leg without ``--full`` is refused).
 
 Timing: the K-step block (barrier + sync, K steps, sync + barrier, max over ranks) is timed once, so ``--steps`` is the number of timed
 steps and ``ms_per_step`` is the block's time over K.  ``--min-timed-s S`` REPEATS the block until about S seconds of steps have been
@@ -24,7 +25,7 @@ timed; ``ms_per_step`` / ``value`` are then the MEDIAN block, ``repeats`` / ``ms
 spread (a single 20-step block is 30 ms: box-to-box and clock noise are larger than most kernel changes).
 ``--dump-outputs DIR`` writes what the timed path returned in its last timed step (rank 0) as ``DIR/scores.npy`` (float32); the
 inputs (weights, frames, sampler draws) are seeded, so two builds run with the same arguments can be compared output for output.
-HBM traffic (``roofline.traffic``, ``whole_step_traffic``): measured in this run by two child passes per leg under
+HBM traffic (``roofline.traffic``, ``whole_step_traffic``; ``--full``): measured in the run by two child passes per leg under
 ``rocprofv3 --pmc FETCH_SIZE`` / ``--pmc WRITE_SIZE`` (``bench.py --probe LEG``: a few serial steps of the leg, nothing else), FETCH_SIZE
 doubled as the gfx950 guide prescribes; ``--no-pmc`` skips them (null).
 """
@@ -66,6 +67,9 @@ def parse():
     ap.add_argument("--two-launch-sampler", action="store_true",
                     help="K1 as its own launches (kvq_fragment_gather per clip -> the fp32 batch tensor -> forward) instead of the "
                          "default: the forward reads the patch-embedding operand through the sampler (kvq_swin3d_forward_fragments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline, HBM traffic, in-run parity, the extra legs, "
+                         "cpu_baseline (default: the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-clips", type=int, default=24, help="clips the CPU oracle is timed on (24 = 3 videos)")
     ap.add_argument("--streams", type=int, default=4,
@@ -955,6 +959,11 @@ def main():
         return run_probe(args)
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    legs = {"no_sampler", "two_launch", "fp16_stress", "bf16_stress", "batch8", "one_stream", "latency", "in_mix", "c3", "c5", "ksvqe"} if args.legs == "all" else {x for x in args.legs.split(",") if x and x != "c2"}
+    if not args.full:
+        if args.legs != "all" and legs:
+            sys.exit(f"bench.py: --legs {args.legs} needs --full")
+        legs = set()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_ranks(args)
     import torch
@@ -972,13 +981,12 @@ def main():
     weights_kind = args.weights or ("init" if args.dtype == "bf16" else "stress")
     net, cfg, wts, hw = build_net(args.dtype, device, weights_kind)
     bb = net.swin_tiny_grpb_backbone
-    headline_parity = golden_parity(net, weights_kind, device) if rank == 0 else None       # before anything is timed
+    headline_parity = golden_parity(net, weights_kind, device) if rank == 0 and args.full else None       # before anything is timed
     B = args.batch
     nstream = max(1, args.streams)
     lanes = [torch.cuda.current_stream()] + [torch.cuda.Stream(device=device) for _ in range(nstream - 1)]
     if args.cu_mask != "none":
         lanes = masked_lanes(nstream, args.cu_mask, device)
-    legs = {"no_sampler", "two_launch", "fp16_stress", "bf16_stress", "batch8", "one_stream", "latency", "in_mix", "c3", "c5", "ksvqe"} if args.legs == "all" else {x for x in args.legs.split(",") if x and x != "c2"}
     if world > 1:
         legs = set()
 
@@ -1079,8 +1087,8 @@ def main():
     out = None
     if rank == 0:
         roof = None
-        want_pmc = world == 1 and not args.no_pmc and args.profile_steps > 0
-        if args.profile_steps > 0:
+        want_pmc = args.full and world == 1 and not args.no_pmc and args.profile_steps > 0
+        if args.full and args.profile_steps > 0:
             src.sample_into(xs[0], 0)
             fused = sampler_on and not args.two_launch_sampler
             roof = c2_roofline(net, {"technical": src.fragments(0, B) if fused else xs[0]}, B, args.profile_steps)
@@ -1119,8 +1127,8 @@ def main():
             "score_checksum": float(allscores.double().sum().item()),
             "roofline": roof,
         }
-    # ---- extra legs (N = 1): the other definitions / configs, each timed the same way -----------------------------------
-    if rank == 0 and world == 1:
+    # ---- extra legs (N = 1, --full): the other definitions / configs, each timed the same way ---------------------------
+    if rank == 0 and world == 1 and args.full:
         with torch.no_grad():
             if "no_sampler" in legs and sampler_on:
                 dt2, _, _, st2 = timed(kd, device, steps_of(step_presampled), args.steps, min(args.warmup, 5), min_s=args.min_timed_s)

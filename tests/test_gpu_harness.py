@@ -187,6 +187,28 @@ def test_bench_times_steps_once_and_dumps_last_step(tmp_path):
     assert np.abs(ref.reshape(-1) - dumps[0].reshape(-1)).max() <= 1e-5
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain ``bench.py`` run measures the headline and nothing else: no roofline, in-run parity, extra legs or CPU baseline.
+    ``--full`` adds them, and the timed steps compute the same scores either way."""
+    import json
+    B, W, K = 2, 1, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(B)]
+    lines, dumps = [], []
+    for extra in ([], ["--full", "--legs", "c2", "--no-cpu-baseline", "--no-pmc", "--profile-steps", "1"]):
+        out = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(out)], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append(np.load(str(out / "scores.npy")))
+    plain, full = lines
+    for d in lines:
+        assert d["steps"] == K and d["warmup"] == W and d["unit"] == "videos/s" and d["higher_is_better"] is True and d["value"] > 0
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["config"]["parity"] is None
+    assert "legs" not in plain["config"] and "parity_pins" not in plain
+    assert full["roofline"]["kernel"] and full["config"]["parity"]["parity_ok"] and full["config"]["legs"] == {}
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def _fake_kvq_tree(tmp_path, n=2, T=96, H=120, W=160):
     g = np.random.Generator(np.random.PCG64(91))
     vids = []

@@ -215,3 +215,15 @@ def test_open_video_reader_order_and_cv2_fallback_padding(tmp_path, monkeypatch)
     monkeypatch.setitem(sys.modules, "decord", None)
     with pytest.raises(ImportError, match="decord or OpenCV"):
         FD.open_video(str(tmp_path / "short.mp4"))
+
+
+def test_bench_extra_legs_need_full():
+    """``bench.py`` without ``--full`` times the headline alone: a ``--legs`` list that names an extra leg is refused before anything
+    is set up."""
+    import os
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "1", "--warmup", "0", "--legs", "c2,c5"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "--legs c2,c5 needs --full" in r.stderr and not r.stdout.strip()

@@ -5,7 +5,7 @@ mkdir -p $(dirname $out)
 : > $out
 for i in $(seq 1 $n); do
   for v in "$A" "$B"; do
-    line=$(env $v python bench.py --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1)
+    line=$(env $v python bench.py --full --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1)
     python - "$v" "$line" >> $out <<'PY'
 import json, sys
 v, line = sys.argv[1], sys.argv[2]

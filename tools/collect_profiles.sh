@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiling evidence of a round, collected on the GPU box (through gpurun, from the repo root):  bash tools/collect_profiles.sh r04
 # Outputs under gpurun_out/<tag>/ (the summaries are then copied into profiles/ as <tag>_*):
-#   bench_line.json        the default bench line (sampler in the step, all legs, rocprofv3 --pmc traffic passes, CPU baseline)
+#   bench_line.json        the full bench line (--full: sampler in the step, all legs, rocprofv3 --pmc traffic passes, CPU baseline)
 #   bench_line_serial.json one stream
 #   step_launches.txt      every launch of one C2 step (hipEvent brackets): us, GFLOP, TF/s, MB, GB/s
 #   kernel_stats.txt       rocprofv3 --kernel-trace --stats of the serial C2 bench (the durations roofline.avg_launch_us must agree with)
@@ -12,9 +12,9 @@ tag=${1:-r06}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-C2="python bench.py --streams 1 --legs c2 --no-cpu-baseline --no-pmc"
+C2="python bench.py --full --streams 1 --legs c2 --no-cpu-baseline --no-pmc"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES"
-timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err
 timeout 300 $C2 --steps 20 --warmup 5 > $out/bench_line_serial.json 2>> $out/bench.err
 timeout 300 python tools/profile_step.py > $out/step_launches.txt 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o t -- $C2 --steps 20 --warmup 3 --min-timed-s 0 > $out/trace.log 2>&1
