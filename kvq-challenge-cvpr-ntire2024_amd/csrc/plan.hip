@@ -467,10 +467,126 @@ extern "C" int kvq_swin3d_tap_dims(const KvqSwinPlan* pl, int index, int32_t out
   return KVQ_OK;
 }
 
+namespace kvq {
+// ---- the schedule of one forward: every launch decided, and every requirement checked, before the first one is enqueued --------------
+// Built per call from the plan, the weights, the taps and the environment: by geometry and weights only, never by the batch.
+enum : uint8_t { kFromProducer, kLnTokens, kLnWindows };                  // BlockStep::ln1: who writes a block's norm1 rows
+enum : uint8_t { kQkvProducer, kQkvGemm, kQkvGemmPadded, kQkvInAttn };    // BlockStep::qkv: who writes its q | k | v
+enum : uint8_t { kEmitNone, kEmitLn1, kEmitQkv };   // what a fused producer writes for the next block (its profile record's variant bits)
+struct BlockStep {
+  int i, blk, par, npar, dsplit_from;   // stage, index into w->blocks, partition parity of this block and of the next one
+  uint8_t ln1, qkv, emit;               // emit: what the fused tail writes for the next block
+  // dense: attention on the bias image (pad_mask: it writes the padding rows' k | v), else the per-score gather; fill_pad: the padded
+  // GEMM's padding rows by kvq_qkv_fill_pad; fused_tail: proj + norm2 + MLP as one launch, else the proj / fc1 / fc2 GEMM chain
+  bool dense, pad_mask, fill_pad, fused_tail;
+};
+struct Schedule {
+  bool embed_fused;                        // one launch, else im2col -> GEMM -> LayerNorm
+  uint8_t embed_emit, merge_emit[KVQ_MAX_STAGES];
+  bool merge_fused[KVQ_MAX_STAGES];
+  bool x16[KVQ_MAX_STAGES + 1];            // stage i's residual stream is fp16
+  std::vector<BlockStep> blocks;
+};
+
+static int build_schedule(const KvqSwinPlan* pl, const KvqSwinWeights* w, bool frag, int lo, int hi, Schedule& s) {
+  const KvqSwinCfg& cfg = pl->cfg;
+  const int last = cfg.num_stages - 1;
+  // ---- the residual stream of a stage in fp16 (round 6) --------------------------------------------------------------------------------
+  // x is written once and read once per block (8 C bytes per token in fp32): 41 % of the step's HBM traffic.  Where EVERY producer and
+  // consumer of a stage's stream is one of the token-per-lane launches (embedding / fused merge -> fused tails -> fused merge) the stream
+  // lives in fp16 — 2.9e-6 on the score of a 32 x 224 x 224 clip in an fp32 emulation, two orders below the 16-bit MFMA operands' own
+  // 3.6e-4 (tools/diag/resid16_probe.py): the stream carries 11 bits where every GEMM input is rounded to 8 or 11 anyway.  Forwards with
+  // feature taps keep fp32; a stage-split forward enters and leaves in fp32.
+  // Consumers that take an fp16 stream: the fused tails of every width (padded partitions too), the fused merge, every LayerNorm launch
+  // (a first block's norm1, the gather-LayerNorm of an un-fused merge); x16 holds only where every reader of the stage is one of them,
+  // so no fp32 reader (GEMM chain, tap, output copy, final LayerNorm) can meet an fp16 stream.
+  // the last stage keeps fp32 (its stream comes out of a GEMM epilogue and feeds the final LayerNorm and the fp32 feature output).
+  // KVQ_RESID16=0: fp32 everywhere (rounds 1-5); so does a plan with kvq_swin3d_plan_set_resid16(plan, 0).
+  static const bool resid16_env = !(getenv("KVQ_RESID16") && atoi(getenv("KVQ_RESID16")) == 0);
+  bool resid16 = resid16_env && pl->resid16;
+  for (float* t : pl->taps) resid16 = resid16 && t == nullptr;
+  // stage i -> i + 1 is the one-launch merge (csrc/merge.hip), up to C = 192 (see the merge's launch site)
+  auto fused_merge = [&](int i) -> bool { return w->merges[i].merge_pack && kvq_patch_merge_supported(pl->st[i].C) && pl->st[i].C <= 192; };
+  // Narrow stages (C <= 128; measured at C = 192: the fused launch loses 19 us to GEMM + attention — the rows would be read twice
+  // through the CU's 64 B/clk load path): the qkv GEMM is an HBM-bound launch whose 6 C bytes per row the attention launch reads right
+  // back): the attention workgroup of a (window, head) computes its own q | k | v from the norm1 rows (attn.hip,
+  // fused_qkv_prologue).  Un-padded partitions on the dense bias only.  Measured (bench.py --legs c2,no_sampler, two runs each,
+  // same box): 300.4 -> 314.6 videos/s with the sampler in the step, 315.5 -> 330.1 without; stage-0 launch 133.5 -> 117.3 us.
+  auto attn_fuses_qkv = [&](int i, int bk) -> bool {
+    return w->blocks[bk].bias_dense && w->blocks[bk].qkv_b && pl->st[i].Lp == pl->st[i].L && pl->st[i].C == 96 && pl->st[i].N <= 400; };
+  // a producer writes the next block's norm1 rows in ITS window order: un-padded partitions only (token -> window row is a bijection)
+  auto emits_ln1 = [](const StageGeom& g, int par) -> bool { return g.Lp == g.L && g.d_dst[par]; };
+  s.embed_fused = lo == 0 && w->embed_pack &&
+                  kvq_patch_embed_supported(cfg.in_chans, cfg.patch[0], cfg.patch[1], cfg.patch[2], cfg.embed_dim, pl->T, pl->H, pl->W);
+  KVQ_REQUIRE(lo > 0 || s.embed_fused || !frag, KVQ_ERR_UNSUPPORTED, "kvq_swin3d_forward_fragments: this plan does not take the fused patch-embedding launch");
+  s.embed_emit = s.embed_fused && emits_ln1(pl->st[0], 0) ? kEmitLn1 : kEmitNone;
+  uint8_t emit = s.embed_emit;             // what the producer in front of the next block wrote for it
+  int blk = 0;
+  for (int i = 0; i < lo; ++i) blk += pl->st[i].depth;
+  for (int i = lo; i <= hi; ++i) {
+    const StageGeom& g = pl->st[i];
+    const int hidden = cfg.mlp_ratio * g.C;
+    // the producer writes fp16: the embedding, the fused merge, or — fp16 OPERANDS only: its 16-bit store is then the stream's type — the
+    // reduction GEMM of an un-fused merge (Swin-B's stage 2, 18 of its 24 blocks, sits behind one).  A stage-split call (KSVQE: stages
+    // 0-1, modulation, stage 2, modulation, stage 3) takes its entry stream from `io` in fp32 and hands the stream behind its last merge
+    // back in fp32: the stages strictly inside the call follow the same rule as in a whole forward
+    bool x16 = resid16 && i < last && (i == 0 ? s.embed_fused : i > lo && (fused_merge(i - 1) || pl->dtype == KVQ_DT_FP16));
+    for (int b = 0; b < g.depth; ++b, ++blk) {
+      const KvqSwinBlockW& bw = w->blocks[blk];
+      KVQ_REQUIRE(bw.norm1_w && bw.norm1_b && bw.rpb_table && bw.qkv_w && bw.proj_w && bw.fc1_w && bw.fc2_w, KVQ_ERR_NULL,
+                  "kvq_swin3d_forward: block %d weights incomplete", blk);
+      BlockStep t{};
+      t.i = i; t.blk = blk; t.par = (b & 1) && g.shifted_any ? 1 : 0; t.npar = ((b + 1) & 1) && g.shifted_any ? 1 : 0;
+      // padded partition: norm1 in TOKEN order, qkv over the tokens only (rows scattered to their window rows by the epilogue)
+      const bool padded = g.Lp != g.L && bw.qkv_b;
+      t.ln1 = emit != kEmitNone ? kFromProducer : padded ? kLnTokens : kLnWindows;
+      t.qkv = emit == kEmitQkv ? kQkvProducer : padded ? kQkvGemmPadded : attn_fuses_qkv(i, blk) ? kQkvInAttn : kQkvGemm;
+      t.dense = bw.bias_dense != nullptr;
+      // the padding rows' q | k | v = qkv(0) = bias: attention32 writes them into its own K | V images (pad_mask); the gather path
+      // reads them from the buffer
+      t.pad_mask = padded && t.dense && g.d_padmask[t.par];
+      t.fill_pad = t.qkv == kQkvGemmPadded && !t.pad_mask;
+      // shifted blocks of the (8,7,7) window with a half-window depth shift: the last window slab along D is depth-split
+      const int slabs = g.Dp / g.ws[0];
+      t.dsplit_from = (t.par == 1 && g.N == 392 && g.ws[0] == 8 && g.ws[1] == 7 && g.ws[2] == 7 && g.ss[0] == 4 && slabs >= 1)
+                          ? g.nW - g.nW / slabs : -1;
+      t.fused_tail = bw.tail_pack && kvq_block_tail_supported(g.C, hidden);
+      x16 = x16 && t.fused_tail && g.d_dst[t.par];
+      // What the fused tail writes for the next block.  Padded partitions could take its norm1 rows in token order (through an identity
+      // map; measured on C5: 19 LayerNorm launches / 0.51 ms saved, but the emitting form of the C = 512 tail costs +25 us per launch (it
+      // spills): 12.9 vs 13.0 ms serial, 20.9 vs 21.2-22.0 videos/s with two steps in flight) — not taken.
+      // Round 5: a padded partition takes the next block's q | k | v from this launch too (token -> window row of the NEXT partition,
+      // rows of Lp per clip; the padding rows are written by the attention launch, pad_mask) — the LayerNorm launch, the qkv GEMM and
+      // the norm1 round trip of every block of Swin-B at 64 x 256 x 256 are gone (C5 23.8 -> 25.05 videos/s, +5.2 %, same box alternating: profiles/r05_padded_qkv_ab.txt);
+      // the C = 512 tail in hidden chunks of 128 emits without the spills the comment above met.
+      // q | k | v (C = 128 / 192 / 256 / 384 / 512, the image path's q scale): no norm1 rows, no qkv GEMM launch (unless its attention
+      // launch projects q | k | v itself).
+      emit = kEmitNone;
+      if (t.fused_tail && b + 1 < g.depth) {
+        const KvqSwinBlockW& nb = w->blocks[blk + 1];
+        const bool rows = g.d_dst[t.npar] && (g.Lp == g.L || (g.d_padmask[t.npar] && nb.bias_dense));
+        emit = rows && !attn_fuses_qkv(i, blk + 1) && nb.qkv_pack && nb.qkv_b && nb.bias_dense && kvq_block_tail_qkv_pack_bytes(g.C, hidden) > 0
+                   ? kEmitQkv : emits_ln1(g, t.npar) ? kEmitLn1 : kEmitNone;
+      }
+      t.emit = emit;
+      s.blocks.push_back(t);
+    }
+    s.x16[i] = x16;
+    if (i < last) {
+      const KvqSwinMergeW& mw = w->merges[i];
+      KVQ_REQUIRE(mw.norm_w && mw.norm_b && mw.red_w, KVQ_ERR_NULL, "kvq_swin3d_forward: merge %d weights missing", i);
+      s.merge_fused[i] = fused_merge(i);
+      s.merge_emit[i] = emit = s.merge_fused[i] && i < hi && emits_ln1(pl->st[i + 1], 0) ? kEmitLn1 : kEmitNone;
+    }
+  }
+  return KVQ_OK;
+}
+}  // namespace kvq
+
 // stages stage_lo .. stage_hi of the trunk.  stage_lo == 0: starts from the clip x (patch embedding first); otherwise from
 // the residual stream `io` (fp32 channels-last (B, D, H_lo, W_lo, C_lo), copied into the workspace).  Afterwards `io`, when
 // given, receives the residual stream behind stage_hi (incl. its PatchMerging), and — stage_hi being the last stage — `feat`,
-// when given, the final LayerNorm of it.
+// when given, the final LayerNorm of it.  The schedule is built first: a forward it refuses enqueues nothing.
 static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float* x, const KvqFragmentSource* frag, int stage_lo, int stage_hi, float* io,
                     float* feat, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace kvq;
@@ -484,301 +600,181 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
   KVQ_REQUIRE(io || (feat && stage_hi == pl->cfg.num_stages - 1), KVQ_ERR_NULL, "kvq_swin3d_forward: no output buffer");
   KVQ_REQUIRE(workspace_bytes >= pl->ws_bytes, KVQ_ERR_WORKSPACE, "kvq_swin3d_forward: workspace %zu < %zu bytes",
               workspace_bytes, pl->ws_bytes);
+  Schedule s{};
+  KVQ_TRY(build_schedule(pl, w, frag != nullptr, stage_lo, stage_hi, s));
   hipStream_t st = (hipStream_t)stream;
   const KvqSwinCfg& cfg = pl->cfg;
-  const int B = pl->B;
+  const int B = pl->B, last = cfg.num_stages - 1;
   unsigned char* ws = (unsigned char*)workspace;
   pl->run_ws = ws;
-  float* xa = (float*)(ws + pl->off_x0);
-  float* xb = (float*)(ws + pl->off_x1);
-  uint16_t* bln = (uint16_t*)(ws + pl->off_ln);
-  uint16_t* bbig = (uint16_t*)(ws + pl->off_big);
-  uint16_t* bo = (uint16_t*)(ws + pl->off_o);
+  float *cur = (float*)(ws + pl->off_x0), *oth = (float*)(ws + pl->off_x1);
+  uint16_t *bln = (uint16_t*)(ws + pl->off_ln), *bbig = (uint16_t*)(ws + pl->off_big), *bo = (uint16_t*)(ws + pl->off_o);
   pl->ev_used = pl->profile ? pl->ev_used : 0;
-
-  // ---- the residual stream of a stage in fp16 (round 6) --------------------------------------------------------------------------------
-  // x is written once and read once per block (8 C bytes per token in fp32): 41 % of the step's HBM traffic.  Where EVERY producer and
-  // consumer of a stage's stream is one of the token-per-lane launches (embedding / fused merge -> fused tails -> fused merge) the stream
-  // lives in fp16 — 2.9e-6 on the score of a 32 x 224 x 224 clip in an fp32 emulation, two orders below the 16-bit MFMA operands' own
-  // 3.6e-4 (tools/diag/resid16_probe.py): the stream carries 11 bits where every GEMM input is rounded to 8 or 11 anyway.  Decided by
-  // geometry and weights only (never by the batch); forwards with feature taps keep fp32; a stage-split forward enters and leaves in fp32.
-  // Consumers that take an fp16 stream: the fused tails of every width (padded partitions too), the fused merge, every LayerNorm launch
-  // (a first block's norm1, the gather-LayerNorm of an un-fused merge);
-  // the last stage keeps fp32 (its stream comes out of a GEMM epilogue and feeds the final LayerNorm and the fp32 feature output).
-  // KVQ_RESID16=0: fp32 everywhere (rounds 1-5); so does a plan with kvq_swin3d_plan_set_resid16(plan, 0).
-  static const bool resid16_env = !(getenv("KVQ_RESID16") && atoi(getenv("KVQ_RESID16")) == 0);
-  const bool resid16_on = resid16_env && pl->resid16;
   // the range detector of the launches that write an fp16 stream: stage i's writers OR bit i into the caller's word
   auto range_of = [&](int stage) -> RangeFlag { return RangeFlag{pl->range_word, 1u << stage}; };
-  bool any_tap = false;
-  for (float* t : pl->taps) any_tap = any_tap || t != nullptr;
-  // Which launches the forward takes, each decided in ONE place: the fp16-stream rule below and the launch sites ask the same predicates.
-  // By geometry and weights only, never by the batch.
-  // stage i -> i + 1 is the one-launch merge (csrc/merge.hip), up to C = 192 (see the merge's launch site)
-  auto fused_merge = [&](int i) -> bool {
-    return i >= 0 && i < cfg.num_stages - 1 && w->merges[i].merge_pack && kvq_patch_merge_supported(pl->st[i].C) && pl->st[i].C <= 192;
+
+  // norm1 + pad + roll + window_partition, then q | k | v, unless the producer in front of the block wrote them
+  auto norm1_qkv = [&](const BlockStep& t, const StageGeom& g, const KvqSwinBlockW& bw) -> int {
+    const int C = g.C;
+    // attn32.hip (bias image) keeps its scores in log2 units: q is scaled by head_dim^-0.5 * log2(e) there; the gather path takes
+    // head_dim^-0.5.
+    const float qs = bw.bias_dense ? kQScaleLog2 : kQScale;
+    if (t.ln1 != kFromProducer)
+      KVQ_TRY(ln(pl, st, cur, t.ln1 == kLnTokens ? nullptr : g.d_src[t.par], 1, g.L, t.ln1 == kLnTokens ? g.L : g.Lp, C, bw.norm1_w,
+                 bw.norm1_b, bln, nullptr, s.x16[t.i]));
+    if (t.qkv == kQkvGemm)
+      KVQ_TRY_UNLESS(8 | (t.i == last ? 32 : 0), gemm(pl, st, KVQ_K_GEMM_QKV, bln, bw.qkv_w, bw.qkv_b, B * g.Lp, 3 * C, C, KVQ_EPI_QKV_BF16, bbig, nullptr, g.nH, qs));
+    if (t.qkv == kQkvGemmPadded)
+      KVQ_TRY(gemm(pl, st, KVQ_K_GEMM_QKV, bln, bw.qkv_w, bw.qkv_b, B * g.L, 3 * C, C, KVQ_EPI_QKV_BF16, bbig, nullptr, g.nH,
+                   qs, g.d_dst[t.par], g.L, g.Lp));
+    if (t.fill_pad) KVQ_TRY(kvq_qkv_fill_pad(bbig, bw.qkv_b, g.d_pad[t.par], g.Lp - g.L, B, g.Lp, g.nH, qs, pl->dtype, st));
+    return KVQ_OK;
   };
-  const bool embed_fused = w->embed_pack && kvq_patch_embed_supported(cfg.in_chans, cfg.patch[0], cfg.patch[1], cfg.patch[2], cfg.embed_dim, pl->T, pl->H, pl->W);
-  // block `bk` (index into w->blocks) of stage i: proj + norm2 + MLP (+ the next block's norm1 or q | k | v) as one launch
-  auto fused_tail = [&](int i, int bk) -> bool { return w->blocks[bk].tail_pack && kvq_block_tail_supported(pl->st[i].C, cfg.mlp_ratio * pl->st[i].C); };
-  // block `bk` of stage i: its attention launch computes its own q | k | v from the norm1 rows (C = 96, un-padded partitions, bias image)
-  auto attn_fuses_qkv = [&](int i, int bk) -> bool {
-    const StageGeom& g = pl->st[i];
-    const KvqSwinBlockW& bw = w->blocks[bk];
-    return bw.bias_dense && bw.qkv_b && g.Lp == g.L && g.C == 96 && g.N <= 400;
-  };
-  bool x16[KVQ_MAX_STAGES] = {false, false, false, false};
-  if (resid16_on && !any_tap) {
-    // a stage-split call (KSVQE: stages 0-1, modulation, stage 2, modulation, stage 3) takes its entry stream from `io` in fp32 and hands the
-    // stream behind its last merge back in fp32: the stages strictly inside the call follow the same rule as in a whole forward
-    int blk0 = 0;
-    for (int i = 0; i < cfg.num_stages - 1 && i <= stage_hi; blk0 += pl->st[i].depth, ++i) {
-      if (i < stage_lo) continue;
-      const StageGeom& g = pl->st[i];
-      // the producer writes fp16: the embedding, the fused merge, or — fp16 OPERANDS only: its 16-bit store is then the stream's type — the
-      // reduction GEMM of an un-fused merge (Swin-B's stage 2, 18 of its 24 blocks, sits behind one)
-      const bool produced16 = i == 0 ? (stage_lo == 0 && embed_fused) : (i > stage_lo && (fused_merge(i - 1) || pl->dtype == KVQ_DT_FP16));
-      bool ok = produced16;
-      for (int b = 0; ok && b < g.depth; ++b) {
-        const KvqSwinBlockW& bw = w->blocks[blk0 + b];
-        const int par = (b & 1) && g.shifted_any ? 1 : 0;
-        ok = fused_tail(i, blk0 + b) && bw.norm1_w && bw.norm1_b && g.d_dst[par];
-      }
-      x16[i] = ok;
+
+  auto attention = [&](const BlockStep& t, const StageGeom& g, const KvqSwinBlockW& bw) -> int {
+    const int C = g.C, M = B * g.Lp;
+    if (!t.dense) {
+      // 4*Lp*N*C flops per block; bytes: q,k,v in + o out (16-bit)
+      Bracket br(pl, st, KVQ_K_ATTN, (cfg.frag_bias[t.i] ? 2 : 0) + t.par, 4.0 * M * g.N * C, 2.0 * 4.0 * M * C);
+      return kvq_window_attention(bbig, g.d_tok[t.par], bw.rpb_table, cfg.frag_bias[t.i] ? bw.fpb_table : nullptr, bw.bias_pack,
+                                  pl->table_len, pl->center, B * g.nW, g.nW, g.N, g.nH, t.par, pl->dtype, bo, st);
     }
-  }
-  bool x16_cur = false;                                        // the stream `cur` holds right now
-  auto f32_only = [&](const char* what) -> int {               // a launch that reads or writes the stream as fp32 met an fp16 one: a bug above, never garbage
-    KVQ_REQUIRE(!x16_cur, KVQ_ERR_UNSUPPORTED, "kvq_swin3d_forward: internal: %s on an fp16 residual stream", what);
+    // + the dense bias once per step: 4 B per score of every (window, head)
+    const bool fq = t.qkv == kQkvInAttn;
+    Bracket br(pl, st, KVQ_K_ATTN, 4 + t.par, 4.0 * M * g.N * C + (fq ? 6.0 * M * C * C : 0.0),
+               (fq ? 2.0 * 2.0 * M * C + 6.0 * C * C : 2.0 * 4.0 * M * C) + (double)kvq_swin3d_bias_dense_bytes(pl, t.blk));
+    KvqAttnDenseArgs aa{};
+    aa.qkv = bbig; aa.bias_dense = bw.bias_dense; aa.n_types = bias_types(g, t.par); aa.BW = B * g.nW; aa.nW = g.nW; aa.N = g.N;
+    aa.num_heads = g.nH; aa.dtype = pl->dtype; aa.out = bo; aa.tile_skip = (const uint32_t*)g.d_skip[t.par]; aa.dsplit_from = t.dsplit_from;
+    if (fq) { aa.x_ln = bln; aa.w_qkv = bw.qkv_w; aa.b_qkv = bw.qkv_b; aa.q_scale = kQScaleLog2; }
+    if (t.pad_mask) { aa.pad_mask = (const uint32_t*)g.d_padmask[t.par]; aa.b_qkv = bw.qkv_b; }
+    KVQ_TRY_UNLESS(1 | (t.i == last ? 32 : 0), kvq_window_attention32(&aa, st));
+    return KVQ_OK;
+  };
+
+  auto tail = [&](const BlockStep& t, const StageGeom& g, const KvqSwinBlockW& bw) -> int {
+    const int C = g.C, M = B * g.Lp, ML = B * g.L, hidden = cfg.mlp_ratio * C, skip_last = t.i == last ? 32 : 0;
+    if (t.fused_tail) {
+      // proj + window_reverse + roll back + crop + residual + norm2 + Mlp + residual [+ the next block's norm1 rows or q | k | v]
+      const bool e1 = t.emit == kEmitLn1, eq = t.emit == kEmitQkv, x16 = s.x16[t.i];
+      KvqBlockTailArgs ta{};
+      ta.attn = bo; ta.x = cur; ta.scatter_map = g.d_src[t.par]; ta.map_rows = g.Lp; ta.out_rows = g.L;
+      ta.M = M; ta.C = C; ta.hidden = hidden; ta.pack = bw.tail_pack; ta.eps = 1e-5f; ta.dtype = pl->dtype; ta.x_f16 = x16 ? 1 : 0;
+      if (g.Lp != g.L) ta.attn_gather = g.d_dst[t.par];      // padded windows: walk the tokens, not the window rows
+      if (t.emit != kEmitNone) {
+        const KvqSwinBlockW& nb = w->blocks[t.blk + 1];
+        ta.next_norm_w = nb.norm1_w; ta.next_norm_b = nb.norm1_b; ta.next_dst = g.d_dst[t.npar]; ta.next_rows = g.Lp;
+        if (eq) { ta.next_qkv_pack = nb.qkv_pack; ta.next_qkv_b = nb.qkv_b; ta.qkv_out = bbig; ta.q_scale = kQScaleLog2; ta.num_heads = g.nH; }
+        else ta.next_ln = bln;
+      }
+      Bracket br(pl, st, KVQ_K_TAIL, kvq::tailmm_geometry_code(C, hidden) * 1000 + (C / 32) * 10 + t.emit, 2.0 * M * C * C + 4.0 * (double)ML * C * hidden + (eq ? 6.0 * M * C * C : 0.0),
+                 (double)M * C * 2.0 + (double)ML * C * ((x16 ? 4.0 : 8.0) + (e1 ? 2.0 : 0.0) + (eq ? 6.0 : 0.0)));
+      KVQ_TRY_UNLESS(C <= 192 ? 2 : 4, block_tail_launch(&ta, range_of(t.i), st));
+      return KVQ_OK;
+    }
+    // proj + window_reverse + roll back + crop + residual.  Padded partition: over the tokens (A rows gathered through token ->
+    // window row, output in place in token order) instead of over the window rows with the padding rows dropped in the epilogue
+    if (g.Lp != g.L) {
+      KvqGemmArgs pa{};
+      pa.A = bo; pa.W = bw.proj_w; pa.bias = bw.proj_b; pa.M = ML; pa.N = C; pa.K = C; pa.epilogue = KVQ_EPI_RESID_F32; pa.out_f32 = cur;
+      pa.dtype = pl->dtype; pa.a_gather = g.d_dst[t.par]; pa.a_rows = g.L; pa.a_phys_rows = g.Lp;
+      Bracket br(pl, st, KVQ_K_GEMM_PROJ, gemm_variant(ML, C, C) * 10 + KVQ_EPI_RESID_F32, 2.0 * M * C * C,
+                 2.0 * ((double)ML * C + (double)C * C) + 8.0 * ML * C);
+      KVQ_TRY(kvq_gemm_bf16(&pa, st));
+    } else {
+      KVQ_TRY_UNLESS(skip_last, gemm(pl, st, KVQ_K_GEMM_PROJ, bo, bw.proj_w, bw.proj_b, M, C, C, KVQ_EPI_RESID_F32, nullptr, cur, 0, 1.f,
+                                     g.d_src[t.par], g.Lp, g.L));
+    }
+    // norm2 + fc1 + GELU + fc2 + residual
+    KVQ_TRY(ln(pl, st, cur, nullptr, 1, g.L, g.L, C, bw.norm2_w, bw.norm2_b, bln, nullptr));
+    KVQ_TRY_UNLESS(skip_last, gemm(pl, st, KVQ_K_GEMM_FC1, bln, bw.fc1_w, bw.fc1_b, ML, hidden, C, KVQ_EPI_GELU_BF16, bbig, nullptr));
+    KVQ_TRY_UNLESS(skip_last, gemm(pl, st, KVQ_K_GEMM_FC2, bbig, bw.fc2_w, bw.fc2_b, ML, C, hidden, KVQ_EPI_RESID_F32, nullptr, cur));
+    return KVQ_OK;
+  };
+
+  // PatchMerging of stage i into the stream of stage i + 1, whose first block is s.blocks[next] (when the call runs it)
+  auto merge = [&](int i, size_t next) -> int {
+    const StageGeom& g = pl->st[i];
+    const KvqSwinMergeW& mw = w->merges[i];
+    const int C = g.C, Ln = g.Dn * g.Hn * g.Wn;
+    const bool in16 = s.x16[i], out16 = s.x16[i + 1], e1 = s.merge_emit[i] == kEmitLn1;
+    if (s.merge_fused[i]) {
+      // concat + LayerNorm(4C) + reduction [+ the next stage's first norm1 in its window order] as one launch (csrc/merge.hip).
+      // C = 96: 37.5 us against 26.3 + 25.6 + 15.9 (Swin-T, 4 clips); C = 128: +0.5-1 % on C5.  C = 192 exists and is tested, but
+      // the 576 KB matrix streams through LDS for 98 workgroups of one wave per SIMD: 66.9 us against 16.2 + 24.8 + 15.3 alone on the chip;
+      // taken since round 5: level on the 4-lane line with two launches fewer (profiles/r05_lane_experiments.txt)
+      KvqPatchMergeArgs ma{};
+      ma.x = cur; ma.merge_map = g.d_merge; ma.B = B; ma.L = g.L; ma.Ln = Ln; ma.C = C; ma.pack = mw.merge_pack; ma.out = oth;
+      ma.eps = 1e-5f; ma.dtype = pl->dtype; ma.x_f16 = in16 ? 1 : 0; ma.out_f16 = out16 ? 1 : 0;
+      if (e1) {
+        const KvqSwinBlockW& nb = w->blocks[s.blocks[next].blk];
+        ma.next_norm_w = nb.norm1_w; ma.next_norm_b = nb.norm1_b; ma.next_dst = pl->st[i + 1].d_dst[0]; ma.next_ln = bln; ma.next_rows = pl->st[i + 1].Lp;
+      }
+      Bracket br(pl, st, KVQ_K_MERGE, s.merge_emit[i], 2.0 * B * Ln * (double)(2 * C) * (4 * C),
+                 (double)B * Ln * 4 * C * (in16 ? 2.0 : 4.0) + (double)B * Ln * 2 * C * ((out16 ? 2.0 : 4.0) + (e1 ? 2.0 : 0.0)));
+      KVQ_TRY_UNLESS(128, patch_merge_launch(&ma, range_of(i + 1), st));
+    } else {
+      KVQ_TRY(ln(pl, st, cur, g.d_merge, 4, g.L, Ln, C, mw.norm_w, mw.norm_b, bln, nullptr, in16));
+      // the reduction GEMM writes the next stage's stream: fp32, or fp16 rows (fp16 operands) through its 16-bit store
+      KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, out16 ? KVQ_EPI_BIAS_BF16 : KVQ_EPI_STORE_F32,
+                               out16 ? reinterpret_cast<uint16_t*>(oth) : nullptr, out16 ? nullptr : oth, 0, 1.f, nullptr, 0, 0,
+                               out16 ? range_of(i + 1) : RangeFlag{nullptr, 0}));
+    }
+    std::swap(cur, oth);
+    return KVQ_OK;
+  };
+
+  auto tap = [&](int idx, size_t elems) -> int {          // feats[idx] of the reference's forward (multi / layer): fp32 streams only
+    if (pl->taps.empty() || !pl->taps[idx]) return KVQ_OK;
+    KVQ_CHECK_HIP(hipMemcpyAsync(pl->taps[idx], cur, elems * sizeof(float), hipMemcpyDeviceToDevice, st));
     return KVQ_OK;
   };
 
   // ---- PatchEmbed3D (swin_backbone.py:715-733): one fused launch, or im2col -> GEMM(+bias) -> LayerNorm ----
   const int L0 = pl->D0 * pl->H0 * pl->W0, E = cfg.embed_dim;
-  float* cur = xa;
-  float* oth = xb;
-  bool first_ln1_ready = false;
   if (stage_lo > 0) {
-    const StageGeom& g0 = pl->st[stage_lo];
-    KVQ_CHECK_HIP(hipMemcpyAsync(xa, io, (size_t)B * g0.L * g0.C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else if (embed_fused) {
+    KVQ_CHECK_HIP(hipMemcpyAsync(cur, io, (size_t)B * pl->st[stage_lo].L * pl->st[stage_lo].C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  } else if (s.embed_fused) {
     KvqPatchEmbedArgs ea{};
     ea.x = x; ea.frag = frag; ea.B = B; ea.in_chans = cfg.in_chans; ea.T = pl->T; ea.H = pl->H; ea.W = pl->W;
     ea.pd = cfg.patch[0]; ea.ph = cfg.patch[1]; ea.pw = cfg.patch[2]; ea.embed_dim = E; ea.pack = w->embed_pack;
-    ea.has_norm = w->embed_ln_w ? 1 : 0; ea.out = xa; ea.eps = 1e-5f; ea.dtype = pl->dtype; ea.out_f16 = x16[0] ? 1 : 0;
-    x16_cur = x16[0];
-    const StageGeom& g0 = pl->st[0];
-    if (g0.Lp == g0.L && g0.d_dst[0] && w->blocks[0].norm1_w && w->blocks[0].norm1_b) {     // + norm1 / partition of the first block
-      ea.next_norm_w = w->blocks[0].norm1_w; ea.next_norm_b = w->blocks[0].norm1_b; ea.next_dst = g0.d_dst[0];
-      ea.next_ln = bln; ea.next_rows = g0.Lp;
-      first_ln1_ready = true;
+    ea.has_norm = w->embed_ln_w ? 1 : 0; ea.out = cur; ea.eps = 1e-5f; ea.dtype = pl->dtype; ea.out_f16 = s.x16[0] ? 1 : 0;
+    const bool e1 = s.embed_emit == kEmitLn1;
+    if (e1) {                                            // + norm1 / partition of the first block
+      ea.next_norm_w = w->blocks[0].norm1_w; ea.next_norm_b = w->blocks[0].norm1_b; ea.next_dst = pl->st[0].d_dst[0];
+      ea.next_ln = bln; ea.next_rows = pl->st[0].Lp;
     }
     const double px = (double)B * L0 * pl->K0;
-    Bracket br(pl, st, KVQ_K_EMBED, (first_ln1_ready ? 1 : 0) + (frag ? 2 : 0), 2.0 * B * L0 * (double)E * pl->K0,
-               px * (frag ? 1.0 : 4.0) + (double)B * L0 * E * ((x16[0] ? 2.0 : 4.0) + (first_ln1_ready ? 2.0 : 0.0)));
+    Bracket br(pl, st, KVQ_K_EMBED, s.embed_emit + (frag ? 2 : 0), 2.0 * B * L0 * (double)E * pl->K0,
+               px * (frag ? 1.0 : 4.0) + (double)B * L0 * E * ((s.x16[0] ? 2.0 : 4.0) + (e1 ? 2.0 : 0.0)));
     KVQ_TRY_UNLESS(64, patch_embed_launch(&ea, range_of(0), st));
   } else {
-    KVQ_REQUIRE(!frag, KVQ_ERR_UNSUPPORTED, "kvq_swin3d_forward_fragments: this plan does not take the fused patch-embedding launch");
     {
-      const double px = (double)B * pl->D0 * pl->H0 * pl->W0 * pl->K0;
-      Bracket br(pl, st, KVQ_K_IM2COL, 0, 0.0, px * 6.0);
+      Bracket br(pl, st, KVQ_K_IM2COL, 0, 0.0, (double)B * pl->D0 * pl->H0 * pl->W0 * pl->K0 * 6.0);
       KVQ_TRY(kvq_patch_im2col(x, B, cfg.in_chans, pl->T, pl->H, pl->W, cfg.patch[0], cfg.patch[1], cfg.patch[2], pl->dtype,
                                bbig, st));
     }
-    KVQ_TRY(gemm(pl, st, KVQ_K_GEMM_EMBED, bbig, w->embed_w, w->embed_b, B * L0, E, pl->K0, KVQ_EPI_STORE_F32, nullptr,
-                 xb));
-    if (w->embed_ln_w) {
-      KVQ_TRY(ln(pl, st, xb, nullptr, 1, L0, L0, E, w->embed_ln_w, w->embed_ln_b, nullptr, xa));
-    } else {
-      cur = xb; oth = xa;
-    }
+    KVQ_TRY(gemm(pl, st, KVQ_K_GEMM_EMBED, bbig, w->embed_w, w->embed_b, B * L0, E, pl->K0, KVQ_EPI_STORE_F32, nullptr, oth));
+    if (w->embed_ln_w) KVQ_TRY(ln(pl, st, oth, nullptr, 1, L0, L0, E, w->embed_ln_w, w->embed_ln_b, nullptr, cur));
+    else std::swap(cur, oth);
   }
-  auto tap = [&](int idx, size_t elems) -> int {          // feats[idx] of the reference's forward (multi / layer)
-    if (pl->taps.empty() || !pl->taps[idx]) return KVQ_OK;
-    KVQ_TRY(f32_only("a feature tap"));
-    KVQ_CHECK_HIP(hipMemcpyAsync(pl->taps[idx], cur, elems * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return KVQ_OK;
-  };
   if (stage_lo == 0) KVQ_TRY(tap(0, (size_t)B * L0 * E));
 
-  int blk = 0;
-  for (int i = 0; i < stage_lo; ++i) blk += pl->st[i].depth;
-  size_t out_elems = 0;           // size of the residual stream behind the last stage run
-  bool merged_ln1_ready = false;  // the fused merge launch of the previous stage wrote the first norm1 rows of this one
+  size_t k = 0, out_elems = 0;     // out_elems: size of the residual stream behind the last stage run
   for (int i = stage_lo; i <= stage_hi; ++i) {
     const StageGeom& g = pl->st[i];
-    const int C = g.C, M = B * g.Lp, ML = B * g.L;
-    bool ln1_ready = (i == 0 && first_ln1_ready) || merged_ln1_ready;   // the producer (embed / previous tail / merge) already wrote this block's norm1 rows
-    bool qkv_ready = false;                                             // the previous block's tail already wrote this block's q | k | v
-    merged_ln1_ready = false;
-    if (i == stage_lo && i > 0) cur = xa, oth = xb;
-    for (int b = 0; b < g.depth; ++b, ++blk) {
-      const KvqSwinBlockW& bw = w->blocks[blk];
-      KVQ_REQUIRE(bw.norm1_w && bw.rpb_table && bw.qkv_w && bw.proj_w && bw.fc1_w && bw.fc2_w, KVQ_ERR_NULL,
-                  "kvq_swin3d_forward: block %d weights incomplete", blk);
-      const int par = (b & 1) && g.shifted_any ? 1 : 0;
-      // Narrow stages (C <= 128; measured at C = 192: the fused launch loses 19 us to GEMM + attention — the rows would be read twice
-      // through the CU's 64 B/clk load path): the qkv GEMM is an HBM-bound launch whose 6 C bytes per row the attention launch reads right
-      // back): the attention workgroup of a (window, head) computes its own q | k | v from the norm1 rows (attn.hip,
-      // fused_qkv_prologue).  Un-padded partitions on the dense bias only.  Measured (bench.py --legs c2,no_sampler, two runs each,
-      // same box): 300.4 -> 314.6 videos/s with the sampler in the step, 315.5 -> 330.1 without; stage-0 launch 133.5 -> 117.3 us.
-      const bool fuse_qkv = attn_fuses_qkv(i, blk);
-      // attn32.hip (bias image) keeps its scores in log2 units: q is scaled by head_dim^-0.5 * log2(e) there; the gather path takes
-      // head_dim^-0.5.  Which one a block takes depends on its weights and geometry only, never on the batch.
-      const float qs = bw.bias_dense ? kQScaleLog2 : kQScale;
-      // norm1 + pad + roll + window_partition
-      if (g.Lp != g.L && bw.qkv_b && qkv_ready) {
-        // padded partition whose q | k | v rows the previous block's tail wrote (window rows of the tokens; the padding rows are the
-        // attention launch's: pad_mask)
-      } else if (g.Lp != g.L && bw.qkv_b) {
-        // padded partition: norm1 in TOKEN order (written by the previous block's tail when there is one), qkv over the tokens only
-        // (rows scattered to their window rows by the epilogue); the padding rows' q | k | v = qkv(0) = bias
-        if (!ln1_ready) KVQ_TRY(ln(pl, st, cur, nullptr, 1, g.L, g.L, C, bw.norm1_w, bw.norm1_b, bln, nullptr, x16_cur));
-        KVQ_TRY(gemm(pl, st, KVQ_K_GEMM_QKV, bln, bw.qkv_w, bw.qkv_b, ML, 3 * C, C, KVQ_EPI_QKV_BF16, bbig, nullptr, g.nH,
-                     qs, g.d_dst[par], g.L, g.Lp));
-        // the padding rows' q | k | v = qkv(0) = bias: attention32 writes them into its own K | V images (pad_mask); the gather path
-        // reads them from the buffer
-        if (!(bw.bias_dense && g.d_padmask[par]))
-          KVQ_TRY(kvq_qkv_fill_pad(bbig, bw.qkv_b, g.d_pad[par], g.Lp - g.L, B, g.Lp, g.nH, qs, pl->dtype, st));
-      } else if (!qkv_ready) {
-        if (!ln1_ready) KVQ_TRY(ln(pl, st, cur, g.d_src[par], 1, g.L, g.Lp, C, bw.norm1_w, bw.norm1_b, bln, nullptr, x16_cur));
-        if (!fuse_qkv)
-          KVQ_TRY_UNLESS(8 | (i == cfg.num_stages - 1 ? 32 : 0), gemm(pl, st, KVQ_K_GEMM_QKV, bln, bw.qkv_w, bw.qkv_b, M, 3 * C, C, KVQ_EPI_QKV_BF16, bbig, nullptr, g.nH, qs));
-      }
-      ln1_ready = false;
-      qkv_ready = false;
-      if (bw.bias_dense) {
-        // + the dense bias once per step: 4 B per score of every (window, head)
-        Bracket br(pl, st, KVQ_K_ATTN, 4 + par, 4.0 * M * g.N * C + (fuse_qkv ? 6.0 * M * C * C : 0.0),
-                   (fuse_qkv ? 2.0 * 2.0 * M * C + 6.0 * C * C : 2.0 * 4.0 * M * C) + (double)kvq_swin3d_bias_dense_bytes(pl, blk));
-        KvqAttnDenseArgs aa{};
-        aa.qkv = bbig; aa.bias_dense = bw.bias_dense; aa.n_types = bias_types(g, par); aa.BW = B * g.nW; aa.nW = g.nW; aa.N = g.N;
-        aa.num_heads = g.nH; aa.dtype = pl->dtype; aa.out = bo; aa.tile_skip = (const uint32_t*)g.d_skip[par];
-        // shifted blocks of the (8,7,7) window with a half-window depth shift: the last window slab along D is depth-split
-        const int slabs = g.Dp / g.ws[0];
-        aa.dsplit_from = (par == 1 && g.N == 392 && g.ws[0] == 8 && g.ws[1] == 7 && g.ws[2] == 7 && g.ss[0] == 4 && slabs >= 1)
-                             ? g.nW - g.nW / slabs : -1;
-        if (fuse_qkv) { aa.x_ln = bln; aa.w_qkv = bw.qkv_w; aa.b_qkv = bw.qkv_b; aa.q_scale = qs; }
-        if (g.Lp != g.L && bw.qkv_b && g.d_padmask[par]) { aa.pad_mask = (const uint32_t*)g.d_padmask[par]; aa.b_qkv = bw.qkv_b; }
-        KVQ_TRY_UNLESS(1 | (i == cfg.num_stages - 1 ? 32 : 0), kvq_window_attention32(&aa, st));
-      } else {
-        // 4*Lp*N*C flops per block; bytes: q,k,v in + o out (16-bit)
-        Bracket br(pl, st, KVQ_K_ATTN, (cfg.frag_bias[i] ? 2 : 0) + par, 4.0 * M * g.N * C, 2.0 * 4.0 * M * C);
-        KVQ_TRY(kvq_window_attention(bbig, g.d_tok[par], bw.rpb_table, cfg.frag_bias[i] ? bw.fpb_table : nullptr,
-                                     bw.bias_pack,
-                                     pl->table_len, pl->center, B * g.nW, g.nW, g.N, g.nH, par, pl->dtype, bo,
-                                     st));
-      }
-      const int hidden = cfg.mlp_ratio * C;
-      if (fused_tail(i, blk)) {
-        // proj + window_reverse + roll back + crop + residual + norm2 + Mlp + residual [+ the next block's norm1]
-        KvqBlockTailArgs ta{};
-        ta.attn = bo; ta.x = cur; ta.scatter_map = g.d_src[par]; ta.map_rows = g.Lp; ta.out_rows = g.L;
-        ta.M = M; ta.C = C; ta.hidden = hidden; ta.pack = bw.tail_pack; ta.eps = 1e-5f; ta.dtype = pl->dtype;
-        ta.x_f16 = x16_cur ? 1 : 0;
-        const int npar = ((b + 1) & 1) && g.shifted_any ? 1 : 0;
-        if (g.Lp != g.L) ta.attn_gather = g.d_dst[par];      // padded windows: walk the tokens, not the window rows
-        // the next block's norm1 rows in ITS window order (un-padded partitions: token -> window row is a bijection).  Padded
-        // partitions could take them in token order (through an identity map; measured on C5: 19 LayerNorm launches / 0.51 ms saved,
-        // but the emitting form of the C = 512 tail costs +25 us per launch (it spills): 12.9 vs 13.0 ms serial, 20.9 vs 21.2-22.0
-        // videos/s with two steps in flight) — not taken.
-        // Round 5: a padded partition takes the next block's q | k | v from this launch too (token -> window row of the NEXT partition,
-        // rows of Lp per clip; the padding rows are written by the attention launch, pad_mask) — the LayerNorm launch, the qkv GEMM and
-        // the norm1 round trip of every block of Swin-B at 64 x 256 x 256 are gone (C5 23.8 -> 25.05 videos/s, +5.2 %, same box alternating: profiles/r05_padded_qkv_ab.txt);
-        // the C = 512 tail in hidden chunks of 128 emits without the spills the comment above met.
-        const bool padded_qkv = g.Lp != g.L && b + 1 < g.depth && g.d_dst[npar] && g.d_padmask[npar] && w->blocks[blk + 1].bias_dense;
-        const int32_t* nmap = (g.Lp == g.L || padded_qkv) ? g.d_dst[npar] : nullptr;
-        if (b + 1 < g.depth && nmap) {
-          const KvqSwinBlockW& nb = w->blocks[blk + 1];
-          KVQ_REQUIRE(nb.norm1_w && nb.norm1_b, KVQ_ERR_NULL, "kvq_swin3d_forward: block %d norm1 missing", blk + 1);
-          ta.next_norm_w = nb.norm1_w; ta.next_norm_b = nb.norm1_b; ta.next_dst = nmap;
-          ta.next_rows = g.Lp;
-          // the next block's q | k | v straight from this launch (C = 128 / 192 / 256 / 384 / 512, un-padded partitions, the image path's q scale):
-          // no norm1 rows, no qkv GEMM launch (unless its attention launch projects q | k | v itself).  By geometry and weights only, never by batch.
-          if (!attn_fuses_qkv(i, blk + 1) && nb.qkv_pack && nb.qkv_b && nb.bias_dense && (g.Lp == g.L || padded_qkv) && kvq_block_tail_qkv_pack_bytes(C, hidden) > 0) {
-            ta.next_qkv_pack = nb.qkv_pack; ta.next_qkv_b = nb.qkv_b; ta.qkv_out = bbig; ta.q_scale = kQScaleLog2; ta.num_heads = g.nH;
-            qkv_ready = true;
-          } else if (g.Lp == g.L) {
-            ta.next_ln = bln;
-            ln1_ready = true;
-          } else {                      // padded partition without the emission: the tail writes x only
-            ta.next_norm_w = nullptr; ta.next_norm_b = nullptr; ta.next_dst = nullptr; ta.next_rows = 0;
-          }
-        }
-        Bracket br(pl, st, KVQ_K_TAIL, kvq::tailmm_geometry_code(C, hidden) * 1000 + (C / 32) * 10 + (ln1_ready ? 1 : 0) + (qkv_ready ? 2 : 0), 2.0 * M * C * C + 4.0 * (double)ML * C * hidden + (qkv_ready ? 6.0 * M * C * C : 0.0),
-                   (double)M * C * 2.0 + (double)ML * C * ((x16_cur ? 4.0 : 8.0) + (ln1_ready ? 2.0 : 0.0) + (qkv_ready ? 6.0 : 0.0)));
-        KVQ_TRY_UNLESS(C <= 192 ? 2 : 4, block_tail_launch(&ta, range_of(i), st));
-        continue;
-      }
-      KVQ_TRY(f32_only("the proj / MLP GEMM chain"));
-      // proj + window_reverse + roll back + crop + residual.  Padded partition: over the tokens (A rows gathered through token ->
-      // window row, output in place in token order) instead of over the window rows with the padding rows dropped in the epilogue
-      if (g.Lp != g.L) {
-        KvqGemmArgs pa{};
-        pa.A = bo; pa.W = bw.proj_w; pa.bias = bw.proj_b; pa.M = ML; pa.N = C; pa.K = C; pa.epilogue = KVQ_EPI_RESID_F32; pa.out_f32 = cur;
-        pa.dtype = pl->dtype; pa.a_gather = g.d_dst[par]; pa.a_rows = g.L; pa.a_phys_rows = g.Lp;
-        Bracket br(pl, st, KVQ_K_GEMM_PROJ, gemm_variant(ML, C, C) * 10 + KVQ_EPI_RESID_F32, 2.0 * M * C * C,
-                   2.0 * ((double)ML * C + (double)C * C) + 8.0 * ML * C);
-        KVQ_TRY(kvq_gemm_bf16(&pa, st));
-      } else {
-        KVQ_TRY_UNLESS(i == cfg.num_stages - 1 ? 32 : 0, gemm(pl, st, KVQ_K_GEMM_PROJ, bo, bw.proj_w, bw.proj_b, M, C, C, KVQ_EPI_RESID_F32, nullptr, cur, 0, 1.f,
-                     g.d_src[par], g.Lp, g.L));
-      }
-      // norm2 + fc1 + GELU + fc2 + residual
-      KVQ_TRY(ln(pl, st, cur, nullptr, 1, g.L, g.L, C, bw.norm2_w, bw.norm2_b, bln, nullptr));
-      KVQ_TRY_UNLESS(i == cfg.num_stages - 1 ? 32 : 0, gemm(pl, st, KVQ_K_GEMM_FC1, bln, bw.fc1_w, bw.fc1_b, ML, cfg.mlp_ratio * C, C, KVQ_EPI_GELU_BF16, bbig,
-                   nullptr));
-      KVQ_TRY_UNLESS(i == cfg.num_stages - 1 ? 32 : 0, gemm(pl, st, KVQ_K_GEMM_FC2, bbig, bw.fc2_w, bw.fc2_b, ML, C, cfg.mlp_ratio * C, KVQ_EPI_RESID_F32,
-                   nullptr, cur));
+    for (int b = 0; b < g.depth; ++b, ++k) {
+      const BlockStep& t = s.blocks[k];
+      const KvqSwinBlockW& bw = w->blocks[t.blk];
+      KVQ_TRY(norm1_qkv(t, g, bw)); KVQ_TRY(attention(t, g, bw)); KVQ_TRY(tail(t, g, bw));
     }
-    if (i < cfg.num_stages - 1) {
-      const KvqSwinMergeW& mw = w->merges[i];
-      KVQ_REQUIRE(mw.norm_w && mw.norm_b && mw.red_w, KVQ_ERR_NULL, "kvq_swin3d_forward: merge %d weights missing", i);
-      const int Ln = g.Dn * g.Hn * g.Wn;
-      if (fused_merge(i)) {
-        // concat + LayerNorm(4C) + reduction [+ the next stage's first norm1 in its window order] as one launch (csrc/merge.hip).
-        // C = 96: 37.5 us against 26.3 + 25.6 + 15.9 (Swin-T, 4 clips); C = 128: +0.5-1 % on C5.  C = 192 exists and is tested, but
-        // the 576 KB matrix streams through LDS for 98 workgroups of one wave per SIMD: 66.9 us against 16.2 + 24.8 + 15.3 alone on the chip;
-        // taken since round 5: level on the 4-lane line with two launches fewer (profiles/r05_lane_experiments.txt)
-        KvqPatchMergeArgs ma{};
-        ma.x = cur; ma.merge_map = g.d_merge; ma.B = B; ma.L = g.L; ma.Ln = Ln; ma.C = C; ma.pack = mw.merge_pack; ma.out = oth;
-        ma.eps = 1e-5f; ma.dtype = pl->dtype; ma.x_f16 = x16_cur ? 1 : 0; ma.out_f16 = x16[i + 1] ? 1 : 0;
-        if (i + 1 <= stage_hi) {
-          const StageGeom& gn = pl->st[i + 1];
-          const KvqSwinBlockW& nb = w->blocks[blk];           // blk: the first block of stage i + 1
-          if (gn.Lp == gn.L && gn.d_dst[0] && nb.norm1_w && nb.norm1_b) {
-            ma.next_norm_w = nb.norm1_w; ma.next_norm_b = nb.norm1_b; ma.next_dst = gn.d_dst[0]; ma.next_ln = bln; ma.next_rows = gn.Lp;
-            merged_ln1_ready = true;
-          }
-        }
-        Bracket br(pl, st, KVQ_K_MERGE, merged_ln1_ready ? 1 : 0, 2.0 * B * Ln * (double)(2 * C) * (4 * C),
-                   (double)B * Ln * 4 * C * (x16_cur ? 2.0 : 4.0) + (double)B * Ln * 2 * C * ((x16[i + 1] ? 2.0 : 4.0) + (merged_ln1_ready ? 2.0 : 0.0)));
-        KVQ_TRY_UNLESS(128, patch_merge_launch(&ma, range_of(i + 1), st));
-        x16_cur = x16[i + 1];
-      } else {
-        KVQ_TRY(ln(pl, st, cur, g.d_merge, 4, g.L, Ln, C, mw.norm_w, mw.norm_b, bln, nullptr, x16_cur));
-        x16_cur = x16[i + 1];                                  // the reduction GEMM writes the next stage's stream: fp32, or fp16 rows (fp16 operands)
-        if (x16_cur) KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, KVQ_EPI_BIAS_BF16, reinterpret_cast<uint16_t*>(oth), nullptr,
-                                               0, 1.f, nullptr, 0, 0, range_of(i + 1)));
-        else KVQ_TRY_UNLESS(128, gemm(pl, st, KVQ_K_GEMM_MERGE, bln, mw.red_w, nullptr, B * Ln, 2 * C, 4 * C, KVQ_EPI_STORE_F32, nullptr,
-                     oth));
-      }
-      float* t = cur; cur = oth; oth = t;
-      out_elems = (size_t)B * Ln * 2 * C;
-    } else {
-      out_elems = (size_t)ML * C;
-    }
+    if (i < last) KVQ_TRY(merge(i, k));
+    out_elems = i < last ? (size_t)B * g.Dn * g.Hn * g.Wn * 2 * g.C : (size_t)B * g.L * g.C;
     KVQ_TRY(tap(i + 1, out_elems));
   }
-  if (io) {
-    KVQ_TRY(f32_only("the stage-split output copy"));
-    KVQ_CHECK_HIP(hipMemcpyAsync(io, cur, out_elems * sizeof(float), hipMemcpyDeviceToDevice, st));
-  }
-  if (feat && stage_hi == cfg.num_stages - 1) {
-    KVQ_TRY(f32_only("the final LayerNorm"));
-    const StageGeom& gl = pl->st.back();
-    KVQ_TRY(ln(pl, st, cur, nullptr, 1, gl.L, gl.L, gl.C, w->norm_w, w->norm_b, nullptr, feat));
-  }
+  if (io) KVQ_CHECK_HIP(hipMemcpyAsync(io, cur, out_elems * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (feat && stage_hi == last)
+    KVQ_TRY(ln(pl, st, cur, nullptr, 1, pl->st[last].L, pl->st[last].L, pl->st[last].C, w->norm_w, w->norm_b, nullptr, feat));
   return KVQ_OK;
 }
 
