@@ -496,6 +496,54 @@ int kvq_vqa_head(const float* feat, int B, int L, int C, int64_t stride_b, int64
                  int64_t stride_c, const float* w1t, const float* w1, const float* b1, int hidden, const float* w2,
                  const float* b2, float* scratch, float* score, void* stream);
 
+/* kvq_vqa_head that KEEPS the per-token map (the "local quality map" of the FAST-VQA family): additive, kvq_vqa_head is untouched.
+ *   tok_map      fp32 [B*L]: tok_map[b][l] = w2 . gelu(W1 f + b1) + b2 — head.py:65's qlt_score before the mean of :68 (b2 included,
+ *                so the map's mean is the score).  It doubles as the token pass's scratch.
+ *   D            depth slices of the token grid, tokens depth-major (l = d * L/D + ...); L % D == 0 or KVQ_ERR_SHAPE.
+ *   depth_score  NULL, or fp32 [B*D]: the mean over the L/D tokens of depth d (summed serially in token order) + b2.
+ *   score        fp32 [B], bit-identical to kvq_vqa_head on the same inputs: the same token kernel by the same rule, the same tree.
+ * Two launches, as kvq_vqa_head: the b2 write-back and the per-depth means ride in the mean launch. */
+int kvq_vqa_head_map(const float* feat, int B, int L, int C, int64_t stride_b, int64_t stride_l, int64_t stride_c,
+                     const float* w1t, const float* w1, const float* b1, int hidden, const float* w2, const float* b2,
+                     int D, float* tok_map, float* depth_score, float* score, void* stream);
+
+/* Quality paint: the token map of a trunk that read its clip through a KvqFragmentSource, painted back onto the geometry of the
+ * SOURCE frames.  The trunk's total stride is (2, 32, 32) (2 x 4 x 4 patch embedding, three 2 x 2 merges): with sh = Fh fs_h / Hf and
+ * sw = Fw fs_w / Wf, token (d, i', j') of clip b saw, on clip frames 2d and 2d + 1, the sh x sw source rectangle with origin
+ *   (hoff[i][j][tt] + (i' sh) % fs_h,  woff[i][j][tt] + (j' sw) % fs_w),   i = i' sh / fs_h,  j = j' sw / fs_w,  tt = 2d / aligned
+ * (get_spatial_fragments, fusion_datasets.py:64-117; hoff / woff are the absolute origins the struct carries).
+ * Supported (kvq_quality_paint_supported, host only, 1 / 0): sh, sw integers, fs_h % sh == 0, fs_w % sw == 0, T == 2 D, T % aligned == 0,
+ * aligned even, Hf Wf <= 1024, cell in {1, 2, 4, 8, 16, 32}, 1 <= n_clips <= 16.  Anything else: KVQ_ERR_UNSUPPORTED.
+ *
+ * heat / cover: fp32 [n_clips][D][ceil(Hs / cell)][ceil(Ws / cell)].  Output pixel (Y, X) is the source block of rows
+ * [cell Y, min(cell Y + cell, Hs)) and columns alike; area_k = its integer overlap with token rectangle k;
+ *   cover = float(sum_k area_k) / float(block pixels)
+ *   heat  = (sum_k float(area_k) * s_k) / float(sum_k area_k), 0 where nothing overlaps,
+ * the sum over the tokens with area_k > 0 in increasing row-major (i', j') order, starting from 0.f, with separately rounded fp32
+ * multiplies and adds and a correctly rounded divide: a defined bit pattern (cell == 1: a copy of the scores).
+ *
+ * overlay (NULL = none): uint8 [n_clips][n_ov][3][Hs][Ws], slice n drawn on clip frame 2 ov_depth[n] (uint8 frames only; the channel
+ * order is the source's).  With (lo, hi) = range[0], range[1] (device), inv = 1 / (hi - lo) in fp32 and s the pixel's cell == 1 heat:
+ *   q = rint(min(max((s - lo) * inv, 0), 1) * 255),  colour = (255 - q, q, 0)
+ *   covered pixel:   (src * (256 - alpha) + colour * alpha + 128) >> 8        uncovered pixel:  (src * dim + 128) >> 8
+ * A gather (no atomics, deterministic): one launch for heat / cover, one more when an overlay is asked for.  The frames are read
+ * only by the overlay; src->indirect is honoured, so the call can sit in a recorded graph. */
+typedef struct {
+  const KvqFragmentSource* src;   /* host struct: direct pointers or the indirect table */
+  int32_t T, D, Hf, Wf;           /* clip frames; token grid (D, Hf, Wf) */
+  int32_t cell;
+  const float* tok_map;           /* fp32 [n_clips][D][Hf][Wf] */
+  float* heat;
+  float* cover;
+  uint8_t* overlay;               /* may be NULL; the five below are read only with it */
+  int32_t ov_depth[16];           /* host: depth slice of each overlay, 0 <= . < D */
+  int32_t n_ov;                   /* 1..16 */
+  const float* range;             /* device float[2]: lo, hi */
+  int32_t alpha, dim;             /* 0..256 */
+} KvqQualityPaintArgs;
+int kvq_quality_paint_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell);
+int kvq_quality_paint(const KvqQualityPaintArgs* host_args, void* stream);
+
 /* VQAHead.forward's other branches (models/head.py:60-68; no reference config sets them): pre_pool != 0 averages the token grid
  * first (AdaptiveAvgPool3d((1,1,1)), head.py:61-62); num_class > 1 applies nn.Softmax() — implicit dim 1 = the classes — to
  * fc_last's outputs per token (head.py:66-67) before the mean over the tokens (head.py:68).

@@ -121,6 +121,12 @@ class KvqFragmentSource(C.Structure):
                 ("mean", C.c_float * 4), ("std", C.c_float * 4), ("indirect", p_void)]
 
 
+class KvqQualityPaintArgs(C.Structure):
+    _fields_ = [("src", C.POINTER(KvqFragmentSource)), ("T", C.c_int32), ("D", C.c_int32), ("Hf", C.c_int32), ("Wf", C.c_int32),
+                ("cell", C.c_int32), ("tok_map", p_void), ("heat", p_void), ("cover", p_void), ("overlay", p_void),
+                ("ov_depth", C.c_int32 * 16), ("n_ov", C.c_int32), ("range", p_void), ("alpha", C.c_int32), ("dim", C.c_int32)]
+
+
 class KvqPatchEmbedArgs(C.Structure):
     _fields_ = [("x", p_void), ("B", C.c_int32), ("in_chans", C.c_int32), ("T", C.c_int32), ("H", C.c_int32),
                 ("W", C.c_int32), ("pd", C.c_int32), ("ph", C.c_int32), ("pw", C.c_int32), ("embed_dim", C.c_int32),
@@ -218,6 +224,10 @@ SYMBOLS = {
     "kvq_patch_im2col": (i32, [p_void, i32, i32, i32, i32, i32, i32, i32, i32, i32, p_void, p_void]),
     "kvq_vqa_head": (i32, [p_void, i32, i32, i32, i64, i64, i64, p_void, p_void, p_void, i32, p_void, p_void, p_void,
                            p_void, p_void]),
+    "kvq_vqa_head_map": (i32, [p_void, i32, i32, i32, i64, i64, i64, p_void, p_void, p_void, i32, p_void, p_void, i32, p_void,
+                               p_void, p_void, p_void]),
+    "kvq_quality_paint_supported": (i32, [C.POINTER(KvqFragmentSource), i32, i32, i32, i32, i32]),
+    "kvq_quality_paint": (i32, [C.POINTER(KvqQualityPaintArgs), p_void]),
     "kvq_vqa_head_classes": (i32, [p_void, i32, i32, i32, i64, i64, i64, p_void, p_void, i32, p_void, p_void, i32, i32, p_void,
                                    p_void, p_void]),
     "kvq_simple_vqa_head": (i32, [p_void, i32, i32, i32, p_void, p_void, i32, p_void, p_void, p_void, p_void,

@@ -18,12 +18,13 @@ CSRC = os.path.join(PKG, "csrc")
 TAG = os.environ.get("KVQ_BUILD_TAG", "")
 LIB = os.path.join(PKG, f"libkvq_hip_{TAG}.so" if TAG else "libkvq_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "kvq_hip.h")
-SOURCES = ["common.cpp", "gemm.hip", "gemm256.hip", "ln.hip", "attn.hip", "attn32.hip", "misc.hip", "resize_aa.hip", "plan.hip", "conv.hip", "tail.hip", "tailmm.hip", "embed.hip", "merge.hip", "vit.hip", "convnet.hip", "bottleneck.hip", "slowneck.hip"]
+SOURCES = ["common.cpp", "gemm.hip", "gemm256.hip", "ln.hip", "attn.hip", "attn32.hip", "misc.hip", "qmap.hip", "resize_aa.hip", "plan.hip", "conv.hip", "tail.hip", "tailmm.hip", "embed.hip", "merge.hip", "vit.hip", "convnet.hip", "bottleneck.hip", "slowneck.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable"]
 # attn.hip is VALU-bound: SLP packing of adjacent f32 ops into v_pk_* costs more v_mov than it saves, and
 # NaN-honouring fmaxf inserts a canonicalising v_max per MFMA output (no NaN can arise: -inf only).
-EXTRA = {"attn.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "attn32.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "tail.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "tailmm.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "embed.hip": ["-fno-slp-vectorize"], "merge.hip": ["-fno-slp-vectorize"]}
+# qmap.hip: its results are specified to the bit with separately rounded multiplies and adds — no contraction into fma
+EXTRA = {"qmap.hip": ["-ffp-contract=off"], "attn.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "attn32.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "tail.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "tailmm.hip": ["-fno-slp-vectorize", "-fno-honor-nans"], "embed.hip": ["-fno-slp-vectorize"], "merge.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

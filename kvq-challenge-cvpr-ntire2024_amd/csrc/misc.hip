@@ -236,6 +236,36 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict_
   if (threadIdx.x == 0) out[b] = red[0] / (float)L + (b2 ? b2[0] : 0.f);
 }
 
+// mean_rows_kernel that keeps the map (kvq_vqa_head_map): the same strided partial sums and the same tree, so score[b] has the
+// same bits; the block then writes depth_score[b][d] = mean of the L/D tokens of depth d (one thread per depth, summed serially
+// in token order) + b2 and adds b2 to the map in place.  Every thread rewrites exactly the elements it read for its partial sum;
+// the depth means read the raw values, so the barrier between them and the write-back orders the two.
+__global__ __launch_bounds__(256) void mean_rows_map_kernel(float* __restrict__ v, int L, int D, const float* b2,
+                                                            float* __restrict__ depth_score, float* __restrict__ out) {
+  __shared__ float red[256];
+  const int b = blockIdx.x;
+  float s = 0.f;
+  for (int l = threadIdx.x; l < L; l += 256) s += v[(size_t)b * L + l];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  const float bias = b2 ? b2[0] : 0.f;
+  if (threadIdx.x == 0) out[b] = red[0] / (float)L + bias;
+  if (depth_score) {
+    const int n = L / D;
+    for (int d = threadIdx.x; d < D; d += 256) {
+      float a = 0.f;
+      for (int l = 0; l < n; ++l) a += v[(size_t)b * L + (size_t)d * n + l];
+      depth_score[(size_t)b * D + d] = a / (float)n + bias;
+    }
+  }
+  __syncthreads();
+  for (int l = threadIdx.x; l < L; l += 256) v[(size_t)b * L + l] += bias;
+}
+
 // ------------------------------------------------------------------------------------------------
 // simpleVQAHead (models/head.py:28-31): Linear(Cin->hidden) -> Linear(hidden->1) per frame, no activation.
 // One block per (b, t) frame row: 256 threads split Cin, each accumulates all hidden dots?  hidden=128,
@@ -503,27 +533,51 @@ extern "C" int kvq_patch_im2col(const float* x, int B, int Cin, int T, int H, in
   return KVQ_OK;
 }
 
+namespace kvq {
+// the token pass of kvq_vqa_head / kvq_vqa_head_map: tok[b*L + l] = w2 . gelu(W1 f + b1), on the fp32 matrix pipe when the shape allows
+static int vqa_head_tokens(const char* who, const float* feat, int B, int L, int C, int64_t stride_b, int64_t stride_l, int64_t stride_c,
+                           const float* w1t, const float* w1, const float* b1, int hidden, const float* w2, float* tok, void* stream) {
+  const bool mfma = w1 && stride_c == 1 && hidden == 64 && C % 64 == 0 && stride_b % 4 == 0 && stride_l % 4 == 0 &&
+                    (((size_t)feat | (size_t)w1) & 15) == 0;
+  KVQ_REQUIRE(mfma || w1t, KVQ_ERR_NULL, "%s: this shape takes the VALU kernel, which reads w1t", who);
+  if (mfma) {
+    hipLaunchKernelGGL(vqa_head_mfma_kernel, dim3((unsigned)(((long)B * L + 15) / 16)), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
+                       (long)stride_b, (long)stride_l, w1, b1, w2, tok);
+    KVQ_CHECK_LAUNCH("vqa_head_mfma_kernel");
+  } else {
+    const int grid = (int)(((long)B * L + HEAD_TOK - 1) / HEAD_TOK);
+    hipLaunchKernelGGL(vqa_head_token_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
+                       (long)stride_b, (long)stride_l, (long)stride_c, w1t, b1, hidden, w2, tok);
+    KVQ_CHECK_LAUNCH("vqa_head_token_kernel");
+  }
+  return KVQ_OK;
+}
+}  // namespace kvq
+
 extern "C" int kvq_vqa_head(const float* feat, int B, int L, int C, int64_t stride_b, int64_t stride_l,
                             int64_t stride_c, const float* w1t, const float* w1, const float* b1, int hidden, const float* w2,
                             const float* b2, float* scratch, float* score, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(feat && (w1t || w1) && b1 && w2 && scratch && score, KVQ_ERR_NULL, "kvq_vqa_head: NULL pointer");
   KVQ_REQUIRE(B > 0 && L > 0 && C > 0 && hidden > 0, KVQ_ERR_SHAPE, "kvq_vqa_head: bad shape");
-  const bool mfma = w1 && stride_c == 1 && hidden == 64 && C % 64 == 0 && stride_b % 4 == 0 && stride_l % 4 == 0 &&
-                    (((size_t)feat | (size_t)w1) & 15) == 0;
-  KVQ_REQUIRE(mfma || w1t, KVQ_ERR_NULL, "kvq_vqa_head: this shape takes the VALU kernel, which reads w1t");
-  if (mfma) {
-    hipLaunchKernelGGL(vqa_head_mfma_kernel, dim3((unsigned)(((long)B * L + 15) / 16)), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
-                       (long)stride_b, (long)stride_l, w1, b1, w2, scratch);
-    KVQ_CHECK_LAUNCH("vqa_head_mfma_kernel");
-  } else {
-    const int grid = (int)(((long)B * L + HEAD_TOK - 1) / HEAD_TOK);
-    hipLaunchKernelGGL(vqa_head_token_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
-                       (long)stride_b, (long)stride_l, (long)stride_c, w1t, b1, hidden, w2, scratch);
-    KVQ_CHECK_LAUNCH("vqa_head_token_kernel");
-  }
+  const int rc = vqa_head_tokens("kvq_vqa_head", feat, B, L, C, stride_b, stride_l, stride_c, w1t, w1, b1, hidden, w2, scratch, stream);
+  if (rc != KVQ_OK) return rc;
   hipLaunchKernelGGL(mean_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scratch, L, b2, score);
   KVQ_CHECK_LAUNCH("mean_rows_kernel");
+  return KVQ_OK;
+}
+
+extern "C" int kvq_vqa_head_map(const float* feat, int B, int L, int C, int64_t stride_b, int64_t stride_l, int64_t stride_c,
+                                const float* w1t, const float* w1, const float* b1, int hidden, const float* w2, const float* b2,
+                                int D, float* tok_map, float* depth_score, float* score, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(feat && (w1t || w1) && b1 && w2 && tok_map && score, KVQ_ERR_NULL, "kvq_vqa_head_map: NULL pointer");
+  KVQ_REQUIRE(B > 0 && L > 0 && C > 0 && hidden > 0, KVQ_ERR_SHAPE, "kvq_vqa_head_map: bad shape");
+  KVQ_REQUIRE(D > 0 && L % D == 0, KVQ_ERR_SHAPE, "kvq_vqa_head_map: %d tokens do not split into %d depth slices", L, D);
+  const int rc = vqa_head_tokens("kvq_vqa_head_map", feat, B, L, C, stride_b, stride_l, stride_c, w1t, w1, b1, hidden, w2, tok_map, stream);
+  if (rc != KVQ_OK) return rc;
+  hipLaunchKernelGGL(mean_rows_map_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, tok_map, L, D, b2, depth_score, score);
+  KVQ_CHECK_LAUNCH("mean_rows_map_kernel");
   return KVQ_OK;
 }
 

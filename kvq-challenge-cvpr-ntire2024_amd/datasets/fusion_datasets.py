@@ -75,8 +75,10 @@ def get_spatial_fragments(video, fragments_h=7, fragments_w=7, fsize_h=32, fsize
     hoff = (rnd_h.cpu().long() + torch.tensor(_grid(H, fragments_h, fsize_h)).view(-1, 1, 1)).int()
     woff = (rnd_w.cpu().long() + torch.tensor(_grid(W, fragments_w, fsize_w)).view(1, -1, 1)).int()
     if lazy:
-        return kernels.FragmentSource([video.contiguous()], [hoff.to(video.device)], [woff.to(video.device)], fragments_h,
-                                      fragments_w, fsize_h, fsize_w, aligned, mean=mean, std=std)
+        src = kernels.FragmentSource([video.contiguous()], [hoff.to(video.device)], [woff.to(video.device)], fragments_h,
+                                     fragments_w, fsize_h, fsize_w, aligned, mean=mean, std=std)
+        src.upsampled = ratio < 1
+        return src
     return kernels.fragment_gather(video.contiguous(), hoff.to(video.device), woff.to(video.device), fragments_h,
                                    fragments_w, fsize_h, fsize_w, aligned, mean=mean, std=std)
 

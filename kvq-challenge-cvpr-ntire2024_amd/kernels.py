@@ -187,10 +187,12 @@ def patch_im2col(x: torch.Tensor, patch: Sequence[int], out_dtype=torch.float16)
     return out
 
 
-def vqa_head(feat: torch.Tensor, w1, b1, w2, b2, w1t=None):
+def vqa_head(feat: torch.Tensor, w1, b1, w2, b2, w1t=None, return_map=False):
     """feat fp32 (B,C,D,H,W) with ANY strides over a dense token grid -> score fp32 [B,1].
     ``w1`` [hidden,C] (what the fp32-MFMA kernel reads: hidden == 64, channels-last features) and / or ``w1t`` [C,hidden]
-    (the VALU kernel's layout; made here from ``w1`` when missing)."""
+    (the VALU kernel's layout; made here from ``w1`` when missing).
+    ``return_map``: ``(score, tok_map (B,D,H,W), depth_score (B,D))`` — the per-token scores (``b2`` included: their mean is the
+    score) and their mean per depth slice (``kvq_vqa_head_map``); the score has the same bits either way."""
     _need_gpu(feat, w1, b1, w2, b2, w1t)
     assert feat.dtype == torch.float32 and feat.dim() == 5
     B, Cc, D, H, W = feat.shape
@@ -206,6 +208,11 @@ def vqa_head(feat: torch.Tensor, w1, b1, w2, b2, w1t=None):
     hidden = w1t.shape[1]
     scratch = torch.empty(B * L, dtype=torch.float32, device=feat.device)
     score = torch.empty(B, dtype=torch.float32, device=feat.device)
+    if return_map:
+        depth = torch.empty(B, D, dtype=torch.float32, device=feat.device)
+        check(lib().kvq_vqa_head_map(ptr(feat), B, L, Cc, sb, sw, sc, ptr(w1t), ptr(w1), ptr(b1), hidden, ptr(w2), ptr(b2), D,
+                                     ptr(scratch), ptr(depth), ptr(score), current_stream()), "kvq_vqa_head_map")
+        return score.reshape(B, 1), scratch.reshape(B, D, H, W), depth
     check(lib().kvq_vqa_head(ptr(feat), B, L, Cc, sb, sw, sc, ptr(w1t), ptr(w1), ptr(b1), hidden, ptr(w2), ptr(b2),
                              ptr(scratch), ptr(score), current_stream()), "kvq_vqa_head")
     return score.reshape(B, 1)
@@ -295,6 +302,9 @@ class FragmentSource:
         self.mean, self.std = mean, std
         self.device, self.is_cuda, self.dtype = v0.device, True, torch.float32
         self.shape = (len(videos), Cc, T, fragments_h * fsize_h, fragments_w * fsize_w)
+        # True: the frames are the sampler's bilinear upsample of a source smaller than the canvas, read at the SMALL source's
+        # offsets (fusion_datasets.py:43-50) — the draws no longer name pixels of the video itself (quality_paint's caller asks)
+        self.upsampled = False
         self._c = None
 
     @staticmethod
@@ -302,8 +312,10 @@ class FragmentSource:
         """the batch of several sources (same geometry / normalisation), in order"""
         s0 = sources[0]
         assert all(s.geometry == s0.geometry and s.mean == s0.mean and s.std == s0.std for s in sources)
-        return FragmentSource([v for s in sources for v in s.videos], [h for s in sources for h in s.hoffs],
-                              [w for s in sources for w in s.woffs], *s0.geometry, mean=s0.mean, std=s0.std)
+        out = FragmentSource([v for s in sources for v in s.videos], [h for s in sources for h in s.hoffs],
+                             [w for s in sources for w in s.woffs], *s0.geometry, mean=s0.mean, std=s0.std)
+        out.upsampled = any(s.upsampled for s in sources)
+        return out
 
     def split_clips(self, num_clips):
         """every T-frame entry as ``num_clips`` clips of T/num_clips consecutive frames — the harness's clip reshape
@@ -320,7 +332,9 @@ class FragmentSource:
                 vs.append(v[:, k * t:(k + 1) * t])
                 hs.append(h[:, :, k * nt:(k + 1) * nt])
                 ws.append(w[:, :, k * nt:(k + 1) * nt])
-        return FragmentSource(vs, hs, ws, *self.geometry, mean=self.mean, std=self.std)
+        out = FragmentSource(vs, hs, ws, *self.geometry, mean=self.mean, std=self.std)
+        out.upsampled = self.upsampled
+        return out
 
     def record_stream(self, stream):
         for t in self.videos + self.hoffs + self.woffs:
@@ -387,6 +401,7 @@ class FragmentSlot(FragmentSource):
         self.geometry, self.mean, self.std = source.geometry, source.mean, source.std
         self.device, self.is_cuda, self.dtype, self.shape = source.device, True, source.dtype, source.shape
         self._frame_shape, self._frame_stride = tuple(source.videos[0].shape), source.videos[0].stride(0)
+        self.upsampled = source.upsampled
         self.table = torch.zeros(3 * _abi.FRAG_MAX_CLIPS, dtype=torch.int64, device=self.device)
         self._c = None
         self.load(source)
@@ -395,7 +410,7 @@ class FragmentSlot(FragmentSource):
         """point the slot at ``source`` (same geometry, frame shape and normalisation), in stream order"""
         if not (source.geometry == self.geometry and source.shape == self.shape and source.mean == self.mean and source.std == self.std
                 and tuple(source.videos[0].shape) == self._frame_shape and source.videos[0].stride(0) == self._frame_stride
-                and source.videos[0].dtype == torch.uint8):
+                and source.videos[0].dtype == torch.uint8 and source.upsampled == self.upsampled):
             # a real exception (not an assert: python -O must not replay a graph recorded with other constants)
             raise ValueError("FragmentSlot.load: a slot serves one sampler geometry, frame shape / stride, uint8 frames and one "
                              f"normalisation; got geometry {source.geometry} frames {tuple(source.videos[0].shape)} {source.videos[0].dtype}")
@@ -443,6 +458,64 @@ class FragmentSlot(FragmentSource):
     def split_clips(self, num_clips):
         assert num_clips == 1, "split the source, then load it"
         return self
+
+
+PAINT_CELLS = (1, 2, 4, 8, 16, 32)
+
+
+def quality_paint_supported(source, token_grid, cell=8) -> bool:
+    """``kvq_quality_paint_supported`` for a ``FragmentSource`` / ``FragmentSlot`` and a token grid (D, Hf, Wf): host only"""
+    f = source.c_struct(any_dtype=True)
+    if f is None:
+        return False
+    D, Hf, Wf = (int(v) for v in token_grid)
+    return bool(lib().kvq_quality_paint_supported(C.byref(f), source.shape[2], D, Hf, Wf, int(cell)))
+
+
+def quality_paint(source, tok_map: torch.Tensor, cell=8, overlay_depths=(), value_range=None, alpha=128, dim=96):
+    """The token map of a forward that read ``source`` (a ``FragmentSource`` or a ``FragmentSlot``), painted onto the geometry of the
+    source frames (``kvq_quality_paint``): ``tok_map`` fp32 (n_clips, D, Hf, Wf) -> ``(heat, cover)`` fp32
+    (n_clips, D, ceil(Hs/cell), ceil(Ws/cell)), and with ``overlay_depths`` also ``overlay`` uint8 (n_clips, n_ov, 3, Hs, Ws): the
+    frames 2 * depth of each clip blended with the red-to-green colour of the scores over ``value_range`` = (lo, hi) — floats, a
+    device float[2], or None = the map's own minimum and maximum, taken on the device without a host read.  Geometries the paint
+    does not cover raise ``KvqError``.  Through a slot the launch reads the pointer table: it can be recorded into a graph."""
+    _need_gpu(tok_map)
+    assert tok_map.dtype == torch.float32 and tok_map.dim() == 4
+    tok_map = tok_map.contiguous()
+    n, D, Hf, Wf = tok_map.shape
+    f = source.c_struct(any_dtype=True)
+    if f is None or n != source.shape[0]:
+        raise _abi.KvqError(f"quality_paint: {n} token maps for a source of {source.shape[0]} clips (at most {_abi.FRAG_MAX_CLIPS})")
+    Hs, Ws = f.Hs, f.Ws
+    if cell not in PAINT_CELLS:
+        raise _abi.KvqError(f"quality_paint: cell {cell} is not one of {PAINT_CELLS}")
+    Ho, Wo = -(-Hs // cell), -(-Ws // cell)
+    dev = tok_map.device
+    heat = torch.empty(n, D, Ho, Wo, dtype=torch.float32, device=dev)
+    cover = torch.empty(n, D, Ho, Wo, dtype=torch.float32, device=dev)
+    a = _abi.KvqQualityPaintArgs()
+    a.src = C.pointer(f)
+    a.T, a.D, a.Hf, a.Wf, a.cell = source.shape[2], D, Hf, Wf, cell
+    a.tok_map, a.heat, a.cover = ptr(tok_map), ptr(heat), ptr(cover)
+    overlay = rng = None
+    depths = [int(d) for d in overlay_depths]
+    if depths:
+        if len(depths) > 16:
+            raise _abi.KvqError("quality_paint: at most 16 overlay slices per call")
+        if value_range is None:
+            lo, hi = torch.aminmax(tok_map)
+            rng = torch.stack((lo, hi))
+        elif torch.is_tensor(value_range):
+            rng = value_range.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            rng = torch.tensor([float(value_range[0]), float(value_range[1])], dtype=torch.float32).to(dev, non_blocking=True)
+        assert rng.numel() == 2
+        overlay = torch.empty(n, len(depths), 3, Hs, Ws, dtype=torch.uint8, device=dev)
+        a.overlay, a.range, a.n_ov, a.alpha, a.dim = ptr(overlay), ptr(rng), len(depths), int(alpha), int(dim)
+        for i, d in enumerate(depths):
+            a.ov_depth[i] = d
+    check(lib().kvq_quality_paint(C.byref(a), stream_of(tok_map)), "kvq_quality_paint")
+    return (heat, cover, overlay) if depths else (heat, cover)
 
 
 # ------------------------------------------------------------------------------------------------

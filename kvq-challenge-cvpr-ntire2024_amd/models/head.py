@@ -34,13 +34,18 @@ class VQAHead(nn.Module):
                                  f32(ps[3]).contiguous(), w1))
         return self._cache[1]
 
-    def forward(self, x, rois=None):
-        """x (B, C, D, H, W) fp32 (any strides) -> (B, num_class)."""
+    def forward(self, x, rois=None, return_map=False):
+        """x (B, C, D, H, W) fp32 (any strides) -> (B, num_class).  ``return_map``: ``(score, token_map (B,D,H,W), timeline (B,D))``
+        — fc_last's output per token (head.py:65, its mean is the score) and its mean per depth slice."""
         w1t, b1, w2, b2, w1 = self._prepared(x.device)
         if self.num_class != 1 or self.pre_pool:      # head.py:61-62, :66-67 — no reference config takes these branches
+            if return_map:
+                raise NotImplementedError("VQAHead(return_map=True): " + (
+                    "pre_pool averages the token grid in front of the head, so there is no per-token score" if self.pre_pool
+                    else "with num_class > 1 a token has a class distribution, not one score"))
             return kernels.vqa_head_classes(x.to(torch.float32), w1, b1, w2.reshape(self.num_class, -1), b2,
                                             pre_pool=self.pre_pool)
-        return kernels.vqa_head(x.to(torch.float32), w1, b1, w2, b2, w1t=w1t)
+        return kernels.vqa_head(x.to(torch.float32), w1, b1, w2, b2, w1t=w1t, return_map=return_map)
 
 
 class simpleVQAHead(nn.Module):  # noqa: N801  (reference spelling)

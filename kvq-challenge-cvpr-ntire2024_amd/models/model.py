@@ -55,20 +55,30 @@ class VQA_Network(nn.Module):  # noqa: N801  (reference spelling)
             setattr(self, key + "_head", head)
 
     def forward(self, inputs, targets=None, inference=True, return_pooled_feats=False, reduce_scores=False,
-                pooled=False, clip_return=False, **kwargs):
-        scores, feats, dis_contra_loss, with_loss = [], {}, None, False
+                pooled=False, clip_return=False, return_maps=False, **kwargs):
+        """``return_maps``: returns ``(what it returns otherwise, maps)``; ``maps[key] = {"token_map" (B,D,H,W), "timeline" (B,D)}``
+        for every key whose head is a ``VQAHead`` — the head's score per feature token and its mean per depth slice."""
+        scores, feats, dis_contra_loss, with_loss, maps = [], {}, None, False, {}
         for key in self.key_names:
             feat = getattr(self, key + "_backbone")(inputs, multi=self.multi, layer=self.layer, **kwargs)
             if key == "KSVQE":                                   # (features, distortion contrastive loss) (model.py:93-96)
                 feat, dis_contra_loss = feat                     # loss is None when the backbone's aux_loss is off
                 with_loss = True
-            scores += [getattr(self, key + "_head")(feat)]
+            head = getattr(self, key + "_head")
+            if return_maps and isinstance(head, VQAHead):
+                score, token_map, timeline = head(feat, return_map=True)
+                maps[key] = {"token_map": token_map, "timeline": timeline}
+                scores += [score]
+            else:
+                scores += [head(feat)]
             if return_pooled_feats:
                 feats[key] = feat
         if reduce_scores:
             scores = reduce(lambda a, b: a + b, scores) if len(scores) > 1 else scores[0]
         if return_pooled_feats:
-            return (scores, feats, dis_contra_loss) if with_loss else (scores, feats)
-        if with_loss:
-            return scores, dis_contra_loss
-        return scores
+            out = (scores, feats, dis_contra_loss) if with_loss else (scores, feats)
+        elif with_loss:
+            out = (scores, dis_contra_loss)
+        else:
+            out = scores
+        return (out, maps) if return_maps else out

@@ -23,6 +23,49 @@ from . import kernels
 from .models.model import VQA_Network
 
 
+class _MapWriter:
+    """Per lane, ``depth`` sets of pinned host buffers, each behind an event: a video's results go device -> host on the lane's
+    stream with no synchronisation; the host waits only on the event of the set it is about to reuse, and writes that set's file then
+    (so files appear as the run proceeds).  ``flush`` writes what is still in flight."""
+
+    def __init__(self, trainer, qm, n_lanes, depth=2):
+        self.trainer, self.qm = trainer, qm
+        self.sets = [[{"event": torch.cuda.Event(), "bufs": {}, "pending": None} for _ in range(depth)] for _ in range(n_lanes)]
+        self.turn = [0] * n_lanes
+        self.written = 0
+
+    def _drain(self, st):
+        if st["pending"] is None:
+            return
+        st["event"].synchronize()
+        name, frame_item, keys = st["pending"]
+        host = {k: st["bufs"][k] for k in keys}
+        host["score"] = float(host.pop("score_"))
+        self.trainer._maps_write(self.qm, name, host, frame_item)
+        self.written += 1
+        st["pending"] = None
+
+    def put(self, lane, stream, name, out, score, item):
+        """enqueue the copies of ``out`` (dict of device tensors) and ``score`` (0-d device tensor) on ``stream``"""
+        st = self.sets[lane][self.turn[lane]]
+        self.turn[lane] = (self.turn[lane] + 1) % len(self.sets[lane])
+        self._drain(st)
+        todo = {k: v for k, v in out.items() if k != "pred"}
+        todo["score_"] = score
+        for k, v in todo.items():
+            b = st["bufs"].get(k)
+            if b is None or b.shape != v.shape or b.dtype != v.dtype:
+                b = st["bufs"][k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+            b.copy_(v, non_blocking=True)
+        st["event"].record(stream)
+        st["pending"] = (name, {"frame_inds": item.get("frame_inds")} if isinstance(item, dict) else None, list(todo))
+
+    def flush(self):
+        for lane in self.sets:
+            for st in lane:
+                self._drain(st)
+
+
 class Trainer:
     def __init__(self, args, config):
         self.args, self.config = args, config
@@ -100,15 +143,113 @@ class Trainer:
         return inputs
 
     def _run_model(self, inputs):
-        """model forward (trainer.py:320-327) -> device tensor of clip scores."""
+        """model forward (trainer.py:320-327) -> device tensor of clip scores; with the yml key ``quality_maps`` a dict of device
+        tensors instead: ``pred`` and, per model key, its quality maps (``_run_model_maps``)."""
+        qm = self._quality_maps()
         with torch.no_grad():
+            if qm is not None:
+                return self._run_model_maps(inputs, qm)
             if self.config["model"]["type"] == "KSVQE":
                 pred, _ = self.model(inputs=inputs, reduce_scores=True)       # (scores, distortion contrastive loss)
                 return pred
             return self.model(inputs=inputs, reduce_scores=True)
 
+    # ---- quality maps (yml `quality_maps: {dir, cell, overlay_frames}`) -----------------------------------------------------
+    def _quality_maps(self):
+        """the parsed yml key, or None (absent / empty: nothing changes)"""
+        qm = self.config.get("quality_maps")
+        if not qm:
+            return None
+        if not isinstance(qm, dict) or not qm.get("dir"):
+            raise ValueError("quality_maps: expected {dir: <path>, cell: 8, overlay_frames: 0}")
+        unknown = set(qm) - {"dir", "cell", "overlay_frames"}
+        if unknown:
+            raise ValueError(f"quality_maps: unknown key(s) {sorted(unknown)}")
+        cell, nov = int(qm.get("cell", 8)), int(qm.get("overlay_frames", 0))
+        if cell not in kernels.PAINT_CELLS:
+            raise ValueError(f"quality_maps.cell must be one of {kernels.PAINT_CELLS}, got {cell}")
+        if not 0 <= nov <= 16:
+            raise ValueError(f"quality_maps.overlay_frames must be 0..16, got {nov}")
+        return {"dir": str(qm["dir"]), "cell": cell, "overlay_frames": nov}
+
+    @staticmethod
+    def overlay_depths(D, n):
+        """``n`` evenly spaced depth slices of ``D`` (the centres of n equal parts)"""
+        n = min(int(n), int(D))
+        return [(2 * k + 1) * D // (2 * n) for k in range(n)]
+
+    def _run_model_maps(self, inputs, qm):
+        """the forward with the heads' maps kept, and the paint onto the source frames where the trunk read them through the sampler.
+        Returns a flat dict of device tensors — what a recorded forward keeps as its static outputs.  The paint reads the batch
+        through the same object the trunk did: under graph replay that is the lane's ``FragmentSlot``, so the paint launch is part
+        of the recording and reads each video's frames and draws through the slot's pointer table."""
+        out, maps = self.model(inputs=inputs, reduce_scores=True, return_maps=True)
+        res = {"pred": out[0] if isinstance(out, tuple) else out}
+        src = None if self.config["model"]["type"] == "KSVQE" else inputs.get("technical")
+        for key, m in maps.items():
+            tok = m["token_map"]
+            res[f"{key}/token_map"], res[f"{key}/timeline"] = tok, m["timeline"]
+            if not (isinstance(src, kernels.FragmentSource) and not src.upsampled and src.shape[0] == tok.shape[0]
+                    and kernels.quality_paint_supported(src, tok.shape[1:], qm["cell"])):
+                continue
+            painted = kernels.quality_paint(src, tok, cell=qm["cell"], overlay_depths=self.overlay_depths(tok.shape[1], qm["overlay_frames"]))
+            for name, t in zip(("heat", "cover", "overlay"), painted):
+                res[f"{key}/{name}"] = t
+        return res
+
+    @staticmethod
+    def _pred(out):
+        return out["pred"] if isinstance(out, dict) else out
+
+    def _maps_note(self, out, item):
+        """one stderr line per reason (not per video) when a sample gets no heat / cover"""
+        if self.config["model"]["type"] == "KSVQE" or any(k.endswith("/heat") for k in out):
+            return
+        x = item.get("technical") if isinstance(item, dict) else None
+        if not isinstance(x, kernels.FragmentSource):
+            why = "the technical view is not sampled lazily (lazy: false)"
+        elif x.upsampled:
+            why = "the source is smaller than the fragment canvas (upsample fallback)"
+        else:
+            why = "the paint does not cover this sampler geometry"
+        seen = self.__dict__.setdefault("_maps_notes", set())
+        if why not in seen:
+            seen.add(why)
+            print(f"quality maps: token_map, timeline and frame_inds only — {why}", file=sys.stderr)
+
+    @staticmethod
+    def _maps_frame_inds(item, n_clips, D):
+        """(n_clips, D, 2): the source frame numbers of each token's frame pair, or None when the item's list does not fit"""
+        fi = item.get("frame_inds") if isinstance(item, dict) else None
+        if isinstance(fi, dict):
+            fi = fi.get("technical", fi.get("fragment", next(iter(fi.values()), None)))
+        if fi is None:
+            return None
+        fi = np.asarray(fi).reshape(-1)
+        return fi.reshape(n_clips, D, 2).astype(np.int64) if fi.size == n_clips * D * 2 else None
+
+    def _maps_write(self, qm, name, host, frame_item):
+        """<dir>/<video_name>.npz from the host copies of one video's results"""
+        arrays = {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in host.items() if "/" in k}
+        keys = sorted({k.split("/")[0] for k in arrays})
+        score = np.float32(host["score"]) if "score" in host else host["pred"].float().mean().numpy()
+        for key in keys:
+            n_clips, D = arrays[f"{key}/token_map"].shape[:2]
+            fi = self._maps_frame_inds(frame_item, n_clips, D)
+            if fi is not None:
+                arrays[f"{key}/frame_inds"] = fi
+            arrays[f"{key}/score"] = np.asarray(score, np.float32)
+        if len(keys) == 1:                       # one model key: no prefix
+            arrays = {k.split("/", 1)[1]: v for k, v in arrays.items()}
+        os.makedirs(qm["dir"], exist_ok=True)
+        path = os.path.join(qm["dir"], os.path.basename(str(name)) + ".npz")
+        tmp = path + ".tmp.npz"
+        np.savez(tmp, **arrays)
+        os.replace(tmp, path)
+        return path
+
     def _forward_video(self, data):
-        return self._run_model(self._model_inputs(data))
+        return self._pred(self._run_model(self._model_inputs(data)))
 
     def _score_all(self):
         bb = getattr(self.model, "KSVQE_backbone", None)
@@ -159,6 +300,8 @@ class Trainer:
         # the flagged videos are scored again below with fp32 streams
         swins = self._swin_trunks() if self._range_guard() else []
         flags = torch.zeros(len(mine), dtype=torch.int32, device=self.device) if swins else None
+        qm = self._quality_maps()
+        writer = _MapWriter(self, qm, len(lanes)) if qm is not None else None
         for st in lanes:
             for m in swins:
                 m.clear_range_flags(st)
@@ -181,8 +324,13 @@ class Trainer:
                     else:
                         item = self.val_dataset[i]
                     inputs = self._model_inputs(item)
-                    pred = graphs.run(lane, inputs) if graphs is not None else self._run_model(inputs)
-                    local[j] = pred.float().mean()                # pred.mean(0) over clips (trainer.py:282)
+                    out = graphs.run(lane, inputs) if graphs is not None else self._run_model(inputs)
+                    local[j] = self._pred(out).float().mean()     # pred.mean(0) over clips (trainer.py:282)
+                    if writer is not None:
+                        # device -> pinned host on this lane's stream, behind the forward (a replay's static outputs are read
+                        # before the lane's next replay rewrites them: stream order); no synchronisation here
+                        self._maps_note(out, item)
+                        writer.put(lane, lanes[lane], self._name(i), out, local[j], item)
                     if swins:
                         self._take_range_flags(swins, lanes[lane], flags, j)
                 if j == 0 and graphs is None and nstream > 1:
@@ -192,6 +340,8 @@ class Trainer:
         finally:
             if feed is not None:
                 feed.close()
+        if writer is not None:
+            writer.flush()
         for st in lanes:
             if st != main:
                 main.wait_stream(st)
@@ -237,8 +387,15 @@ class Trainer:
         try:
             for m in swins:
                 m.residual16 = False
+            qm = self._quality_maps()
             for j in redo:
-                local[j] = self._run_model(self._model_inputs(self.val_dataset[mine[j]])).float().mean()
+                item = self.val_dataset[mine[j]]
+                out = self._run_model(self._model_inputs(item))
+                local[j] = self._pred(out).float().mean()
+                if qm is not None:                 # the video's file is rewritten from the fp32-stream forward
+                    host = {k: v.cpu() for k, v in out.items()}
+                    host["score"] = float(local[j])
+                    self._maps_write(qm, self._name(mine[j]), host, item)
         finally:
             for m, s in zip(swins, saved):
                 m.residual16 = s
