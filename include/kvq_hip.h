@@ -544,6 +544,34 @@ typedef struct {
 int kvq_quality_paint_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell);
 int kvq_quality_paint(const KvqQualityPaintArgs* host_args, void* stream);
 
+/* The same paint for a trunk whose input was one WINDOW of the fragment canvas per clip frame: KSVQE's quality-aware region selection
+ * (kvq_qrs_top_region + kvq_crop_regions) cuts kh x kw anchors of `anchor` pixels out of the Fh fs_h x Fw fs_w canvas, the window of
+ * the frame's key-frame group.  With gh = Fh fs_h / anchor, gw = Fw fs_w / anchor, sh = kh anchor / Hf, sw = kw anchor / Wf and
+ *   reg = region[b][2d + phase],   ry = reg / (gw - kw + 1),   rx = reg % (gw - kw + 1)
+ * token (d, i', j') of clip b has the canvas origin (y, x) = (ry anchor + i' sh, rx anchor + j' sw) and saw the sh x sw source
+ * rectangle with origin (hoff[i][j][tt] + y % fs_h, woff[i][j][tt] + x % fs_w), i = y / fs_h, j = x / fs_w, tt = 2d / aligned.
+ * phase: a token's two frames 2d and 2d + 1 can lie in different key-frame groups (the key frames sit at odd indices) and then have
+ * different windows; the draws cannot differ (aligned is even).  Slice d is painted with the window of clip frame 2d + phase, and
+ * overlay slice n is drawn on clip frame 2 ov_depth[n] + phase.
+ * heat / cover / overlay: the arithmetic, summation order and layouts of kvq_quality_paint, bit for bit; with kh anchor and kw anchor
+ * equal to the canvas (every region 0) and phase 0 the outputs are those of kvq_quality_paint.
+ * Supported (kvq_quality_paint_regions_supported, host only, 1 / 0): the conditions of kvq_quality_paint_supported with the canvas
+ * replaced by the window (sh, sw integers, fs_h % sh == 0, fs_w % sw == 0, ...), and anchor % sh == 0, anchor % sw == 0,
+ * (Fh fs_h) % anchor == 0, (Fw fs_w) % anchor == 0, 1 <= kh <= gh, 1 <= kw <= gw; the call also wants phase in {0, 1}.  Anything else:
+ * KVQ_ERR_UNSUPPORTED; NULL pointers: KVQ_ERR_NULL.
+ * region is device data the host never reads: a value outside [0, (gh - kh + 1)(gw - kw + 1)) paints its slice as uncovered (heat 0,
+ * cover 0, every overlay pixel "uncovered"); nothing is read through it and no error is raised.
+ * The same two launches (the window origin is a compile-time variant of the same kernels); src->indirect is honoured. */
+typedef struct {
+  KvqQualityPaintArgs paint;      /* every field as for kvq_quality_paint */
+  const int32_t* region;          /* device int32 [n_clips][T]: the window index of every clip frame, as kvq_qrs_top_region returns it
+                                     (row-major over (gh - kh + 1) x (gw - kw + 1) window origins) */
+  int32_t anchor, kh, kw;         /* anchor size in canvas pixels; window size in anchors */
+  int32_t phase;                  /* 0 or 1 */
+} KvqQualityPaintRegionArgs;
+int kvq_quality_paint_regions_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell, int anchor, int kh, int kw);
+int kvq_quality_paint_regions(const KvqQualityPaintRegionArgs* host_args, void* stream);
+
 /* VQAHead.forward's other branches (models/head.py:60-68; no reference config sets them): pre_pool != 0 averages the token grid
  * first (AdaptiveAvgPool3d((1,1,1)), head.py:61-62); num_class > 1 applies nn.Softmax() — implicit dim 1 = the classes — to
  * fc_last's outputs per token (head.py:66-67) before the mean over the tokens (head.py:68).

@@ -127,6 +127,11 @@ class KvqQualityPaintArgs(C.Structure):
                 ("ov_depth", C.c_int32 * 16), ("n_ov", C.c_int32), ("range", p_void), ("alpha", C.c_int32), ("dim", C.c_int32)]
 
 
+class KvqQualityPaintRegionArgs(C.Structure):
+    _fields_ = [("paint", KvqQualityPaintArgs), ("region", p_void), ("anchor", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
+                ("phase", C.c_int32)]
+
+
 class KvqPatchEmbedArgs(C.Structure):
     _fields_ = [("x", p_void), ("B", C.c_int32), ("in_chans", C.c_int32), ("T", C.c_int32), ("H", C.c_int32),
                 ("W", C.c_int32), ("pd", C.c_int32), ("ph", C.c_int32), ("pw", C.c_int32), ("embed_dim", C.c_int32),
@@ -228,6 +233,8 @@ SYMBOLS = {
                                p_void, p_void, p_void]),
     "kvq_quality_paint_supported": (i32, [C.POINTER(KvqFragmentSource), i32, i32, i32, i32, i32]),
     "kvq_quality_paint": (i32, [C.POINTER(KvqQualityPaintArgs), p_void]),
+    "kvq_quality_paint_regions_supported": (i32, [C.POINTER(KvqFragmentSource), i32, i32, i32, i32, i32, i32, i32, i32]),
+    "kvq_quality_paint_regions": (i32, [C.POINTER(KvqQualityPaintRegionArgs), p_void]),
     "kvq_vqa_head_classes": (i32, [p_void, i32, i32, i32, i64, i64, i64, p_void, p_void, i32, p_void, p_void, i32, i32, p_void,
                                    p_void, p_void]),
     "kvq_simple_vqa_head": (i32, [p_void, i32, i32, i32, p_void, p_void, i32, p_void, p_void, p_void, p_void,

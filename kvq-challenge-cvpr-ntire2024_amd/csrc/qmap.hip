@@ -1,4 +1,4 @@
-// Quality paint (kvq_quality_paint): the head's per-token scores drawn back onto the geometry of the source frames the fragment
+// Quality paint (kvq_quality_paint, kvq_quality_paint_regions): the head's per-token scores drawn back onto the geometry of the source frames the fragment
 // sampler read them from.  Store-bound, and most of what it stores is zeros.
 //
 // A gather: every output pixel finds the token rectangles that meet it, so there are no atomics and the result is a defined bit
@@ -34,6 +34,9 @@ struct PaintParams {
   int vec;                      // heat and cover are 16-byte aligned
   int n_ov, alpha, dim;
   int ov_depth[16];
+  // kvq_quality_paint_regions only (the REGION instantiations): the token grid covers one window of the canvas per clip frame
+  const int32_t* region;        // [n_clips][T] window index, row-major over nry x nrx window origins
+  int T, anchor, nry, nrx, phase;
 };
 
 struct ActiveList {
@@ -44,8 +47,18 @@ struct ActiveList {
 };
 
 // The rectangles of slice (b, d) that meet source rows [y0, y1), compacted in increasing token order.  All QM_THREADS threads call it.
+// REGION: the token grid starts at the canvas origin of the window region[b][2d + phase] names instead of (0, 0); a value that names
+// no window leaves the slice without rectangles (the same for every thread of the workgroup: it returns in front of the barriers).
+template <bool REGION>
 __device__ __forceinline__ int build_active(const PaintParams& p, int b, int d, int y0, int y1, ActiveList& a) {
   const int ntok = p.Hf * p.Wf, tt = (2 * d) / p.aligned;
+  int oy = 0, ox = 0;
+  if (REGION) {
+    const int reg = p.region[(size_t)b * p.T + 2 * d + p.phase];
+    if (reg < 0 || reg >= p.nry * p.nrx) return 0;
+    const int ry = reg / p.nrx;
+    oy = ry * p.anchor; ox = (reg - ry * p.nrx) * p.anchor;
+  }
   const int32_t* ho = p.table ? reinterpret_cast<const int32_t*>(p.table[KVQ_FRAG_MAX_CLIPS + b]) : p.hoff[b];
   const int32_t* wo = p.table ? reinterpret_cast<const int32_t*>(p.table[2 * KVQ_FRAG_MAX_CLIPS + b]) : p.woff[b];
   const float* tok = p.tok + ((size_t)b * p.D + d) * ntok;
@@ -57,7 +70,7 @@ __device__ __forceinline__ int build_active(const PaintParams& p, int b, int d, 
     int r0 = 0, c0 = 0;
     if (k < ntok) {
       const int ip = k / p.Wf, jp = k - ip * p.Wf;
-      const int yy = ip * p.sh, xx = jp * p.sw;
+      const int yy = oy + ip * p.sh, xx = ox + jp * p.sw;
       const int i = yy / p.fsh, j = xx / p.fsw;
       const int o = (i * p.Fw + j) * p.nt + tt;
       r0 = ho[o] + (yy - i * p.fsh);
@@ -97,11 +110,12 @@ __device__ __forceinline__ void gather_block(const PaintParams& p, const ActiveL
   }
 }
 
+template <bool REGION>
 __global__ __launch_bounds__(QM_THREADS) void quality_paint_kernel(PaintParams p) {
   __shared__ ActiveList a;
   const int b = blockIdx.z, d = blockIdx.y, Y0 = blockIdx.x * p.band;
   const int rows = min(p.band, p.Ho - Y0);
-  const int n = build_active(p, b, d, Y0 * p.cell, min((Y0 + rows) * p.cell, p.Hs), a);
+  const int n = build_active<REGION>(p, b, d, Y0 * p.cell, min((Y0 + rows) * p.cell, p.Hs), a);
   const size_t plane = ((size_t)b * p.D + d) * p.Ho;
   for (int item = threadIdx.x; item < rows * p.groups; item += QM_THREADS) {
     const int row = item / p.groups, g = item - row * p.groups;
@@ -137,16 +151,17 @@ __global__ __launch_bounds__(QM_THREADS) void quality_paint_kernel(PaintParams p
 }
 
 // Overlay: one workgroup = (clip, overlay slice, band of source rows); a work item owns 4 consecutive pixels of a row in all three
-// channel planes.  Integer blend, see kvq_hip.h.
+// channel planes.  Integer blend, see kvq_hip.h.  REGION: the slice is drawn on the frame whose window it was painted with.
+template <bool REGION>
 __global__ __launch_bounds__(QM_THREADS) void quality_overlay_kernel(PaintParams p) {
   __shared__ ActiveList a;
   const int b = blockIdx.z, ov = blockIdx.y, y_lo = blockIdx.x * p.band;
   const int d = p.ov_depth[ov];
   const int rows = min(p.band, p.Hs - y_lo);
-  const int n = build_active(p, b, d, y_lo, y_lo + rows, a);
+  const int n = build_active<REGION>(p, b, d, y_lo, y_lo + rows, a);
   const float lo = p.range[0], inv = __fdiv_rn(1.f, __fsub_rn(p.range[1], lo));
   const uint8_t* vid = reinterpret_cast<const uint8_t*>(p.table ? p.table[b] : p.video[b]);
-  const size_t frame = (size_t)(2 * d) * p.Hs * p.Ws, hw = (size_t)p.Hs * p.Ws;
+  const size_t frame = (size_t)(2 * d + (REGION ? p.phase : 0)) * p.Hs * p.Ws, hw = (size_t)p.Hs * p.Ws;
   uint8_t* out = p.overlay + ((size_t)b * p.n_ov + ov) * 3 * hw;
   for (int item = threadIdx.x; item < rows * p.groups; item += QM_THREADS) {
     const int row = item / p.groups, g = item - row * p.groups;
@@ -199,70 +214,113 @@ __global__ __launch_bounds__(QM_THREADS) void quality_overlay_kernel(PaintParams
   }
 }
 
-static bool paint_geometry_ok(const KvqFragmentSource* f, int T, int D, int Hf, int Wf, int cell) {
+// wh x ww: the part of the canvas the token grid covers — all of it (kvq_quality_paint) or one window (kvq_quality_paint_regions)
+static bool paint_geometry_ok(const KvqFragmentSource* f, int T, int D, int Hf, int Wf, int cell, long wh, long ww) {
   if (!f || T <= 0 || D <= 0 || Hf <= 0 || Wf <= 0) return false;
   if (f->n_clips < 1 || f->n_clips > KVQ_FRAG_MAX_CLIPS) return false;
   if (f->Hs <= 0 || f->Ws <= 0 || f->Fh <= 0 || f->Fw <= 0 || f->fs_h <= 0 || f->fs_w <= 0 || f->aligned <= 0) return false;
   if (!(cell == 1 || cell == 2 || cell == 4 || cell == 8 || cell == 16 || cell == 32)) return false;
   if (T != 2 * D || f->aligned % 2 != 0 || T % f->aligned != 0) return false;
   if ((long)Hf * Wf > QM_MAX_TOK) return false;
-  const int ch = f->Fh * f->fs_h, cw = f->Fw * f->fs_w;
-  if (ch % Hf != 0 || cw % Wf != 0) return false;
-  const int sh = ch / Hf, sw = cw / Wf;
+  if (wh % Hf != 0 || ww % Wf != 0) return false;
+  const long sh = wh / Hf, sw = ww / Wf;
   return f->fs_h % sh == 0 && f->fs_w % sw == 0;
 }
 
-}  // namespace kvq
-
-extern "C" int kvq_quality_paint_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell) {
-  return kvq::paint_geometry_ok(src, T, D, Hf, Wf, cell) ? 1 : 0;
+static bool paint_canvas_ok(const KvqFragmentSource* f, int T, int D, int Hf, int Wf, int cell) {
+  return f && f->Fh > 0 && f->Fw > 0 && f->fs_h > 0 && f->fs_w > 0 &&
+         paint_geometry_ok(f, T, D, Hf, Wf, cell, (long)f->Fh * f->fs_h, (long)f->Fw * f->fs_w);
 }
 
-extern "C" int kvq_quality_paint(const KvqQualityPaintArgs* a, void* stream) {
-  using namespace kvq;
-  KVQ_REQUIRE(a && a->src && a->tok_map && a->heat && a->cover, KVQ_ERR_NULL, "kvq_quality_paint: NULL pointer");
+static bool paint_regions_ok(const KvqFragmentSource* f, int T, int D, int Hf, int Wf, int cell, int anchor, int kh, int kw) {
+  if (!f || anchor <= 0 || kh <= 0 || kw <= 0) return false;
+  if (!paint_geometry_ok(f, T, D, Hf, Wf, cell, (long)kh * anchor, (long)kw * anchor)) return false;
+  const long ch = (long)f->Fh * f->fs_h, cw = (long)f->Fw * f->fs_w;
+  if (ch % anchor != 0 || cw % anchor != 0 || kh > ch / anchor || kw > cw / anchor) return false;
+  const long sh = (long)kh * anchor / Hf, sw = (long)kw * anchor / Wf;
+  return anchor % sh == 0 && anchor % sw == 0;
+}
+
+// Both entry points: `rg` NULL paints the token grid over the whole canvas, else over the window of each frame.
+static int paint_run(const char* who, const KvqQualityPaintArgs* a, const KvqQualityPaintRegionArgs* rg, void* stream) {
   const KvqFragmentSource* f = a->src;
-  KVQ_REQUIRE(paint_geometry_ok(f, a->T, a->D, a->Hf, a->Wf, a->cell), KVQ_ERR_UNSUPPORTED,
-              "kvq_quality_paint: geometry outside kvq_quality_paint_supported (T %d, token grid %d x %d x %d, cell %d)", a->T, a->D,
-              a->Hf, a->Wf, a->cell);
   PaintParams p{};
   p.table = f->indirect;
   for (int b = 0; b < f->n_clips && !f->indirect; ++b) {
-    KVQ_REQUIRE(f->hoff[b] && f->woff[b], KVQ_ERR_NULL, "kvq_quality_paint: clip %d has a NULL draw pointer", b);
+    KVQ_REQUIRE(f->hoff[b] && f->woff[b], KVQ_ERR_NULL, "%s: clip %d has a NULL draw pointer", who, b);
     p.video[b] = f->video[b]; p.hoff[b] = f->hoff[b]; p.woff[b] = f->woff[b];
   }
   p.tok = a->tok_map; p.heat = a->heat; p.cover = a->cover;
   p.chan_stride = f->chan_stride ? f->chan_stride : (long)a->T * f->Hs * f->Ws;
   p.Hs = f->Hs; p.Ws = f->Ws; p.Fw = f->Fw; p.fsh = f->fs_h; p.fsw = f->fs_w; p.aligned = f->aligned; p.nt = a->T / f->aligned;
   p.D = a->D; p.Hf = a->Hf; p.Wf = a->Wf; p.sh = f->Fh * f->fs_h / a->Hf; p.sw = f->Fw * f->fs_w / a->Wf; p.cell = a->cell;
+  if (rg) {
+    p.region = rg->region; p.T = a->T; p.anchor = rg->anchor; p.phase = rg->phase;
+    p.sh = rg->kh * rg->anchor / a->Hf; p.sw = rg->kw * rg->anchor / a->Wf;
+    p.nry = f->Fh * f->fs_h / rg->anchor - rg->kh + 1; p.nrx = f->Fw * f->fs_w / rg->anchor - rg->kw + 1;
+  }
   p.Ho = ceil_div(f->Hs, a->cell); p.Wo = ceil_div(f->Ws, a->cell);
-  KVQ_REQUIRE((long)f->n_clips * a->D * p.Ho * (long)p.Wo < (1L << 40) && a->D < 65536, KVQ_ERR_SHAPE, "kvq_quality_paint: output too large");
+  KVQ_REQUIRE((long)f->n_clips * a->D * p.Ho * (long)p.Wo < (1L << 40) && a->D < 65536, KVQ_ERR_SHAPE, "%s: output too large", who);
   p.vec = (((size_t)a->heat | (size_t)a->cover) & 15) == 0;
   p.groups = ceil_div(p.Wo + 3, 4);
   p.band = QM_THREADS / p.groups > 0 ? QM_THREADS / p.groups : 1;
   if (p.band > p.Ho) p.band = p.Ho;
   if (a->overlay) {
-    KVQ_REQUIRE(a->range, KVQ_ERR_NULL, "kvq_quality_paint: an overlay needs the value range");
-    KVQ_REQUIRE(f->src_is_u8, KVQ_ERR_UNSUPPORTED, "kvq_quality_paint: the overlay is drawn on uint8 frames");
+    KVQ_REQUIRE(a->range, KVQ_ERR_NULL, "%s: an overlay needs the value range", who);
+    KVQ_REQUIRE(f->src_is_u8, KVQ_ERR_UNSUPPORTED, "%s: the overlay is drawn on uint8 frames", who);
     KVQ_REQUIRE(a->n_ov >= 1 && a->n_ov <= 16 && a->alpha >= 0 && a->alpha <= 256 && a->dim >= 0 && a->dim <= 256, KVQ_ERR_SHAPE,
-                "kvq_quality_paint: n_ov %d (1..16), alpha %d, dim %d (0..256)", a->n_ov, a->alpha, a->dim);
+                "%s: n_ov %d (1..16), alpha %d, dim %d (0..256)", who, a->n_ov, a->alpha, a->dim);
     for (int n = 0; n < a->n_ov; ++n) {
-      KVQ_REQUIRE(a->ov_depth[n] >= 0 && a->ov_depth[n] < a->D, KVQ_ERR_SHAPE, "kvq_quality_paint: overlay depth %d outside 0..%d", a->ov_depth[n], a->D - 1);
+      KVQ_REQUIRE(a->ov_depth[n] >= 0 && a->ov_depth[n] < a->D, KVQ_ERR_SHAPE, "%s: overlay depth %d outside 0..%d", who, a->ov_depth[n], a->D - 1);
       p.ov_depth[n] = a->ov_depth[n];
     }
     for (int b = 0; b < f->n_clips && !f->indirect; ++b)
-      KVQ_REQUIRE(f->video[b], KVQ_ERR_NULL, "kvq_quality_paint: clip %d has no frames", b);
+      KVQ_REQUIRE(f->video[b], KVQ_ERR_NULL, "%s: clip %d has no frames", who, b);
   }
-  hipLaunchKernelGGL(quality_paint_kernel, dim3((unsigned)ceil_div(p.Ho, p.band), (unsigned)a->D, (unsigned)f->n_clips), dim3(QM_THREADS), 0,
-                     (hipStream_t)stream, p);
+  const dim3 grid((unsigned)ceil_div(p.Ho, p.band), (unsigned)a->D, (unsigned)f->n_clips);
+  if (rg) hipLaunchKernelGGL(quality_paint_kernel<true>, grid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(quality_paint_kernel<false>, grid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
   KVQ_CHECK_LAUNCH("quality_paint_kernel");
   if (!a->overlay) return KVQ_OK;
   p.overlay = a->overlay; p.range = a->range; p.n_ov = a->n_ov; p.alpha = a->alpha; p.dim = a->dim;
   p.groups = ceil_div(p.Ws, 4);
   p.band = QM_THREADS / p.groups > 0 ? QM_THREADS / p.groups : 1;
   if (p.band > p.Hs) p.band = p.Hs;
-  hipLaunchKernelGGL(quality_overlay_kernel, dim3((unsigned)ceil_div(p.Hs, p.band), (unsigned)a->n_ov, (unsigned)f->n_clips), dim3(QM_THREADS), 0,
-                     (hipStream_t)stream, p);
+  const dim3 ogrid((unsigned)ceil_div(p.Hs, p.band), (unsigned)a->n_ov, (unsigned)f->n_clips);
+  if (rg) hipLaunchKernelGGL(quality_overlay_kernel<true>, ogrid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(quality_overlay_kernel<false>, ogrid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
   KVQ_CHECK_LAUNCH("quality_overlay_kernel");
   return KVQ_OK;
+}
+
+}  // namespace kvq
+
+extern "C" int kvq_quality_paint_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell) {
+  return kvq::paint_canvas_ok(src, T, D, Hf, Wf, cell) ? 1 : 0;
+}
+
+extern "C" int kvq_quality_paint(const KvqQualityPaintArgs* a, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(a && a->src && a->tok_map && a->heat && a->cover, KVQ_ERR_NULL, "kvq_quality_paint: NULL pointer");
+  KVQ_REQUIRE(paint_canvas_ok(a->src, a->T, a->D, a->Hf, a->Wf, a->cell), KVQ_ERR_UNSUPPORTED,
+              "kvq_quality_paint: geometry outside kvq_quality_paint_supported (T %d, token grid %d x %d x %d, cell %d)", a->T, a->D,
+              a->Hf, a->Wf, a->cell);
+  return paint_run("kvq_quality_paint", a, nullptr, stream);
+}
+
+extern "C" int kvq_quality_paint_regions_supported(const KvqFragmentSource* src, int T, int D, int Hf, int Wf, int cell, int anchor,
+                                                   int kh, int kw) {
+  return kvq::paint_regions_ok(src, T, D, Hf, Wf, cell, anchor, kh, kw) ? 1 : 0;
+}
+
+extern "C" int kvq_quality_paint_regions(const KvqQualityPaintRegionArgs* r, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(r && r->paint.src && r->paint.tok_map && r->paint.heat && r->paint.cover && r->region, KVQ_ERR_NULL,
+              "kvq_quality_paint_regions: NULL pointer");
+  const KvqQualityPaintArgs* a = &r->paint;
+  KVQ_REQUIRE(paint_regions_ok(a->src, a->T, a->D, a->Hf, a->Wf, a->cell, r->anchor, r->kh, r->kw) && (r->phase == 0 || r->phase == 1),
+              KVQ_ERR_UNSUPPORTED,
+              "kvq_quality_paint_regions: geometry outside kvq_quality_paint_regions_supported (T %d, token grid %d x %d x %d, cell %d, "
+              "windows of %d x %d anchors of %d, phase %d)", a->T, a->D, a->Hf, a->Wf, a->cell, r->kh, r->kw, r->anchor, r->phase);
+  return paint_run("kvq_quality_paint_regions", a, r, stream);
 }

@@ -472,28 +472,22 @@ def quality_paint_supported(source, token_grid, cell=8) -> bool:
     return bool(lib().kvq_quality_paint_supported(C.byref(f), source.shape[2], D, Hf, Wf, int(cell)))
 
 
-def quality_paint(source, tok_map: torch.Tensor, cell=8, overlay_depths=(), value_range=None, alpha=128, dim=96):
-    """The token map of a forward that read ``source`` (a ``FragmentSource`` or a ``FragmentSlot``), painted onto the geometry of the
-    source frames (``kvq_quality_paint``): ``tok_map`` fp32 (n_clips, D, Hf, Wf) -> ``(heat, cover)`` fp32
-    (n_clips, D, ceil(Hs/cell), ceil(Ws/cell)), and with ``overlay_depths`` also ``overlay`` uint8 (n_clips, n_ov, 3, Hs, Ws): the
-    frames 2 * depth of each clip blended with the red-to-green colour of the scores over ``value_range`` = (lo, hi) — floats, a
-    device float[2], or None = the map's own minimum and maximum, taken on the device without a host read.  Geometries the paint
-    does not cover raise ``KvqError``.  Through a slot the launch reads the pointer table: it can be recorded into a graph."""
+def _paint_args(who, a, source, tok_map, cell, overlay_depths, value_range, alpha, dim):
+    """fill a ``KvqQualityPaintArgs`` and allocate the outputs: (tensors the call must outlive, heat, cover, overlay or None)"""
     _need_gpu(tok_map)
     assert tok_map.dtype == torch.float32 and tok_map.dim() == 4
     tok_map = tok_map.contiguous()
     n, D, Hf, Wf = tok_map.shape
     f = source.c_struct(any_dtype=True)
     if f is None or n != source.shape[0]:
-        raise _abi.KvqError(f"quality_paint: {n} token maps for a source of {source.shape[0]} clips (at most {_abi.FRAG_MAX_CLIPS})")
+        raise _abi.KvqError(f"{who}: {n} token maps for a source of {source.shape[0]} clips (at most {_abi.FRAG_MAX_CLIPS})")
     Hs, Ws = f.Hs, f.Ws
     if cell not in PAINT_CELLS:
-        raise _abi.KvqError(f"quality_paint: cell {cell} is not one of {PAINT_CELLS}")
+        raise _abi.KvqError(f"{who}: cell {cell} is not one of {PAINT_CELLS}")
     Ho, Wo = -(-Hs // cell), -(-Ws // cell)
     dev = tok_map.device
     heat = torch.empty(n, D, Ho, Wo, dtype=torch.float32, device=dev)
     cover = torch.empty(n, D, Ho, Wo, dtype=torch.float32, device=dev)
-    a = _abi.KvqQualityPaintArgs()
     a.src = C.pointer(f)
     a.T, a.D, a.Hf, a.Wf, a.cell = source.shape[2], D, Hf, Wf, cell
     a.tok_map, a.heat, a.cover = ptr(tok_map), ptr(heat), ptr(cover)
@@ -501,7 +495,7 @@ def quality_paint(source, tok_map: torch.Tensor, cell=8, overlay_depths=(), valu
     depths = [int(d) for d in overlay_depths]
     if depths:
         if len(depths) > 16:
-            raise _abi.KvqError("quality_paint: at most 16 overlay slices per call")
+            raise _abi.KvqError(f"{who}: at most 16 overlay slices per call")
         if value_range is None:
             lo, hi = torch.aminmax(tok_map)
             rng = torch.stack((lo, hi))
@@ -514,8 +508,52 @@ def quality_paint(source, tok_map: torch.Tensor, cell=8, overlay_depths=(), valu
         a.overlay, a.range, a.n_ov, a.alpha, a.dim = ptr(overlay), ptr(rng), len(depths), int(alpha), int(dim)
         for i, d in enumerate(depths):
             a.ov_depth[i] = d
+    return (tok_map, rng, f), heat, cover, overlay
+
+
+def quality_paint(source, tok_map: torch.Tensor, cell=8, overlay_depths=(), value_range=None, alpha=128, dim=96):
+    """The token map of a forward that read ``source`` (a ``FragmentSource`` or a ``FragmentSlot``), painted onto the geometry of the
+    source frames (``kvq_quality_paint``): ``tok_map`` fp32 (n_clips, D, Hf, Wf) -> ``(heat, cover)`` fp32
+    (n_clips, D, ceil(Hs/cell), ceil(Ws/cell)), and with ``overlay_depths`` also ``overlay`` uint8 (n_clips, n_ov, 3, Hs, Ws): the
+    frames 2 * depth of each clip blended with the red-to-green colour of the scores over ``value_range`` = (lo, hi) — floats, a
+    device float[2], or None = the map's own minimum and maximum, taken on the device without a host read.  Geometries the paint
+    does not cover raise ``KvqError``.  Through a slot the launch reads the pointer table: it can be recorded into a graph."""
+    a = _abi.KvqQualityPaintArgs()
+    keep, heat, cover, overlay = _paint_args("quality_paint", a, source, tok_map, cell, overlay_depths, value_range, alpha, dim)
     check(lib().kvq_quality_paint(C.byref(a), stream_of(tok_map)), "kvq_quality_paint")
-    return (heat, cover, overlay) if depths else (heat, cover)
+    del keep
+    return (heat, cover) if overlay is None else (heat, cover, overlay)
+
+
+def quality_paint_regions_supported(source, token_grid, anchor, kh, kw, cell=8) -> bool:
+    """``kvq_quality_paint_regions_supported`` for a ``FragmentSource`` / ``FragmentSlot``, a token grid (D, Hf, Wf) and windows of
+    ``kh`` x ``kw`` anchors of ``anchor`` canvas pixels: host only"""
+    f = source.c_struct(any_dtype=True)
+    if f is None:
+        return False
+    D, Hf, Wf = (int(v) for v in token_grid)
+    return bool(lib().kvq_quality_paint_regions_supported(C.byref(f), source.shape[2], D, Hf, Wf, int(cell), int(anchor), int(kh), int(kw)))
+
+
+def quality_paint_regions(source, tok_map: torch.Tensor, region: torch.Tensor, anchor, kh, kw, phase=0, cell=8, overlay_depths=(),
+                          value_range=None, alpha=128, dim=96):
+    """``quality_paint`` for a trunk that saw one window of ``source``'s fragment canvas per clip frame (KSVQE's region selection,
+    ``kvq_quality_paint_regions``): ``region`` int32 (n_clips, T) on the device, the window index of every clip frame as
+    ``qrs_top_region`` returns it (``KSVQE.last_regions``), windows of ``kh`` x ``kw`` anchors of ``anchor`` canvas pixels.  Depth
+    slice d is painted with the window of clip frame 2d + ``phase`` (0 or 1: the two frames of a token can lie in different key-frame
+    groups) and overlays are drawn on that frame.  A region value that names no window leaves its slice uncovered.  Same returns
+    as ``quality_paint``."""
+    _need_gpu(region)
+    n, T = tok_map.shape[0], source.shape[2]
+    if region.dtype != torch.int32 or tuple(region.shape) != (n, T) or region.device != tok_map.device:
+        raise _abi.KvqError(f"quality_paint_regions: region must be int32 ({n}, {T}) on the map's device, got {region.dtype} {tuple(region.shape)}")
+    region = region.contiguous()
+    r = _abi.KvqQualityPaintRegionArgs()
+    keep, heat, cover, overlay = _paint_args("quality_paint_regions", r.paint, source, tok_map, cell, overlay_depths, value_range, alpha, dim)
+    r.region, r.anchor, r.kh, r.kw, r.phase = ptr(region), int(anchor), int(kh), int(kw), int(phase)
+    check(lib().kvq_quality_paint_regions(C.byref(r), stream_of(tok_map)), "kvq_quality_paint_regions")
+    del keep
+    return (heat, cover) if overlay is None else (heat, cover, overlay)
 
 
 # ------------------------------------------------------------------------------------------------

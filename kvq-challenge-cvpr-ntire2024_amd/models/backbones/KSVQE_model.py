@@ -108,6 +108,13 @@ class KSVQE(SwinTransformer3D):
         for m in mods + list(self.semantic_cross) + list(self.distortion_cross) + list(self.distortion_self):
             m.operand_dtype = self.operand_dtype
 
+    @property
+    def last_regions(self):
+        """int32 (B, T) on the device: the QRS window index of every frame of the last forward (``kvq_qrs_top_region``'s index of the
+        frame's key-frame group), or None before the first one.  Overwritten by each forward; reading it synchronises nothing.  What
+        ``kernels.quality_paint_regions`` takes to paint the head's token map back onto the source frames."""
+        return self.spa_patchnet.last_regions
+
     # ------------------------------------------------------------------ forward
     def forward(self, x, multi=False, layer=-1, adaptive_window_size=False, **kwargs):
         if adaptive_window_size:

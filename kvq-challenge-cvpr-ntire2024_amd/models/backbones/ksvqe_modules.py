@@ -176,6 +176,7 @@ class RegionNet_CLIP(nn.Module):  # noqa: N801
         self.k, self.stride, self.anchor_size, self.num_samples, self.sample_type = k, stride, anchor_size, num_samples, sample_type
         if stride != 1:
             raise NotImplementedError("window stride other than 1")
+        self.last_regions = None
 
     def forward(self, x, score, sigma, group_id, extra_score=None):
         if self.training or self.sample_type == "random" or extra_score is not None:
@@ -188,6 +189,7 @@ class RegionNet_CLIP(nn.Module):  # noqa: N801
         idx = kernels.qrs_top_region(score.to(torch.float32).reshape(b * n_key, gs, gs).contiguous(), h // self.anchor_size,
                                      w // self.anchor_size, kk, kk)
         full = extend_by_group(idx.reshape(b, n_key), group_id).reshape(b * t).contiguous()
+        self.last_regions = full.reshape(b, t)      # the window index of every frame (kept for KSVQE.last_regions; no launch, no read)
         return kernels.crop_regions(x.to(torch.float32).contiguous(), full, self.anchor_size, kk, kk)
 
 

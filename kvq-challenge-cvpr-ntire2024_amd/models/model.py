@@ -57,7 +57,8 @@ class VQA_Network(nn.Module):  # noqa: N801  (reference spelling)
     def forward(self, inputs, targets=None, inference=True, return_pooled_feats=False, reduce_scores=False,
                 pooled=False, clip_return=False, return_maps=False, **kwargs):
         """``return_maps``: returns ``(what it returns otherwise, maps)``; ``maps[key] = {"token_map" (B,D,H,W), "timeline" (B,D)}``
-        for every key whose head is a ``VQAHead`` — the head's score per feature token and its mean per depth slice."""
+        for every key whose head is a ``VQAHead`` — the head's score per feature token and its mean per depth slice — plus
+        ``"regions"`` int32 (B, T) where the backbone keeps the window it cut for every frame (``KSVQE.last_regions``)."""
         scores, feats, dis_contra_loss, with_loss, maps = [], {}, None, False, {}
         for key in self.key_names:
             feat = getattr(self, key + "_backbone")(inputs, multi=self.multi, layer=self.layer, **kwargs)
@@ -68,6 +69,9 @@ class VQA_Network(nn.Module):  # noqa: N801  (reference spelling)
             if return_maps and isinstance(head, VQAHead):
                 score, token_map, timeline = head(feat, return_map=True)
                 maps[key] = {"token_map": token_map, "timeline": timeline}
+                regions = getattr(getattr(self, key + "_backbone"), "last_regions", None)      # read AFTER the forward that set it
+                if regions is not None:
+                    maps[key]["regions"] = regions
                 scores += [score]
             else:
                 scores += [head(feat)]

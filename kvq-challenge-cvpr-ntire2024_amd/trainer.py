@@ -138,6 +138,11 @@ class Trainer:
                 v = data[k].materialise() if isinstance(data[k], kernels.FragmentSource) else data[k].to(self.device)
                 inputs[k] = v.unsqueeze(0) if v.dim() == 4 else v
             inputs["dis_label"] = torch.as_tensor(data["dis_label"]).reshape(-1).to(self.device)
+            if isinstance(data["fragment"], kernels.FragmentSource) and self._quality_maps() is not None:
+                # the model gets the sampled tensor as before; the quality paint reads the draws (and, for overlays, the uint8 frames)
+                # the sample was made from, so the source travels with the inputs — under graph replay through a FragmentSlot.
+                # KSVQE.forward reads its three keys only
+                inputs["fragment_source"] = data["fragment"]
         elif "feat" in data and torch.is_tensor(data["feat"]):
             inputs["feat"] = data["feat"].to(self.device)
         return inputs
@@ -185,14 +190,30 @@ class Trainer:
         of the recording and reads each video's frames and draws through the slot's pointer table."""
         out, maps = self.model(inputs=inputs, reduce_scores=True, return_maps=True)
         res = {"pred": out[0] if isinstance(out, tuple) else out}
-        src = None if self.config["model"]["type"] == "KSVQE" else inputs.get("technical")
+        ksvqe = self.config["model"]["type"] == "KSVQE"
+        src = inputs.get("fragment_source") if ksvqe else inputs.get("technical")
         for key, m in maps.items():
             tok = m["token_map"]
             res[f"{key}/token_map"], res[f"{key}/timeline"] = tok, m["timeline"]
-            if not (isinstance(src, kernels.FragmentSource) and not src.upsampled and src.shape[0] == tok.shape[0]
-                    and kernels.quality_paint_supported(src, tok.shape[1:], qm["cell"])):
+            if not (isinstance(src, kernels.FragmentSource) and not src.upsampled and src.shape[0] == tok.shape[0]):
                 continue
-            painted = kernels.quality_paint(src, tok, cell=qm["cell"], overlay_depths=self.overlay_depths(tok.shape[1], qm["overlay_frames"]))
+            depths = self.overlay_depths(tok.shape[1], qm["overlay_frames"])
+            if ksvqe:
+                # the trunk saw one QRS window of the canvas per frame: paint through it, slice d with the window of frame 2d (phase 0,
+                # the frame the overlay shows)
+                net, regions = getattr(self.model, key + "_backbone").spa_patchnet, m.get("regions")
+                kk = int(round(net.k ** 0.5))
+                if regions is None or not kernels.quality_paint_regions_supported(src, tok.shape[1:], net.anchor_size, kk, kk, qm["cell"]):
+                    continue
+                painted = kernels.quality_paint_regions(src, tok, regions, net.anchor_size, kk, kk, phase=0, cell=qm["cell"],
+                                                        overlay_depths=depths)
+                res[f"{key}/regions"] = regions
+                # row length of the window index, for the writer's (ry, rx) decode on the host: a constant of the sampler geometry
+                self.__dict__.setdefault("_region_row", {})[key] = src.geometry[1] * src.geometry[3] // net.anchor_size - kk + 1
+            elif kernels.quality_paint_supported(src, tok.shape[1:], qm["cell"]):
+                painted = kernels.quality_paint(src, tok, cell=qm["cell"], overlay_depths=depths)
+            else:
+                continue
             for name, t in zip(("heat", "cover", "overlay"), painted):
                 res[f"{key}/{name}"] = t
         return res
@@ -203,11 +224,15 @@ class Trainer:
 
     def _maps_note(self, out, item):
         """one stderr line per reason (not per video) when a sample gets no heat / cover"""
-        if self.config["model"]["type"] == "KSVQE" or any(k.endswith("/heat") for k in out):
+        if any(k.endswith("/heat") for k in out):
             return
-        x = item.get("technical") if isinstance(item, dict) else None
+        ksvqe = self.config["model"]["type"] == "KSVQE"
+        view = "fragment" if ksvqe else "technical"
+        if ksvqe and not (isinstance(item, dict) and "fragment" in item):
+            return
+        x = item.get(view) if isinstance(item, dict) else None
         if not isinstance(x, kernels.FragmentSource):
-            why = "the technical view is not sampled lazily (lazy: false)"
+            why = f"the {view} view is not sampled lazily (lazy: false)"
         elif x.upsampled:
             why = "the source is smaller than the fragment canvas (upsample fallback)"
         else:
@@ -232,6 +257,10 @@ class Trainer:
         """<dir>/<video_name>.npz from the host copies of one video's results"""
         arrays = {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in host.items() if "/" in k}
         keys = sorted({k.split("/")[0] for k in arrays})
+        for key in keys:
+            nrx = self.__dict__.get("_region_row", {}).get(key) if f"{key}/regions" in arrays else None
+            if nrx:                              # window index -> (ry, rx) in anchors, (n_clips, T, 2)
+                arrays[f"{key}/regions"] = np.stack(np.divmod(arrays[f"{key}/regions"].astype(np.int32), np.int32(nrx)), -1).astype(np.int32)
         score = np.float32(host["score"]) if "score" in host else host["pred"].float().mean().numpy()
         for key in keys:
             n_clips, D = arrays[f"{key}/token_map"].shape[:2]

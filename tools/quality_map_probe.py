@@ -6,6 +6,8 @@
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/quality_map_probe.py head    # the head with / without the map, in its own run
     python tools/quality_map_probe.py e2e         # videos/s of config/kwai_swin_grpb_qmap_test.yml with / without quality_maps,
                                                   # one process, the two configurations alternating, three runs each
+    python tools/quality_map_probe.py ksvqe       # samples/s of KSVQE on a fake decoded-frame tree: config/Kwai_KSVQE_test.yml (what the
+                                                  # parent commit runs), config/Kwai_KSVQE_qmap_test.yml without and with its key
 """
 import os
 import sys
@@ -117,5 +119,57 @@ def e2e():
           "dataset synthesis on the host included)")
 
 
+def ksvqe():
+    """KSVQE end to end on N uint8 [T,H,W,3] .npy stacks (96-frame samples, one clip per forward): the yml without the key and with
+    `lazy: false` enqueues what it enqueued before this feature; `lazy: true` alone moves the sampling into the lazy path; the key adds
+    the head's map launch, the region paint and the npz writer.  One process, the configurations alternating, three runs each."""
+    import yaml
+    from kvq_amd.trainer import Trainer
+    N, T, H, W = 8, 100, 540, 960
+    work = tempfile.mkdtemp(prefix="qmap_ksvqe_probe_")
+    base = np.random.Generator(np.random.PCG64(5)).integers(0, 256, size=(T, H, W, 3), dtype=np.uint8)
+    for i in range(N):
+        np.save(os.path.join(work, f"clip{i}.mp4.npy"), np.roll(base, i, axis=1))
+    open(os.path.join(work, "anno.txt"), "w").write("".join(f"clip{i}.mp4,1,{i % 5},3.0\n" for i in range(N)))
+    os.chdir(work)
+    sd = {"KSVQE_backbone." + k: torch.from_numpy(v) for k, v in synth.synth_ksvqe_weights(3).items()}
+    sd.update({"KSVQE_head." + k: torch.from_numpy(v) for k, v in synth.synth_vqa_head_weights(768, 64, 3, "stress").items()})
+
+    def config(name, key):
+        cfg = yaml.safe_load(open(os.path.join(ROOT, "config", name)))
+        cfg["data"]["val"]["args"].update(anno_file=os.path.join(work, "anno.txt"), data_prefix=work)
+        if key:
+            cfg["quality_maps"]["dir"] = os.path.join(work, "maps")
+        else:
+            cfg.pop("quality_maps", None)
+        return cfg
+
+    legs = (("Kwai_KSVQE_test.yml (lazy: false, no key)", config("Kwai_KSVQE_test.yml", False)),
+            ("qmap yml without the key (lazy: true)", config("Kwai_KSVQE_qmap_test.yml", False)),
+            ("qmap yml with the key (cell 8)", config("Kwai_KSVQE_qmap_test.yml", True)))
+    trainers = {}
+    for name, cfg in legs:
+        trainers[name] = Trainer(types.SimpleNamespace(gpu_id="0"), cfg)
+        trainers[name].model.load_state_dict(sd, strict=False)
+        trainers[name].inferece_test()                   # records the lanes' graphs, builds the weight images, warms the page cache
+    rates = {name: [] for name, _ in legs}
+    for _ in range(3):
+        for name, _ in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            trainers[name].inferece_test()
+            torch.cuda.synchronize()
+            rates[name].append(N / (time.perf_counter() - t0))
+    print(f"ksvqe: {N} videos of {T} x {H} x {W}, one 96-frame sample each, decode (np.load) and H2D included")
+    for name, _ in legs:
+        r = rates[name]
+        print(f"  {name:44s} {np.median(r):7.2f} samples/s (runs {', '.join(f'{v:.2f}' for v in r)}; spread "
+              f"{100 * (max(r) - min(r)) / np.median(r):.1f} %), graph_stats {getattr(trainers[name], 'graph_stats', None)}")
+    first = np.median(rates[legs[0][0]])
+    print("  ratios to the first line: " + ", ".join(f"{np.median(rates[name]) / first:.3f}" for name, _ in legs[1:]))
+    z = np.load(os.path.join(work, "maps", "clip0.mp4.npz"))
+    print("  clip0.mp4.npz: " + ", ".join(f"{k} {z[k].shape}" for k in z.files))
+
+
 if __name__ == "__main__":
-    {"paint": paint, "noise": noise, "head": head, "e2e": e2e}[sys.argv[1] if len(sys.argv) > 1 else "paint"]()
+    {"paint": paint, "noise": noise, "head": head, "e2e": e2e, "ksvqe": ksvqe}[sys.argv[1] if len(sys.argv) > 1 else "paint"]()
