@@ -13,6 +13,7 @@ import torch
 
 from . import _abi
 from ._abi import check, current_stream, dtype_code, lib, ptr, stream_of
+from ._prepared import to_operand
 
 HALF_TYPES = (torch.float16, torch.bfloat16)
 
@@ -1075,9 +1076,7 @@ def stem_mfma_pack_weight(w_kc: torch.Tensor, kernel, cin: int, out_dtype):
     w = w_kc.reshape(kd * kh, kw, cin, cout).permute(0, 3, 1, 2)                 # [slice][o][tap][c]
     img = torch.zeros(kd * kh, 16, 8, 4, dtype=torch.float32, device=w_kc.device)
     img[:, :cout, :kw, :cin] = w
-    if out_dtype == torch.float16:
-        img = img.clamp(-65504.0, 65504.0)
-    return img.reshape(kd * kh, 16, 32).to(out_dtype).contiguous()
+    return to_operand(img, out_dtype, img.device, (kd * kh, 16, 32))
 
 
 def conv_stem_mfma(x: torch.Tensor, wpack: torch.Tensor, bias8: torch.Tensor, kernel, stride, pad, relu: bool):
@@ -1116,9 +1115,7 @@ def stem64_pack_weight(w_ok: torch.Tensor, out_dtype):
     assert w_ok.shape[0] == 64 and w_ok.shape[1] >= 147
     img = torch.zeros(7, 64, 8, 4, dtype=torch.float32, device=w_ok.device)
     img[:, :, :7, :3] = w_ok[:, :147].float().reshape(64, 7, 7, 3).permute(1, 0, 2, 3)
-    if out_dtype == torch.float16:
-        img = img.clamp(-65504.0, 65504.0)
-    return img.reshape(7, 64, 32).to(out_dtype).contiguous()
+    return to_operand(img, out_dtype, img.device, (7, 64, 32))
 
 
 def conv_stem64_pool(x: torch.Tensor, t_index, wimg: torch.Tensor, bias64: torch.Tensor, relu: bool = True, out=None, out_coff: int = 0):

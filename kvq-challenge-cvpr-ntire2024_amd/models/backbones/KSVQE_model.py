@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
 from . import ksvqe_modules as KM
 from .clip_visual import build_CLIPmodel_basedadapter_cls
 from .swin_backbone import SwinTransformer3D
@@ -73,31 +73,20 @@ class KSVQE(SwinTransformer3D):
             self.semantic_cross.append(KM.crossattention1(c, heads[i]))
             self.distortion_cross.append(KM.crossattention1(c, heads[i]))
             self.distortion_self.append(KM.Attention(c, heads[i]))
-        self._acache = None
+        self._acache, self._mixc = _prepared.PreparedCache(), _prepared.PreparedCache()
 
     # ------------------------------------------------------------------ adapters: Linear -> ReLU -> Linear -> ReLU = two GEMMs
     def _adapters(self, device):
         half = _abi.torch_dtype(self.operand_dtype)
         mods = [self.dist_adapter] + list(self.semantic_adapter) + list(self.distortion_adapter)
-        sig = (self.operand_dtype,) + tuple((p.data_ptr(), p._version) for m in mods for p in m.parameters())
-        if self._acache is None or self._acache[0] != sig:
-            def f(m):
-                w = m.weight.detach().to(device, torch.float32)
-                if half == torch.float16:
-                    w = w.clamp(-65504.0, 65504.0)
-                return w.to(half).contiguous(), m.bias.detach().to(device, torch.float32).contiguous()
-            self._acache = (sig, {id(m): (f(m[0]), f(m[2])) for m in mods})
-        return self._acache[1]
+        f = lambda m: (_prepared.to_operand(m.weight, half, device), _prepared.to_f32(m.bias, device))  # noqa: E731
+        return self._acache.get((self.operand_dtype, str(device)), [p for m in mods for p in m.parameters()],
+                                lambda: {id(m): (f(m[0]), f(m[2])) for m in mods})
 
     def _mix_coeffs(self):
         """(a1, a2) of every tuned stage as host floats, re-read only when the parameters change (no device sync per forward)."""
-        sig = ((self.a1.data_ptr(), self.a1._version), (self.a2.data_ptr(), self.a2._version))
-        c = self.__dict__.get("_mixc")
-        if c is None or c[0] != sig:
-            a1, a2 = self.a1.detach().cpu().reshape(-1).tolist(), self.a2.detach().cpu().reshape(-1).tolist()
-            c = (sig, list(zip(a1, a2)))
-            self.__dict__["_mixc"] = c
-        return c[1]
+        return self._mixc.get((), (self.a1, self.a2), lambda: list(zip(self.a1.detach().cpu().reshape(-1).tolist(),
+                                                                      self.a2.detach().cpu().reshape(-1).tolist())))
 
     def _run_adapter(self, mod, rows16):
         (w0, b0), (w2, b2) = self._adapters(rows16.device)[id(mod)]
@@ -196,12 +185,7 @@ class KSVQE(SwinTransformer3D):
         pt = patch_tokens[:, ::2].reshape(-1, patch_tokens.shape[-1]).contiguous()
         pt = self._run_adapter(self.semantic_adapter[k], kernels.to_half(pt, half)).reshape(n * tt, -1, c)
         enhanced, _ = self.semantic_cross[k](frames16, pt)
-        sm = self.semantic_mod[k]
-        wsm = sm._cached(rows.device, lambda: (sm.conv_gama.weight.detach().to(rows.device, torch.float32).reshape(-1).contiguous(),
-                                               float(sm.conv_gama.bias.detach()),
-                                               sm.conv_beta.weight.detach().to(rows.device, torch.float32).reshape(-1).contiguous(),
-                                               float(sm.conv_beta.bias.detach())))
-        x_s = kernels.sem_modulate(enhanced.reshape(-1, c).contiguous(), rows, *wsm)         # (n t' hw, c)
+        x_s = kernels.sem_modulate(enhanced.reshape(-1, c).contiguous(), rows, *self.semantic_mod[k]._weights(rows.device))   # (n t' hw, c)
         # --- distortion: CONTRIQUE tokens adapted to c channels, cross-attended per frame, then self-attention over the
         # frames of every spatial position, then (mean, std)-driven channel modulation.  The chain stays in the 16-bit operand
         # type between its GEMMs (the values each next GEMM would round to anyway)

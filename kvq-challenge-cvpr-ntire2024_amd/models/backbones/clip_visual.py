@@ -15,12 +15,10 @@ KSVQE-only modules; the rest of KSVQE is not built yet (``VQA
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
 
 
 class _Block(nn.Module):
@@ -71,8 +69,8 @@ class CLIP_extractor_addadapter_cls(nn.Module):  # noqa: N801  (reference spelli
                               nn.Linear(self.embed_dim // 4, self.embed_dim), nn.ReLU(inplace=True))
                 for _ in range(11 - CLIP_location + 1)])
         self.grid_size = self.visual.grid_size
-        self.operand_dtype = _abi.dtype_code(os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
-        self._wcache = None
+        self.operand_dtype = _prepared.default_operand_dtype()
+        self._wcache = _prepared.PreparedCache()
         self._pos = {}
 
     def freeze(self):
@@ -85,22 +83,14 @@ class CLIP_extractor_addadapter_cls(nn.Module):  # noqa: N801  (reference spelli
 
     # ------------------------------------------------------------------ weights (16-bit GEMM operands, fp32 vectors)
     def _weights(self, device):
-        sig = (self.operand_dtype,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._wcache is not None and self._wcache[0] == sig:
-            return self._wcache[1]
+        return self._wcache.get((self.operand_dtype, str(device)), self.parameters(), lambda: self._build_weights(device))
+
+    def _build_weights(self, device):
         half = _abi.torch_dtype(self.operand_dtype)
-
-        def h(t):
-            t = t.detach().to(device, torch.float32)
-            if half == torch.float16:
-                t = t.clamp(-65504.0, 65504.0)
-            return t.to(half).contiguous()
-
-        def f(t):
-            return t.detach().to(device, torch.float32).contiguous()
-
+        h = lambda t, shape=None: _prepared.to_operand(t, half, device, shape)  # noqa: E731
+        f = lambda t: _prepared.to_f32(t, device)  # noqa: E731
         v = self.visual
-        w = {"conv": h(v.conv1.weight.reshape(v.conv1.weight.shape[0], -1)), "cls": f(v.class_embedding),
+        w = {"conv": h(v.conv1.weight, (v.conv1.weight.shape[0], -1)), "cls": f(v.class_embedding),
              "ln_pre": (f(v.ln_pre.weight), f(v.ln_pre.bias)), "blocks": [], "adapters": []}
         for blk in v.transformer.resblocks:
             w["blocks"].append(dict(
@@ -111,13 +101,13 @@ class CLIP_extractor_addadapter_cls(nn.Module):  # noqa: N801  (reference spelli
         if self.cls_use:
             for ad in self.adapter_layer:
                 w["adapters"].append((h(ad[0].weight), f(ad[0].bias), h(ad[2].weight), f(ad[2].bias)))
-        self._wcache, self._pos = (sig, w), {}
+        self._pos = {}
         return w
 
     def _pos_embed(self, hw, device):
         """``resize_pos_embed2d`` (CLIP_backbone.py:35-70): bicubic resize of the grid rows when the token grid differs;
         a weight-side transformation, cached per grid."""
-        key = (hw, str(device), self.visual.positional_embedding._version)
+        key = _prepared.signature((hw, str(device)), (self.visual.positional_embedding,))
         p = self._pos.get(key)
         if p is None:
             pos = self.visual.positional_embedding.detach().to(device, torch.float32)

@@ -12,29 +12,25 @@ import os
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
+from ..._prepared import to_f32
 
 
 class _HipModule(nn.Module):
     def __init__(self):
         super().__init__()
-        self.operand_dtype = _abi.dtype_code(os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
-        self._wc = None
+        self.operand_dtype = _prepared.default_operand_dtype()
+        self._wc = _prepared.PreparedCache()
 
     def _half(self):
         return _abi.torch_dtype(self.operand_dtype)
 
-    def _cached(self, device, build):
-        sig = (self.operand_dtype, str(device)) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._wc is None or self._wc[0] != sig:
-            self._wc = (sig, build())
-        return self._wc[1]
+    def _cached(self, device, build, tensors=None):
+        """``build()``'s result until the operand type, the device or one of ``tensors`` (default: every parameter) changes."""
+        return self._wc.get((self.operand_dtype, str(device)), self.parameters() if tensors is None else tensors, build)
 
     def _w16(self, t, device):
-        t = t.detach().to(device, torch.float32)
-        if self._half() == torch.float16:
-            t = t.clamp(-65504.0, 65504.0)
-        return t.to(self._half()).contiguous()
+        return _prepared.to_operand(t, self._half(), device)
 
     @staticmethod
     def _need(*ts):
@@ -57,7 +53,7 @@ class crossattention1(_HipModule):  # noqa: N801  (reference spelling)
         """``keep16``: return the 16-bit attention output as it leaves the kernel (what the next GEMM would convert to)."""
         self._need(Q, K)
         dev, h = Q.device, self._half()
-        w = self._cached(dev, lambda: [(self._w16(m.weight, dev), m.bias.detach().to(dev, torch.float32).contiguous())
+        w = self._cached(dev, lambda: [(self._w16(m.weight, dev), to_f32(m.bias, dev))
                                        for m in (self.fc_q, self.fc_k, self.fc_v)])
         B, Nq, C = Q.shape
         # operands already in the 16-bit operand type (KSVQE.forward hands the adapters' GEMM outputs and one shared copy of
@@ -88,7 +84,7 @@ class Attention(_HipModule):
         self._need(x)
         dev, h = x.device, self._half()
         w = self._cached(dev, lambda: (self._w16(self.to_qkv.weight, dev), self._w16(self.to_out[0].weight, dev),
-                                       self.to_out[0].bias.detach().to(dev, torch.float32).contiguous()))
+                                       to_f32(self.to_out[0].bias, dev)))
         B, n, C = x.shape
         x16 = x.contiguous().reshape(-1, C) if x.dtype == h else kernels.to_half(x.to(torch.float32).contiguous().reshape(-1, C), h)
         qkv = kernels.gemm(x16, w[0], None, _abi.EPI_BIAS_BF16)
@@ -105,12 +101,14 @@ class Semantic_Transformation2(_HipModule):  # noqa: N801
         self.conv_gama = nn.Conv2d(inChannels, 1, 1, padding=0, stride=1)
         self.conv_beta = nn.Conv2d(inChannels, 1, 1, padding=0, stride=1)
 
+    def _weights(self, dev):
+        """(gama weight fp32 [C], gama bias, beta weight fp32 [C], beta bias): the arguments ``kernels.sem_modulate`` takes."""
+        return self._cached(dev, lambda: (to_f32(self.conv_gama.weight, dev).reshape(-1), float(self.conv_gama.bias.detach()),
+                                          to_f32(self.conv_beta.weight, dev).reshape(-1), float(self.conv_beta.bias.detach())))
+
     def forward(self, x, input):  # noqa: A002  (reference argument name)
         self._need(x, input)
-        dev = x.device
-        w = self._cached(dev, lambda: (self.conv_gama.weight.detach().to(dev, torch.float32).reshape(-1).contiguous(),
-                                       float(self.conv_gama.bias.detach()), self.conv_beta.weight.detach().to(dev, torch.float32)
-                                       .reshape(-1).contiguous(), float(self.conv_beta.bias.detach())))
+        w = self._weights(x.device)
         N, C, hh, ww = x.shape
         rows = lambda t: t.to(torch.float32).permute(0, 2, 3, 1).reshape(N * hh * ww, C).contiguous()   # noqa: E731  (layout only)
         out = kernels.sem_modulate(rows(x), rows(input), *w)
@@ -128,8 +126,8 @@ class Dist_Transformation3(_HipModule):  # noqa: N801
     def forward(self, x, input):  # noqa: A002
         self._need(x, input)
         dev, h = x.device, self._half()
-        w = self._cached(dev, lambda: (self._w16(self.get_gamma.weight, dev), self.get_gamma.bias.detach().to(dev, torch.float32).contiguous(),
-                                       self._w16(self.get_beta.weight, dev), self.get_beta.bias.detach().to(dev, torch.float32).contiguous()))
+        w = self._cached(dev, lambda: (self._w16(self.get_gamma.weight, dev), to_f32(self.get_gamma.bias, dev),
+                                       self._w16(self.get_beta.weight, dev), to_f32(self.get_beta.bias, dev)))
         if x.dtype == h and x.dim() == 3:
             # (B, positions, C) 16-bit rows, any position order: the statistics are over all positions of a sample
             B, C = x.shape[0], x.shape[2]
@@ -224,20 +222,16 @@ class CONTRIQUE_model(_HipModule):  # noqa: N801
                                        nn.Linear(n_features, projection_dim, bias=False), nn.BatchNorm1d(projection_dim))
 
     def _fold(self, lin, bn, device):
-        scale = bn.weight.detach().to(device, torch.float32) / torch.sqrt(bn.running_var.to(device, torch.float32) + bn.eps)
-        bias = bn.bias.detach().to(device, torch.float32) - bn.running_mean.to(device, torch.float32) * scale
-        return self._w16(lin.weight.detach().to(device, torch.float32) * scale[:, None], device), bias.contiguous()
+        w, bias = _prepared.fold_bn(lin.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, device)
+        return self._w16(w, device), bias
 
     def forward(self, x):
         self._need(x)
         dev, h = x.device, self._half()
         self._net.operand_dtype = self.operand_dtype
-        sig_extra = tuple((t.data_ptr(), t._version) for t in self.projector.buffers())
-        w = self._cached(dev, lambda: (sig_extra, self._fold(self.projector[0], self.projector[1], dev),
-                                       self._fold(self.projector[3], self.projector[4], dev)))
-        if w[0] != sig_extra:                                    # running statistics changed: refold
-            self._wc = None
-            return self.forward(x)
+        pj = self.projector                                      # the running statistics are part of what the folds read
+        w = self._cached(dev, lambda: (self._fold(pj[0], pj[1], dev), self._fold(pj[3], pj[4], dev)),
+                         tensors=list(pj.parameters()) + list(pj.buffers()))
         b, c, t, hh, ww = x.shape
         a = self.anchor_size
         gh, gw = hh // a, ww // a
@@ -247,6 +241,6 @@ class CONTRIQUE_model(_HipModule):  # noqa: N801
         _, f32 = self._net.features(p)
         f = f32.reshape(-1, self.n_features)
         f16 = kernels.l2_normalize_rows(f.contiguous(), h) if self.normalize else kernels.to_half(f.contiguous(), h)
-        z = kernels.conv_gemm(f16, *w[1], True)
-        z = kernels.gemm(z, *w[2], _abi.EPI_BIAS_BF16)
+        z = kernels.conv_gemm(f16, *w[0], True)
+        z = kernels.gemm(z, *w[1], _abi.EPI_BIAS_BF16)
         return kernels.to_float(z).reshape(b, t, gh * gw, -1)

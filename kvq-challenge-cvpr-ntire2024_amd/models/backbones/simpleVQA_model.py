@@ -6,12 +6,10 @@ forward = im2col + MFMA GEMM (BatchNorm folded, ReLU / identity add in the epilo
 of libkvq_hip.so on channels-last 16-bit activations.  No PyTorch compute path."""
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
 from .swin_backbone import _Affine
 
 
@@ -54,23 +52,15 @@ class Bottleneck(nn.Module):
 def _fold(conv: _Conv, bn: _BN, half, device):
     """BatchNorm (eval) folded into the conv: w' = w*g/sqrt(var+eps), b' = beta - mean*g/sqrt(var+eps);
     weight reordered to the im2col column order (kh,kw,c), zero padded to a multiple of 32, 16-bit."""
-    w = conv.weight.detach().to(device=device, dtype=torch.float32)
-    scale = bn.weight.detach().to(device, torch.float32) / torch.sqrt(bn.running_var.to(device, torch.float32) + bn.eps)
-    bias = bn.bias.detach().to(device, torch.float32) - bn.running_mean.to(device, torch.float32) * scale
-    w = (w * scale.view(-1, 1, 1, 1)).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-    K = w.shape[1]
-    kpad = -(-K // 32) * 32
-    if kpad != K:
-        w = torch.nn.functional.pad(w, (0, kpad - K))
-    if half == torch.float16:
-        w = w.clamp(-65504.0, 65504.0)
-    return w.to(half).contiguous(), bias.contiguous()
+    w, bias = _prepared.fold_bn(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, device)
+    w = _prepared.pad_k32(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
+    return _prepared.to_operand(w, half, device), bias
 
 
 class ResNet(nn.Module):
     def __init__(self, block=Bottleneck, layers=(3, 4, 6, 3), operand_dtype=None, **kwargs):
         super().__init__()
-        self.operand_dtype = _abi.dtype_code(operand_dtype or os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
+        self.operand_dtype = _prepared.default_operand_dtype(operand_dtype)
         self.inplanes = 64
         self.conv1, self.bn1 = _Conv(3, 64, 7, 2, 3), _BN(64)
         self.layer1 = self._make_layer(64, layers[0], 1)
@@ -79,7 +69,7 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(512, layers[3], 2)
         # unused by forward but part of the reference's state_dict (simpleVQA_model.py:167)
         self.quality = nn.Sequential(_Affine((128, 4096 + 2048 + 1024 + 2048 + 256), (128,)), _Affine((1, 128), (1,)))
-        self._wcache = None
+        self._wcache = _prepared.PreparedCache()
         # features() only: carry the stream between bottlenecks in 16 bits (CONTRIQUE_model switches it on; forward() — the SimpleVQA
         # path pinned to the reference by |dscore| <= 1e-3 — always keeps the fp32 stream)
         self.residual16 = False
@@ -92,17 +82,14 @@ class ResNet(nn.Module):
 
     # ---- weights ---------------------------------------------------------------------------------
     def _weights(self, device):
-        sig = (self.operand_dtype,) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) +
-                                            list(self.buffers()))
-        if self._wcache is not None and self._wcache[0] == sig:
-            return self._wcache[1]
+        return self._wcache.get((self.operand_dtype, str(device)), list(self.parameters()) + list(self.buffers()),
+                                lambda: self._build_weights(device))
+
+    def _build_weights(self, device):
         half = _abi.torch_dtype(self.operand_dtype)
         w = {"stem": _fold(self.conv1, self.bn1, half, device)}
         # the same stem weight for the channel-padded implicit conv: (kh,kw,c<3) columns spread to (kh,kw,8), K 392 -> 416
-        ws = w["stem"][0][:, :147].reshape(64, 49, 3)
-        w8 = torch.zeros(64, 416, dtype=ws.dtype, device=device)
-        w8[:, :392].view(64, 49, 8)[:, :, :3] = ws
-        w["stem8"] = w8
+        w["stem8"] = _prepared.spread_stem8(w["stem"][0], 49, 3)
         self.__dict__["_pruned"] = {}
         for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), 1):
             for bi, blk in enumerate(layer):
@@ -112,7 +99,6 @@ class ResNet(nn.Module):
                 w[k + "3"] = _fold(blk.conv3, blk.bn3, half, device)
                 if blk.downsample is not None:
                     w[k + "d"] = _fold(blk.downsample[0], blk.downsample[1], half, device)
-        self._wcache = (sig, w)
         return w
 
     # ---- conv on channels-last 16-bit (N,H,W,C) ---------------------------------------------------
@@ -135,7 +121,7 @@ class ResNet(nn.Module):
                 live = kernels.live_taps((1, h, w_), (1, k, k), (1, stride, stride), (0, pad, pad))
                 if len(live[1]) * len(live[2]) < k * k:
                     cache = self.__dict__.setdefault("_pruned", {})
-                    ck = (wb[0].data_ptr(), wb[0]._version, h, w_, stride)
+                    ck = _prepared.signature((h, w_, stride), (wb[0],))
                     if ck not in cache:
                         cache[ck] = kernels.prune_conv_weight(wb[0], (1, k, k), c, live)
                     wk = cache[ck]
@@ -345,7 +331,7 @@ class TorchvisionResNet50(ResNet):
 
     def __init__(self, operand_dtype=None):
         nn.Module.__init__(self)
-        self.operand_dtype = _abi.dtype_code(operand_dtype or os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
+        self.operand_dtype = _prepared.default_operand_dtype(operand_dtype)
         self.inplanes = 64
         self.conv1, self.bn1 = _Conv(3, 64, 7, 2, 3), _BN(64)
         self.relu, self.maxpool = nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1)
@@ -354,7 +340,7 @@ class TorchvisionResNet50(ResNet):
         self.layer3 = self._make_layer(256, 6, 2)
         self.layer4 = self._make_layer(512, 3, 2)
         self.avgpool, self.fc = nn.AdaptiveAvgPool2d((1, 1)), nn.Linear(2048, 1000)
-        self._wcache = None
+        self._wcache = _prepared.PreparedCache()
 
     def forward(self, *a, **k):
         raise NotImplementedError("only the convolutional trunk is used (CONTRIQUE_model); call features()")

@@ -9,7 +9,6 @@ with BatchNorm folded and ReLU / identity add in the epilogue (1x1x1 stride-1 co
 residual stream between bottlenecks stays fp32; pools = ``kvq_pool_nd`` / ``kvq_mean_std_pool``."""
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 
 import weakref
@@ -17,13 +16,14 @@ import weakref
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
 
 DEPTHS = (3, 4, 6, 3)
 SLOW = dict(inner=(64, 128, 256, 512), out=(256, 512, 1024, 2048), ka=(1, 1, 3, 3))
 FAST = dict(inner=(8, 16, 32, 64), out=(32, 64, 128, 256), ka=(3, 3, 3, 3))
 SPATIAL_STRIDE = (1, 2, 2, 2)
 FAST_C = (8, 32, 64, 128)          # fast-pathway channels entering fusion 0..3
+SLOW_STEM = "feature_extraction.0.multipathway_blocks.0"      # conv_table() key of the slow pathway's stem (3 -> 64, k 1x7x7)
 
 
 def conv_table():
@@ -202,7 +202,7 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
         per video when SlowFast runs alone, but a loss when another branch (the Swin trunk of config C3) already fills the
         chip from its own stream — that caller passes False."""
         super().__init__()
-        self.operand_dtype = _abi.dtype_code(operand_dtype or os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
+        self.operand_dtype = _prepared.default_operand_dtype(operand_dtype)
         self.two_lanes = TWO_LANES if two_lanes is None else bool(two_lanes)
         # False: no launch cuts K, so a clip's features do not depend on how many clips share its forward (the feature
         # extractor writes per-clip files; the reference runs batch 1) — datasets/slowfast_clips.py::extract_video sets it
@@ -222,36 +222,31 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
             _set_nested(self, f"{base}.{nname}.running_mean", torch.zeros(c), buffer=True)
             _set_nested(self, f"{base}.{nname}.running_var", torch.ones(c), buffer=True)
             _set_nested(self, f"{base}.{nname}.num_batches_tracked", torch.tensor(0, dtype=torch.long), buffer=True)
-        self._wcache = None
+        self._wcache = _prepared.PreparedCache()
 
     # ---- weights: BatchNorm folded, (kd,kh,kw,c) column order, K padded to 32, 16-bit -----------------
     def _weights(self, device):
         sd = self.state_dict()
-        sig = (self.operand_dtype,) + tuple((t.data_ptr(), t._version) for t in sd.values())
-        if self._wcache is not None and self._wcache[0] == sig:
-            return self._wcache[1]
+        return self._wcache.get((self.operand_dtype, str(device)), sd.values(), lambda: self._build_weights(sd, device))
+
+    def _build_weights(self, sd, device):
         half = _abi.torch_dtype(self.operand_dtype)
         out = {}
         for key, (wshape, stride, pad, cname, nname) in self.table.items():
             base = key.split("#")[0]
-            w = sd[f"{base}.{cname}.weight"].to(device, torch.float32)
-            g, b = sd[f"{base}.{nname}.weight"].to(device, torch.float32), sd[f"{base}.{nname}.bias"].to(device, torch.float32)
-            mu, var = sd[f"{base}.{nname}.running_mean"].to(device, torch.float32), sd[f"{base}.{nname}.running_var"].to(device, torch.float32)
-            scale = g / torch.sqrt(var + 1e-5)
-            w = (w * scale.view(-1, 1, 1, 1, 1)).permute(0, 2, 3, 4, 1).reshape(wshape[0], -1)
+            w, bias = _prepared.fold_bn(sd[f"{base}.{cname}.weight"], *(sd[f"{base}.{nname}.{leaf}"] for leaf in
+                                        ("weight", "bias", "running_mean", "running_var")), 1e-5, device)
+            w = w.permute(0, 2, 3, 4, 1).reshape(wshape[0], -1)
             if wshape[0] in (8, 16) and w.shape[1] > 256:        # few outputs, long patch: direct fp32 stem conv (conv.hip)
                 out[key + "/direct"] = w.t().contiguous()
                 kk = tuple(wshape[2:])
                 if wshape[0] == 8 and wshape[1] <= 4 and kk[2] == 7 and stride[2] == 2 and pad[2] == 3:
                     # the same stem on the matrix cores (kvq_conv_stem_mfma): 16-bit [kd*kh][16][32] weight image
                     out[key + "/mfma"] = kernels.stem_mfma_pack_weight(out[key + "/direct"], kk, wshape[1], half)
-            kpad = -(-w.shape[1] // 32) * 32
-            if kpad != w.shape[1]:
-                w = torch.nn.functional.pad(w, (0, kpad - w.shape[1]))
-            if half == torch.float16:
-                w = w.clamp(-65504.0, 65504.0)
-            out[key] = (w.to(half).contiguous(), (b - mu * scale).contiguous(), tuple(wshape[2:]), stride, pad)
-        self._wcache = (sig, out)
+            out[key] = (_prepared.to_operand(_prepared.pad_k32(w), half, device), bias, tuple(wshape[2:]), stride, pad)
+        # the slow stem (3 -> 64, k 1x7x7) for the channel-padded implicit conv: (kh,kw,c<3) columns spread to (kh,kw,8)
+        (_, cin, _, kh, kw) = self.table[SLOW_STEM][0]
+        out[SLOW_STEM + "/stem8"] = _prepared.spread_stem8(out[SLOW_STEM][0], kh * kw, cin)
         return out
 
     def _bottleneck_pack(self, Wt, pre, projection, stride):
@@ -307,7 +302,7 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
         y = kernels.conv_gemm(a, spec[0], spec[1], True, **rkw)
         return (y.reshape(shape), None) if r16 else (y[0].reshape(shape), y[1].reshape(shape))
 
-    def _stem(self, x, spec, half, direct=None, mfma=None):
+    def _stem(self, x, spec, half, direct=None, mfma=None, stem8=None):
         B, C, T, H, W = x.shape
         wt, bias, k, stride, pad = spec
         if mfma is not None and STEM_MFMA:
@@ -316,18 +311,10 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
             y = kernels.conv_stem_mfma(x.contiguous(), mfma, bias, k, stride, pad, True)
         elif direct is not None:
             y = kernels.conv_stem_direct(x, direct, bias, k, stride, pad, True, half)
-        elif IMPLICIT_CONV and C <= 8 and k[0] == 1:
+        elif IMPLICIT_CONV and stem8 is not None:
             # slow pathway: 3 -> 64 channels, k 1x7x7: implicit GEMM over the clip packed to 8 channels (no 147-column patch matrix)
             x8 = kernels.pack_channels_last8(x, (B, T, C, H, W), (C * T * H * W, H * W, T * H * W, W, 1), half)
-            w8 = self.__dict__.setdefault("_stem8", {})
-            key = (wt.data_ptr(), wt._version)
-            if key not in w8:
-                taps = k[1] * k[2]
-                t8 = torch.zeros(wt.shape[0], -(-taps * 8 // 32) * 32, dtype=wt.dtype, device=wt.device)
-                t8[:, :taps * 8].view(wt.shape[0], taps, 8)[:, :, :C] = wt[:, :taps * C].reshape(wt.shape[0], taps, C)
-                w8.clear()
-                w8[key] = t8
-            y = kernels.conv_implicit(x8.reshape(B, T, H, W, 8), w8[key], bias, k, stride, pad, True)
+            y = kernels.conv_implicit(x8.reshape(B, T, H, W, 8), stem8, bias, k, stride, pad, True)
         else:
             a, (d, h, w) = kernels.im2col_nd(x, (B, C, T, H, W), (C * T * H * W, T * H * W, H * W, W, 1), k, stride, pad,
                                              half, wt.shape[1])
@@ -391,7 +378,7 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
         Hs, Ws = odim(H, 7, 2, 3), odim(W, 7, 2, 3)
         Hp, Wp = odim(Hs, 3, 2, 1), odim(Ws, 3, 2, 1)
         # stems: slow 3 -> 64 (1x7x7), fast 3 -> 8 (5x7x7), each followed by the (1,3,3) max-pool
-        wt, bias, k, st, pd = Wt[fe + "0.multipathway_blocks.0"]
+        wt, bias, k, st, pd = Wt[SLOW_STEM]
         slow = tensor(B, T // 4, Hp, Wp, 64 + 2 * FAST_C[0])
         if STEM_POOL and tuple(k) == (1, 7, 7) and tuple(st) == (1, 2, 2) and tuple(pd) == (0, 3, 3) and wt.shape[0] == 64 and W <= 224 and W % 4 == 0:
             # frame selection + stem + max-pool in one launch straight from the fp32 clip (no slow clip, no 64-channel stem map in HBM)
@@ -401,10 +388,7 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
         else:
             slow_in = tensor(B, T // 4, H, W, 3, _abi.NET_T_F32_PLANAR)
             op(_abi.NET_SELECT_T, fast_in, slow_in, t_index=t_sel)
-            taps = k[1] * k[2]
-            w8 = torch.zeros(wt.shape[0], -(-taps * 8 // 32) * 32, dtype=wt.dtype, device=device)
-            w8[:, :taps * 8].view(wt.shape[0], taps, 8)[:, :, :3] = wt[:, :taps * 3].reshape(wt.shape[0], taps, 3)
-            keep.append(w8)
+            w8 = Wt[SLOW_STEM + "/stem8"]
             s_stem = tensor(B, T // 4, Hs, Ws, 64)
             op(_abi.NET_STEM8, slow_in, s_stem, k, st, pd, cout=64, kpad=w8.shape[1], relu=1, w=w8, bias=bias)
             op(_abi.NET_POOL, s_stem, slow, (1, 3, 3), (1, 2, 2), (0, 1, 1), is_max=1, dst_coff=0)
@@ -568,7 +552,7 @@ class slowfast(nn.Module):  # noqa: N801  (reference spelling)
         W = self._weights(fast_in.device)
         half = _abi.torch_dtype(self.operand_dtype)
         fe = "feature_extraction."
-        slow = self._stem(slow_in.float().contiguous(), W[fe + "0.multipathway_blocks.0"], half)
+        slow = self._stem(slow_in.float().contiguous(), W[SLOW_STEM], half, stem8=W[SLOW_STEM + "/stem8"])
         fast = self._stem(fast_in.float().contiguous(), W[fe + "0.multipathway_blocks.1"], half,
                           W.get(fe + "0.multipathway_blocks.1/direct"), W.get(fe + "0.multipathway_blocks.1/mfma"))
         slow = torch.cat([slow, self._conv_relu(fast, W[fe + "0.multipathway_fusion"])], dim=-1)

@@ -18,7 +18,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from ... import _abi, kernels
+from ... import _abi, _prepared, kernels
 from ..._abi import KvqSwinBlockW, KvqSwinCfg, KvqSwinWeights, check, current_stream, lib, ptr
 
 
@@ -118,10 +118,11 @@ class SwinTransformer3D(nn.Module):
                  base_x_size=(32, 224, 224), operand_dtype=None):
         super().__init__()
         # 16-bit MFMA operand type (extension over the reference signature): "fp16" (default; holds the
-        # 1e-3 MOS parity gate) or "bf16".  Env KVQ_OPERAND_DTYPE overrides the default.
-        self.operand_dtype = _abi.dtype_code(operand_dtype or os.environ.get("KVQ_OPERAND_DTYPE", "fp16"))
-        # proj+norm2+Mlp as one launch where the width allows it (C <= 192); KVQ_FUSED_TAIL=0 keeps the GEMM chain
-        self.fused_tail = True          # False: proj / norm2 / fc1 / fc2 as separate launches (tests compare the two)
+        # 1e-3 MOS parity gate) or "bf16".  The environment sets the default, the argument overrides it (_prepared.default_operand_dtype).
+        self.operand_dtype = _prepared.default_operand_dtype(operand_dtype)
+        # packed weight images of the fused launches (patch embedding, proj+norm2+Mlp tail, the next block's q|k|v, PatchMerging) wherever
+        # the library has a kernel for the width.  False: none, so the plan runs the unfused launches and a FragmentSource is materialised
+        self.fused_tail = True          # (tests compare the two)
         # attention bias pre-built per (window, head) for each plan geometry (csrc/attn.hip, dense variant): ~1.2 GB of
         # HBM for Swin-T at 32x224x224; KVQ_DENSE_BIAS=0 (or a geometry above the cap) keeps the per-score gather path
         self.dense_bias = os.environ.get("KVQ_DENSE_BIAS", "1") != "0"
@@ -246,25 +247,25 @@ class SwinTransformer3D(nn.Module):
     def _weights(self, device) -> KvqSwinWeights:
         """bf16 copies of the GEMM weights + a KvqSwinWeights of raw pointers; rebuilt whenever a
         parameter was modified in place or moved (tracked through tensor versions / data_ptr)."""
-        sig = (self.operand_dtype, self.fused_tail, FUSE_MERGE) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        sig = _prepared.signature((self.operand_dtype, str(device), self.fused_tail, FUSE_MERGE), self.parameters())
         if self._wcache is not None and self._wcache[0] == sig:
             return self._wcache[1]
         keep = []
         half = _abi.torch_dtype(self.operand_dtype)
 
         def f32(p):
-            t = p.detach().to(device=device, dtype=torch.float32).contiguous()
-            keep.append(t)
-            return ptr(t)
+            keep.append(_prepared.to_f32(p, device))
+            return ptr(keep[-1])
 
-        def bf16(p, shape=None):       # GEMM weight in the 16-bit operand type (fp16 saturates, never inf)
-            t = p.detach().to(device=device, dtype=torch.float32)
-            t = t.reshape(shape) if shape is not None else t
-            if half == torch.float16:
-                t = t.clamp(-65504.0, 65504.0)
-            t = t.to(half).contiguous()
-            keep.append(t)
-            return ptr(t)
+        def bf16(p, shape=None):       # GEMM weight in the 16-bit operand type
+            keep.append(_prepared.to_operand(p, half, device, shape))
+            return ptr(keep[-1])
+
+        def image(nbytes, entry, *args):
+            """The ``nbytes`` weight image that the library's ``entry`` writes from ``args``: kept alive with the weights, returned as a pointer."""
+            keep.append(torch.empty(nbytes, dtype=torch.uint8, device=device))
+            check(getattr(lib(), entry)(*args, ptr(keep[-1]), current_stream()), entry)
+            return ptr(keep[-1])
 
         w = KvqSwinWeights()
         pe = self.patch_embed
@@ -275,11 +276,7 @@ class SwinTransformer3D(nn.Module):
         K0 = pe.proj.weight[0].numel()
         nbytes = lib().kvq_patch_embed_pack_bytes(self.embed_dim, K0) if self.fused_tail else 0
         if nbytes:          # im2col + GEMM + LayerNorm (+ the first norm1) as one launch (csrc/embed.hip)
-            ep = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            check(lib().kvq_patch_embed_pack(w.embed_w, w.embed_b, w.embed_ln_w, w.embed_ln_b, self.embed_dim, K0, ptr(ep),
-                                             current_stream()), "kvq_patch_embed_pack")
-            keep.append(ep)
-            w.embed_pack = ptr(ep)
+            w.embed_pack = image(nbytes, "kvq_patch_embed_pack", w.embed_w, w.embed_b, w.embed_ln_w, w.embed_ln_b, self.embed_dim, K0)
         nblk = sum(self.depths)
         blocks = (KvqSwinBlockW * nblk)()
         k = 0
@@ -310,17 +307,11 @@ class SwinTransformer3D(nn.Module):
                 Cb, hid = blk.mlp.fc1.weight.shape[1], blk.mlp.fc1.weight.shape[0]
                 nbytes = lib().kvq_block_tail_pack_bytes(Cb, hid) if self.fused_tail else 0
                 if nbytes:      # fused proj+norm2+Mlp launch for this width (csrc/tail.hip)
-                    tp = torch.empty(nbytes, dtype=torch.uint8, device=device)
-                    check(lib().kvq_block_tail_pack(b.proj_w, b.proj_b, b.norm2_w, b.norm2_b, b.fc1_w, b.fc1_b, b.fc2_w,
-                                                    b.fc2_b, Cb, hid, ptr(tp), current_stream()), "kvq_block_tail_pack")
-                    keep.append(tp)
-                    b.tail_pack = ptr(tp)
+                    b.tail_pack = image(nbytes, "kvq_block_tail_pack", b.proj_w, b.proj_b, b.norm2_w, b.norm2_b, b.fc1_w, b.fc1_b, b.fc2_w,
+                                        b.fc2_b, Cb, hid)
                 nbytes = lib().kvq_block_tail_qkv_pack_bytes(Cb, hid) if self.fused_tail else 0
                 if nbytes:      # this block's qkv weight as the image the PREVIOUS block's tail streams to emit q | k | v (csrc/tailmm.hip)
-                    qp = torch.empty(nbytes, dtype=torch.uint8, device=device)
-                    check(lib().kvq_block_tail_qkv_pack(b.qkv_w, Cb, hid, ptr(qp), current_stream()), "kvq_block_tail_qkv_pack")
-                    keep.append(qp)
-                    b.qkv_pack = ptr(qp)
+                    b.qkv_pack = image(nbytes, "kvq_block_tail_qkv_pack", b.qkv_w, Cb, hid)
             if layer.downsample is not None:
                 m = w.merges[i]
                 m.norm_w, m.norm_b = f32(layer.downsample.norm.weight), f32(layer.downsample.norm.bias)
@@ -328,11 +319,8 @@ class SwinTransformer3D(nn.Module):
                 Cm = layer.downsample.reduction.weight.shape[1] // 4
                 nbytes = lib().kvq_patch_merge_pack_bytes(Cm) if self.fused_tail and FUSE_MERGE else 0
                 if nbytes:      # concat + LayerNorm + reduction (+ the next norm1) as one launch for this width (csrc/merge.hip)
-                    mp = torch.empty(nbytes, dtype=torch.uint8, device=device)
-                    check(lib().kvq_patch_merge_pack(f32(layer.downsample.reduction.weight), m.norm_w, m.norm_b, Cm, self.operand_dtype,
-                                                     ptr(mp), current_stream()), "kvq_patch_merge_pack")
-                    keep.append(mp)
-                    m.merge_pack = ptr(mp)
+                    m.merge_pack = image(nbytes, "kvq_patch_merge_pack", f32(layer.downsample.reduction.weight), m.norm_w, m.norm_b, Cm,
+                                         self.operand_dtype)
         w.blocks = C.cast(blocks, C.POINTER(KvqSwinBlockW))
         w.norm_w, w.norm_b = f32(self.norm.weight), f32(self.norm.bias)
         keep.append(blocks)

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from .. import kernels
+from .._prepared import PreparedCache, to_f32
 from .backbones.swin_backbone import _Affine
 
 
@@ -21,18 +22,18 @@ class VQAHead(nn.Module):
         with torch.no_grad():
             nn.init.trunc_normal_(self.fc_hid.weight, std=0.02)
             nn.init.trunc_normal_(self.fc_last.weight, std=0.02)
+        self._cache = PreparedCache()
 
     def _prepared(self, device):
         """fp32 device copies in the layouts the kernels stream (W1 as it is and transposed), rebuilt only when a
         parameter changed (version / data_ptr) — no per-forward conversion kernels."""
         ps = (self.fc_hid.weight, self.fc_hid.bias, self.fc_last.weight, self.fc_last.bias)
-        sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_cache", None) is None or self._cache[0] != sig:
-            f32 = lambda p: p.detach().to(device=device, dtype=torch.float32)  # noqa: E731
-            w1 = f32(ps[0]).reshape(self.hidden_channels, -1).contiguous()
-            self._cache = (sig, (w1.t().contiguous(), f32(ps[1]).contiguous(), f32(ps[2]).reshape(-1).contiguous(),
-                                 f32(ps[3]).contiguous(), w1))
-        return self._cache[1]
+
+        def build():
+            w1, b1, w2, b2 = (to_f32(p, device) for p in ps)
+            w1 = w1.reshape(self.hidden_channels, -1)
+            return w1.t().contiguous(), b1, w2.reshape(-1), b2, w1
+        return self._cache.get((str(device),), ps, build)
 
     def forward(self, x, rois=None, return_map=False):
         """x (B, C, D, H, W) fp32 (any strides) -> (B, num_class).  ``return_map``: ``(score, token_map (B,D,H,W), timeline (B,D))``
