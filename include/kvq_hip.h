@@ -138,17 +138,33 @@ size_t kvq_swin3d_workspace_bytes(const KvqSwinPlan* plan);
 int kvq_swin3d_out_dims(const KvqSwinPlan* plan, int32_t out4[4]);
 
 #define KVQ_FRAG_MAX_CLIPS 16
+/* Frame type of a source (the `src_is_u8` argument / field: 0 and 1 keep the meaning they always had).  The I420 values name
+ * planar YUV 4:2:0 frames, "I420, frame-major": every frame is Y (H x W) | U | V (ceil(H/2) x ceil(W/2) each), contiguous,
+ * H W + 2 ceil(H/2) ceil(W/2) bytes, frames back to back (the payload layout of Y4M; a run of frames of a longer video is
+ * still one pointer).  Odd H and W are legal.  Every consumer converts with the one integer conversion of kvq_yuv420_to_rgb
+ * below and then treats the R, G, B bytes exactly as it treats uint8 frames: its output is bit-equal to the same call on the
+ * converted frames. */
+typedef enum {
+  KVQ_SRC_F32 = 0,                 /* fp32 (C, T, H, W)  */
+  KVQ_SRC_U8 = 1,                  /* uint8 (C, T, H, W) */
+  KVQ_SRC_I420_BT601_LIMITED = 2,  /* I420, BT.601 matrix (Kr .299, Kb .114), luma 16..235 / chroma 16..240 */
+  KVQ_SRC_I420_BT601_FULL = 3,     /* BT.601, full range (JPEG)            */
+  KVQ_SRC_I420_BT709_LIMITED = 4,  /* BT.709 (Kr .2126, Kb .0722), limited */
+  KVQ_SRC_I420_BT709_FULL = 5
+} KvqSrcFormat;
 /* A batch of clips that is still (decoded frames, sampler draws): what kvq_fragment_gather would be called with, clip by clip.
  * kvq_patch_embed / kvq_swin3d_forward_fragments read the patch-embedding operand straight from it — get_spatial_fragments
  * (fusion_datasets.py:22-121) + (v - mean) / std (:1017-1020) happen in registers, with the same fp32 arithmetic, and the fp32
  * (B,3,T,H,W) clip (4 B/pixel written, 4 B/pixel read back) never exists. */
 typedef struct {
   const void* video[KVQ_FRAG_MAX_CLIPS];     /* clip b: uint8 (C, T, Hs, Ws), device; frames contiguous, channel planes
-                                                chan_stride ELEMENTS apart (a clip may be a run of frames of a longer video) */
+                                                chan_stride ELEMENTS apart (a clip may be a run of frames of a longer video).
+                                                I420 (src_is_u8 >= KVQ_SRC_I420_BT601_LIMITED): the clip's first frame, T frames
+                                                back to back, C == 3; chan_stride is ignored */
   const int32_t* hoff[KVQ_FRAG_MAX_CLIPS];   /* clip b: int32 [Fh][Fw][T/aligned] absolute patch origins, device    */
   const int32_t* woff[KVQ_FRAG_MAX_CLIPS];
   int64_t chan_stride;                       /* in ELEMENTS of the frame type; 0 = T * Hs * Ws (contiguous clips)    */
-  int32_t n_clips, src_is_u8, Hs, Ws, Fh, Fw, fs_h, fs_w, aligned;
+  int32_t n_clips, src_is_u8 /* KvqSrcFormat */, Hs, Ws, Fh, Fw, fs_h, fs_w, aligned;
   int32_t normalise;                         /* 0: raw pixel values                                                  */
   float mean[4], std[4];
   const void* const* indirect;               /* ABI 30.  NULL, or a DEVICE array of 3 * KVQ_FRAG_MAX_CLIPS pointers — video[16] | hoff[16] |
@@ -522,8 +538,8 @@ int kvq_vqa_head_map(const float* feat, int B, int L, int C, int64_t stride_b, i
  * the sum over the tokens with area_k > 0 in increasing row-major (i', j') order, starting from 0.f, with separately rounded fp32
  * multiplies and adds and a correctly rounded divide: a defined bit pattern (cell == 1: a copy of the scores).
  *
- * overlay (NULL = none): uint8 [n_clips][n_ov][3][Hs][Ws], slice n drawn on clip frame 2 ov_depth[n] (uint8 frames only; the channel
- * order is the source's).  With (lo, hi) = range[0], range[1] (device), inv = 1 / (hi - lo) in fp32 and s the pixel's cell == 1 heat:
+ * overlay (NULL = none): uint8 [n_clips][n_ov][3][Hs][Ws], slice n drawn on clip frame 2 ov_depth[n] (uint8 or I420 frames, no fp32;
+ * the channel order is the source's, R G B for I420).  With (lo, hi) = range[0], range[1] (device), inv = 1 / (hi - lo) in fp32 and s the pixel's cell == 1 heat:
  *   q = rint(min(max((s - lo) * inv, 0), 1) * 255),  colour = (255 - q, q, 0)
  *   covered pixel:   (src * (256 - alpha) + colour * alpha + 128) >> 8        uncovered pixel:  (src * dim + 128) >> 8
  * A gather (no atomics, deterministic): one launch for heat / cover, one more when an overlay is asked for.  The frames are read
@@ -589,20 +605,36 @@ int kvq_simple_vqa_head(const float* feat, int B, int T, int Cin, const float* w
 
 /* get_spatial_fragments + (v-mean)/std (datasets/fusion_datasets.py:22-121, 1017-1020) with the
  * drawn offsets as inputs (the reference draws them inside with torch.randint, :87-98).
- *   video  uint8 or fp32 (C,T,H,W) on device (src_is_u8 selects)
+ *   video  uint8 or fp32 (C,T,H,W) on device (src_is_u8 selects), or T I420 frames (src_is_u8 = a KVQ_SRC_I420_* value, C == 3)
  *   hoff/woff int32 [Fh][Fw][T/aligned] absolute patch origins = grid + random offset
  *   out    fp32 (C,T,Fh*fs_h,Fw*fs_w);  mean/std: host fp32 [C] (std==NULL -> no normalisation) */
 int kvq_fragment_gather(const void* video, int src_is_u8, int C, int T, int H, int W, const int32_t* hoff,
                         const int32_t* woff, int Fh, int Fw, int fs_h, int fs_w, int aligned,
                         const float* host_mean, const float* host_std, float* out, void* stream);
-/* The same for every clip of a KvqFragmentSource in ONE launch (uint8 or fp32 frames, clips may be frame runs of a longer
+/* The same for every clip of a KvqFragmentSource in ONE launch (uint8, fp32 or I420 frames, clips may be frame runs of a longer
  * video: chan_stride): out fp32 (n_clips, C, T, Fh*fs_h, Fw*fs_w).  What FragmentSource.materialise() runs. */
 int kvq_fragment_gather_batch(const KvqFragmentSource* src, int C, int T, float* out, void* stream);
+
+/* Planar YUV 4:2:0 -> RGB, the conversion of every KVQ_SRC_I420_* consumer.  Chroma is sampled nearest (pixel (y, x) takes chroma
+ * sample (y >> 1, x >> 1)); integer arithmetic with 16 fractional bits:
+ *   q = floor(c * 65536 + 0.5) for  qy = s_y,  qrv = 2 (1 - Kr) s_c,  qgu = -2 (1 - Kb) Kb / Kg s_c,  qgv = -2 (1 - Kr) Kr / Kg s_c,
+ *   qbu = 2 (1 - Kb) s_c   with Kg = 1 - Kr - Kb, limited range: s_y = 255 / 219, s_c = 255 / 224, yoff = 16; full: 1, 1, 0
+ *   R = clamp((qy (Y - yoff) + qrv (V - 128) + 32768) >> 16, 0, 255)
+ *   G = clamp((qy (Y - yoff) + qgu (U - 128) + qgv (V - 128) + 32768) >> 16, 0, 255)
+ *   B = clamp((qy (Y - yoff) + qbu (U - 128) + 32768) >> 16, 0, 255)         (>> of a negative sum: arithmetic)
+ * int32 never overflows; the result is within 1 of floor(float64 + 0.5).
+ * kvq_yuv420_coeffs (host only): out6 = qy, qrv, qgu, qgv, qbu, yoff of `format`, the integers the launches carry.
+ * kvq_yuv420_to_rgb: frames = T I420 frames (device) -> rgb_out uint8 (3, T, H, W), one launch. */
+int kvq_yuv420_coeffs(int format /* KVQ_SRC_I420_* */, int32_t host_out6[6]);
+int kvq_yuv420_to_rgb(const void* frames, int T, int H, int W, int format, uint8_t* rgb_out, void* stream);
 
 /* torchvision Resize on a tensor (= bilinear, align_corners=False, no antialias; get_resize_function,
  * fusion_datasets.py:229-241) + crop + (v-mean)/std: get_resized_video (:244-252), get_resizecrop_video
  * (:299-316).  video u8|fp32 (C,T,H,W) -> resized to (rh,rw) -> crop [cy:cy+oh, cx:cx+ow] -> out fp32
- * (C,T,oh,ow).  round_u8: round+clamp to 0..255 before normalising (what torchvision does to integer tensors). */
+ * (C,T,oh,ow).  round_u8: round+clamp to 0..255 before normalising (what torchvision does to integer tensors).
+ * src_is_u8 must be KVQ_SRC_F32 or KVQ_SRC_U8 here, in kvq_resize_bilinear_aa and in kvq_upsample_frames: since the I420 values
+ * exist any other value is KVQ_ERR_UNSUPPORTED (before, every non-zero value meant uint8) — I420 frames would be read past their
+ * end as uint8 planes; convert them first (kvq_yuv420_to_rgb). */
 int kvq_resize_bilinear(const void* video, int src_is_u8, int C, int T, int H, int W, int rh, int rw, int cy,
                         int cx, int oh, int ow, int round_u8, const float* host_mean, const float* host_std,
                         float* out, void* stream);

@@ -112,6 +112,16 @@ class KvqBlockTailArgs(C.Structure):
 
 
 FRAG_MAX_CLIPS = 16
+# KvqSrcFormat: the frame type of a source (the ``src_is_u8`` argument / field).  The I420 values: planar YUV 4:2:0, frame-major
+SRC_F32, SRC_U8, SRC_I420_BT601_LIMITED, SRC_I420_BT601_FULL, SRC_I420_BT709_LIMITED, SRC_I420_BT709_FULL = range(6)
+I420_FORMATS = (SRC_I420_BT601_LIMITED, SRC_I420_BT601_FULL, SRC_I420_BT709_LIMITED, SRC_I420_BT709_FULL)
+
+
+def i420_format(matrix="bt601", full_range=False) -> int:
+    """the KvqSrcFormat of I420 frames with the ``bt601`` | ``bt709`` matrix in limited or full range"""
+    if matrix not in ("bt601", "bt709"):
+        raise ValueError(f"yuv matrix must be 'bt601' or 'bt709', got {matrix!r}")
+    return (SRC_I420_BT601_LIMITED if matrix == "bt601" else SRC_I420_BT709_LIMITED) + int(bool(full_range))
 
 
 class KvqFragmentSource(C.Structure):
@@ -263,6 +273,8 @@ SYMBOLS = {
     "kvq_pool_nd_strided": (i32, [p_void, i32, C.POINTER(i32 * 5), C.POINTER(i32 * 3), C.POINTER(i32 * 3), C.POINTER(i32 * 3),
                                   i32, p_void, i32, i32, p_void]),
     "kvq_mean_std_pool": (i32, [p_void, i32, i32, i32, i32, p_void, i64, i32, i32, p_void]),
+    "kvq_yuv420_coeffs": (i32, [i32, C.POINTER(i32 * 6)]),
+    "kvq_yuv420_to_rgb": (i32, [p_void, i32, i32, i32, i32, p_void, p_void]),
     "kvq_fragment_gather_batch": (i32, [C.POINTER(KvqFragmentSource), i32, i32, p_void, p_void]),
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),

@@ -13,20 +13,29 @@
 // fs_h x fs_w mini-patch, so its rows are two 4-byte runs of a source row) and is normalised in registers with the same
 // IEEE fp32 (v - mean) / std as kvq_fragment_gather — the operands are bit-identical to the two-launch sequence, which
 // wrote the fp32 clip (4 B/px) and read it back (4 B/px).
+//
+// I420 (patch_embed_i420_kernel): the frames are planar YUV 4:2:0 (I420, 1.5 B/px: what a decoder hands over).  A lane's 4 x 2 pixels of a frame are the same
+// two 4-byte Y loads plus their chroma samples (nearest: (y >> 1, x >> 1); a patch origin may be odd in either axis, so a row of four
+// pixels spans two or three samples: one 2-byte and one 1-byte load per plane and row, never a byte outside the frame), converted to
+// R, G, B bytes in registers with yuv.hpp's integers and packed into the words the uint8 read loads — everything behind that point,
+// the s_tab lookup included, is the same code, so the operands are the numbers the uint8 read produces from the converted frames.
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "yuv.hpp"
 
 namespace kvq {
 
 struct FragSrc {
-  const uint8_t* video[KVQ_FRAG_MAX_CLIPS];   // clip b: (Cin, T, Hs, Ws)
+  const uint8_t* video[KVQ_FRAG_MAX_CLIPS];   // clip b: (Cin, T, Hs, Ws), or T I420 frames
   const int32_t* hoff[KVQ_FRAG_MAX_CLIPS];    // clip b: [Fh][Fw][T / aligned] patch origins
   const int32_t* woff[KVQ_FRAG_MAX_CLIPS];
   long chan_stride;
   int Hs, Ws, Fw, fsh, fsw, aligned;
   float mean[4], std[4];
   const void* const* table;   // KvqFragmentSource.indirect: video[16] | hoff[16] | woff[16] in device memory, or nullptr
+  int i420;                   // the frames are I420: patch_embed_i420_kernel, with the conversion's integers
+  YuvCoef yuv;
 };
 
 struct EmbedParams {
@@ -81,8 +90,10 @@ __host__ __device__ constexpr int embed_stage_off(int CM, int KS) { return CM * 
 #endif
 __host__ __device__ constexpr bool embed_staged(int CM, bool) { return CM == 3 && KVQ_EMBED_STAGED; }
 
-template <typename E_, int CM, int KS, bool EMIT, bool FRAG>
-__global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_embed_kernel(EmbedParams p) {
+// The body of both kernels below.  FRAG: the operand is read through the sampler (else from the fp32 clip); I420 (with FRAG): out of
+// I420 frames instead of uint8 channel planes.
+template <typename E_, int CM, int KS, bool EMIT, bool FRAG, bool I420>
+__device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   fp16_saturate_mode();
   constexpr int E = 32 * CM, WBYTES = CM * KS * 1024;
   constexpr bool STAGED = embed_staged(CM, FRAG);
@@ -130,12 +141,48 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
     const size_t plane = (size_t)f.Hs * f.Ws;
     const uint8_t* vb = f.table ? (const uint8_t*)f.table[bu] : f.video[bu];
     typedef uint32_t __attribute__((aligned(1))) u32u;
+    if constexpr (I420) {
+      typedef uint16_t __attribute__((aligned(1))) u16u;
+      constexpr int PD = KS / 3;                     // three channels (checked on the host): k-step s is (c, kd) = (s / PD, s % PD)
+      const I420Geom geo = i420_geom(f.Hs, f.Ws);
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int c = s / p.pd, t = d * p.pd + (s - c * p.pd), g = t / f.aligned;
-      const uint8_t* src = vb + (size_t)c * f.chan_stride + (size_t)t * plane + (size_t)(ho[g] + (oy - fi * f.fsh)) * f.Ws + (wo[g] + (ox - fj * f.fsw));
-      raw[s][0] = *reinterpret_cast<const u32u*>(src);
-      raw[s][1] = *reinterpret_cast<const u32u*>(src + f.Ws);
+      for (int kd = 0; kd < PD; ++kd) {
+        const int t = d * PD + kd, g = t / f.aligned;
+        const int sy = ho[g] + (oy - fi * f.fsh), sx = wo[g] + (ox - fj * f.fsw);
+        const uint8_t* fr = vb + (size_t)t * geo.frame;
+        // pixels sx .. sx + 3 take chroma columns cx, cx | cx + 1, cx + 1, cl with cl = (sx + 3) >> 1 = cx + 1 (sx even) or cx + 2 (odd):
+        // columns cx and cx + 1 as one 2-byte load, cl as a byte — all <= (Ws - 1) >> 1 because sx + 3 <= Ws - 1
+        const int cx = sx >> 1, cl = (sx + 3) >> 1;
+        const bool odd = sx & 1;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const uint32_t yw = *reinterpret_cast<const u32u*>(fr + (size_t)(sy + r) * f.Ws + sx);
+          const uint8_t* up = fr + geo.ysize + (size_t)((sy + r) >> 1) * geo.cw;
+          const uint8_t* vp = up + geo.csize;
+          const uint32_t u01 = *reinterpret_cast<const u16u*>(up + cx), v01 = *reinterpret_cast<const u16u*>(vp + cx);
+          // samples cx, cx + 1, cl; pixels 0 .. 3 take 0, (odd ? 1 : 0), 1, cl
+          const YuvChroma c0 = yuv_chroma(f.yuv, (int)(u01 & 255u), (int)(v01 & 255u)), c1 = yuv_chroma(f.yuv, (int)(u01 >> 8), (int)(v01 >> 8));
+          const YuvChroma c3 = yuv_chroma(f.yuv, (int)up[cl], (int)vp[cl]);
+          const YuvChroma ch[4] = {c0, odd ? c1 : c0, c1, c3};
+          uint32_t rr = 0, gg = 0, bb = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int l = yuv_luma(f.yuv, (int)((yw >> (8 * e)) & 255u));
+            rr |= (uint32_t)yuv_out(l, ch[e].r) << (8 * e);
+            gg |= (uint32_t)yuv_out(l, ch[e].g) << (8 * e);
+            bb |= (uint32_t)yuv_out(l, ch[e].b) << (8 * e);
+          }
+          raw[kd][r] = rr; raw[PD + kd][r] = gg; raw[2 * PD + kd][r] = bb;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const int c = s / p.pd, t = d * p.pd + (s - c * p.pd), g = t / f.aligned;
+        const uint8_t* src = vb + (size_t)c * f.chan_stride + (size_t)t * plane + (size_t)(ho[g] + (oy - fi * f.fsh)) * f.Ws + (wo[g] + (ox - fj * f.fsw));
+        raw[s][0] = *reinterpret_cast<const u32u*>(src);
+        raw[s][1] = *reinterpret_cast<const u32u*>(src + f.Ws);
+      }
     }
     // a pixel is one of 256 bytes: (v - mean) / std — the IEEE fp32 divide of fragment_gather_kernel — once per byte value
     // and channel (Cin divides per thread) instead of once per pixel (8 * KS per lane); looked up below, behind the barrier
@@ -295,6 +342,17 @@ __global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_emb
   }      // tiles
 }
 
+template <typename E_, int CM, int KS, bool EMIT, bool FRAG>
+__global__ __launch_bounds__(256, embed_staged(CM, FRAG) ? 2 : 3) void patch_embed_kernel(EmbedParams p) {
+  patch_embed_body<E_, CM, KS, EMIT, FRAG, false>(p);
+}
+
+// the sampler read out of I420 frames (KvqFragmentSource.src_is_u8 = a KVQ_SRC_I420_* value)
+template <typename E_, int CM, int KS, bool EMIT>
+__global__ __launch_bounds__(256, embed_staged(CM, true) ? 2 : 3) void patch_embed_i420_kernel(EmbedParams p) {
+  patch_embed_body<E_, CM, KS, EMIT, true, true>(p);
+}
+
 template <typename E_, int CM, int KS>
 static int launch_embed(const EmbedParams& p, hipStream_t st) {
   const int lds = embed_stage_off(CM, KS) + (embed_staged(CM, p.x == nullptr) ? 4 * 32 * (32 * CM * 4 + 16) : 0);
@@ -307,7 +365,8 @@ static int launch_embed(const EmbedParams& p, hipStream_t st) {
     return KVQ_OK;
   };
   int rc;
-  if (p.x == nullptr) rc = p.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, true>) : go(patch_embed_kernel<E_, CM, KS, false, true>);
+  if (p.x == nullptr && p.frag.i420) rc = p.next_ln ? go(patch_embed_i420_kernel<E_, CM, KS, true>) : go(patch_embed_i420_kernel<E_, CM, KS, false>);
+  else if (p.x == nullptr) rc = p.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, true>) : go(patch_embed_kernel<E_, CM, KS, false, true>);
   else rc = p.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, false>) : go(patch_embed_kernel<E_, CM, KS, false, false>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("patch_embed_kernel");
@@ -340,11 +399,14 @@ extern "C" int kvq_patch_embed_pack(const void* w, const float* bias, const floa
 }
 
 extern "C" int kvq_patch_embed_fragments_supported(const KvqFragmentSource* f, int B, int in_chans, int pd, int T, int H, int W) {
-  // uint8 frames; whole 4 x 4 patches inside a mini-patch; one clip per wave of 32 tokens; frames of a token in range
-  if (!f || !f->src_is_u8 || f->n_clips != B || B > KVQ_FRAG_MAX_CLIPS || in_chans > 4 || pd <= 0) return 0;
+  // uint8 or I420 frames; whole 4 x 4 patches inside a mini-patch; one clip per wave of 32 tokens; frames of a token in range
+  if (!f || f->src_is_u8 < KVQ_SRC_U8 || f->src_is_u8 > KVQ_SRC_I420_BT709_FULL || f->n_clips != B || B > KVQ_FRAG_MAX_CLIPS || in_chans > 4 ||
+      pd <= 0) return 0;
+  const bool i420 = kvq::yuv_format_ok(f->src_is_u8);
+  if (i420 && (in_chans != 3 || !kvq::i420_size_ok(f->Hs, f->Ws))) return 0;      // R, G, B
   if (f->fs_h <= 0 || f->fs_w <= 0 || f->fs_h % 4 || f->fs_w % 4 || f->Fh * f->fs_h != H || f->Fw * f->fs_w != W) return 0;
   if (f->aligned <= 0 || T % f->aligned || T % pd) return 0;
-  if (f->chan_stride < 0 || (f->chan_stride && f->chan_stride < (long)T * f->Hs * f->Ws)) return 0;
+  if (!i420 && (f->chan_stride < 0 || (f->chan_stride && f->chan_stride < (long)T * f->Hs * f->Ws))) return 0;
   if (f->Hs < H || f->Ws < W) return 0;                      // the upsample fallback is not in the hot path (as kvq_fragment_gather)
   return ((long)(T / pd) * (H / 4) * (W / 4)) % 32 == 0 ? 1 : 0;
 }
@@ -377,6 +439,8 @@ int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStre
     }
     p.frag.chan_stride = f->chan_stride ? f->chan_stride : (long)a->T * f->Hs * f->Ws;
     p.frag.Hs = f->Hs; p.frag.Ws = f->Ws; p.frag.Fw = f->Fw; p.frag.fsh = f->fs_h; p.frag.fsw = f->fs_w; p.frag.aligned = f->aligned;
+    p.frag.i420 = yuv_format_ok(f->src_is_u8);
+    if (p.frag.i420) p.frag.yuv = yuv420_coeffs(f->src_is_u8);
     for (int c = 0; c < 4; ++c) { p.frag.mean[c] = f->normalise ? f->mean[c] : 0.f; p.frag.std[c] = f->normalise ? f->std[c] : 1.f; }   // (v - 0) / 1 == v
   }
   p.x = a->x; p.B = a->B; p.Cin = a->in_chans; p.T = a->T; p.H = a->H; p.W = a->W; p.pd = a->pd;

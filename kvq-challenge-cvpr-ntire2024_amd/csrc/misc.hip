@@ -1,5 +1,6 @@
 // HBM-bound helpers around the trunk: patch-embed im2col, the two score heads, the fragment sampler.
 #include "common.hpp"
+#include "yuv.hpp"
 
 namespace kvq {
 
@@ -308,6 +309,7 @@ struct FragParams {
   int normalise;
   float* out;
   long chan_stride;          // elements between the channel planes of a clip (T * H * W when contiguous)
+  YuvCoef yuv;               // src_is_u8 >= KVQ_SRC_I420_BT601_LIMITED: T I420 frames, converted per pixel (yuv.hpp)
 };
 
 // a batch of clips in one launch (blockIdx.z = clip): per-clip frames / draws, outputs out + z * C * T * OH * OW
@@ -340,7 +342,14 @@ __global__ __launch_bounds__(256) void fragment_gather_kernel(FragParams p, Frag
   const int sy = p.hoff[o] + (oy - fi * p.fsh), sx = p.woff[o] + (ox - fj * p.fsw);
   const size_t src = (size_t)c * p.chan_stride + ((size_t)t * p.H + sy) * p.W + sx;
   float v[VW];
-  if (p.src_is_u8) {
+  if (p.src_is_u8 >= KVQ_SRC_I420_BT601_LIMITED) {
+    // every channel plane converts its own pixels: three byte loads each, all inside frame t (this is not the hot path — the fused
+    // embedding read is)
+    const I420Geom geo = i420_geom(p.H, p.W);
+    const uint8_t* fr = reinterpret_cast<const uint8_t*>(p.video) + (size_t)t * geo.frame;
+#pragma unroll
+    for (int e = 0; e < VW; ++e) v[e] = (float)i420_pixel(fr, geo, p.yuv, c, sy, sx + e);
+  } else if (p.src_is_u8) {
     const uint8_t* s8 = reinterpret_cast<const uint8_t*>(p.video) + src;
 #pragma unroll
     for (int e = 0; e < VW; ++e) v[e] = (float)s8[e];
@@ -410,6 +419,7 @@ extern "C" int kvq_resize_bilinear(const void* video, int src_is_u8, int C, int 
                                    int cx, int oh, int ow, int round_u8, const float* host_mean, const float* host_std,
                                    float* out, void* stream) {
   using namespace kvq;
+  KVQ_REQUIRE(src_is_u8 == KVQ_SRC_F32 || src_is_u8 == KVQ_SRC_U8, KVQ_ERR_UNSUPPORTED, "kvq_resize_bilinear: frame type %d (convert I420 frames first: kvq_yuv420_to_rgb)", src_is_u8);
   KVQ_REQUIRE(video && out, KVQ_ERR_NULL, "kvq_resize_bilinear: NULL pointer");
   KVQ_REQUIRE(C > 0 && C <= 4 && T > 0 && H > 0 && W > 0 && rh > 0 && rw > 0 && oh > 0 && ow > 0 && cy >= 0 && cx >= 0 &&
                   cy + oh <= rh && cx + ow <= rw,
@@ -495,6 +505,7 @@ extern "C" int kvq_upsample_frames_out_dims(int H, int W, double scale_factor, i
 extern "C" int kvq_upsample_frames(const void* video, int src_is_u8, int C, int T, int H, int W, double scale_factor, void* out,
                                    void* stream) {
   using namespace kvq;
+  KVQ_REQUIRE(src_is_u8 == KVQ_SRC_F32 || src_is_u8 == KVQ_SRC_U8, KVQ_ERR_UNSUPPORTED, "kvq_upsample_frames: frame type %d (convert I420 frames first: kvq_yuv420_to_rgb)", src_is_u8);
   KVQ_REQUIRE(video && out, KVQ_ERR_NULL, "kvq_upsample_frames: NULL pointer");
   KVQ_REQUIRE(C > 0 && T > 0 && H > 0 && W > 0 && scale_factor > 0.0, KVQ_ERR_SHAPE, "kvq_upsample_frames: bad shape / scale");
   int32_t od[2];
@@ -707,7 +718,10 @@ extern "C" int kvq_fragment_gather(const void* video, int src_is_u8, int C, int 
   // a source smaller than the canvas is legal (the caller ran the upsample fallback, fusion_datasets.py:43-50, whose output may
   // stay one pixel short of the canvas: floor(H * scale)); what must hold is that a mini-patch fits
   KVQ_REQUIRE(H >= fs_h && W >= fs_w, KVQ_ERR_UNSUPPORTED, "kvq_fragment_gather: source %dx%d smaller than one %dx%d mini-patch", H, W, fs_h, fs_w);
+  KVQ_REQUIRE(src_is_u8 >= KVQ_SRC_F32 && src_is_u8 <= KVQ_SRC_I420_BT709_FULL && (!yuv_format_ok(src_is_u8) || (C == 3 && i420_size_ok(H, W))), KVQ_ERR_UNSUPPORTED,
+              "kvq_fragment_gather: frame type %d with %d channels", src_is_u8, C);
   FragParams p{};
+  if (yuv_format_ok(src_is_u8)) p.yuv = yuv420_coeffs(src_is_u8);
   p.video = video; p.src_is_u8 = src_is_u8; p.C = C; p.T = T; p.H = H; p.W = W;
   p.hoff = hoff; p.woff = woff; p.Fh = Fh; p.Fw = Fw; p.fsh = fs_h; p.fsw = fs_w; p.aligned = aligned;
   p.normalise = host_std != nullptr;
@@ -736,8 +750,12 @@ extern "C" int kvq_fragment_gather_batch(const KvqFragmentSource* f, int C, int 
   KVQ_REQUIRE(T % f->aligned == 0, KVQ_ERR_SHAPE, "Please provide match vclip and align index");
   KVQ_REQUIRE(f->Hs >= f->fs_h && f->Ws >= f->fs_w, KVQ_ERR_UNSUPPORTED,
               "kvq_fragment_gather_batch: source %dx%d smaller than one %dx%d mini-patch", f->Hs, f->Ws, f->fs_h, f->fs_w);
-  KVQ_REQUIRE(f->chan_stride == 0 || f->chan_stride >= (int64_t)T * f->Hs * f->Ws, KVQ_ERR_SHAPE, "kvq_fragment_gather_batch: channel stride");
+  KVQ_REQUIRE(f->src_is_u8 >= KVQ_SRC_F32 && f->src_is_u8 <= KVQ_SRC_I420_BT709_FULL && (!yuv_format_ok(f->src_is_u8) || (C == 3 && i420_size_ok(f->Hs, f->Ws))),
+              KVQ_ERR_UNSUPPORTED, "kvq_fragment_gather_batch: frame type %d with %d channels", f->src_is_u8, C);
+  KVQ_REQUIRE(yuv_format_ok(f->src_is_u8) || f->chan_stride == 0 || f->chan_stride >= (int64_t)T * f->Hs * f->Ws, KVQ_ERR_SHAPE,
+              "kvq_fragment_gather_batch: channel stride");
   FragParams p{};
+  if (yuv_format_ok(f->src_is_u8)) p.yuv = yuv420_coeffs(f->src_is_u8);
   FragBatch fb{};
   for (int b = 0; b < f->n_clips; ++b) {
     KVQ_REQUIRE(f->video[b] && f->hoff[b] && f->woff[b], KVQ_ERR_NULL, "kvq_fragment_gather_batch: clip %d has a NULL pointer", b);

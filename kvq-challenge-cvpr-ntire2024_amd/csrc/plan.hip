@@ -745,8 +745,9 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
       ea.next_ln = bln; ea.next_rows = pl->st[0].Lp;
     }
     const double px = (double)B * L0 * pl->K0;
-    Bracket br(pl, st, KVQ_K_EMBED, s.embed_emit + (frag ? 2 : 0), 2.0 * B * L0 * (double)E * pl->K0,
-               px * (frag ? 1.0 : 4.0) + (double)B * L0 * E * ((s.x16[0] ? 2.0 : 4.0) + (e1 ? 2.0 : 0.0)));
+    const bool i420 = frag && frag->src_is_u8 >= KVQ_SRC_I420_BT601_LIMITED;      // variant bit 4: patch_embed_i420_kernel, 0.5 B per operand element
+    Bracket br(pl, st, KVQ_K_EMBED, s.embed_emit + (frag ? 2 : 0) + (i420 ? 4 : 0), 2.0 * B * L0 * (double)E * pl->K0,
+               px * (i420 ? 0.5 : (frag ? 1.0 : 4.0)) + (double)B * L0 * E * ((s.x16[0] ? 2.0 : 4.0) + (e1 ? 2.0 : 0.0)));
     KVQ_TRY_UNLESS(64, patch_embed_launch(&ea, range_of(0), st));
   } else {
     {

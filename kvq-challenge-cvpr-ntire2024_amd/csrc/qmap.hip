@@ -11,6 +11,7 @@
 // of this file differed from the numpy reference in the last bit), so the file is built with -ffp-contract=off (_build.EXTRA).  A
 // file-scope "#pragma clang fp contract(off)" is NOT enough: it does not reach the header's inlined functions (checked in the ISA).
 #include "common.hpp"
+#include "yuv.hpp"
 
 namespace kvq {
 
@@ -35,6 +36,8 @@ struct PaintParams {
   int n_ov, alpha, dim;
   int ov_depth[16];
   // kvq_quality_paint_regions only (the REGION instantiations): the token grid covers one window of the canvas per clip frame
+  int i420;                     // the overlay's frames are I420 (video[b] = the clip's first frame), converted with `yuv` (yuv.hpp)
+  YuvCoef yuv;
   const int32_t* region;        // [n_clips][T] window index, row-major over nry x nrx window origins
   int T, anchor, nry, nrx, phase;
 };
@@ -162,6 +165,8 @@ __global__ __launch_bounds__(QM_THREADS) void quality_overlay_kernel(PaintParams
   const float lo = p.range[0], inv = __fdiv_rn(1.f, __fsub_rn(p.range[1], lo));
   const uint8_t* vid = reinterpret_cast<const uint8_t*>(p.table ? p.table[b] : p.video[b]);
   const size_t frame = (size_t)(2 * d + (REGION ? p.phase : 0)) * p.Hs * p.Ws, hw = (size_t)p.Hs * p.Ws;
+  const I420Geom geo = i420_geom(p.Hs, p.Ws);
+  const uint8_t* yuv_frame = vid + (size_t)(2 * d + (REGION ? p.phase : 0)) * geo.frame;      // i420 only
   uint8_t* out = p.overlay + ((size_t)b * p.n_ov + ov) * 3 * hw;
   for (int item = threadIdx.x; item < rows * p.groups; item += QM_THREADS) {
     const int row = item / p.groups, g = item - row * p.groups;
@@ -187,7 +192,10 @@ __global__ __launch_bounds__(QM_THREADS) void quality_overlay_kernel(PaintParams
       uint8_t* o8 = out + (size_t)ch * hw + (size_t)y * p.Ws + x0;
       uint32_t px[4], packed = 0;
       const bool full = x0 + 4 <= p.Ws;
-      if (full && ((size_t)s8 & 3) == 0) {
+      if (p.i420) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = x0 + e < p.Ws ? (uint32_t)i420_pixel(yuv_frame, geo, p.yuv, ch, y, x0 + e) : 0u;
+      } else if (full && ((size_t)s8 & 3) == 0) {
         const uint32_t w = *reinterpret_cast<const uint32_t*>(s8);
 #pragma unroll
         for (int e = 0; e < 4; ++e) px[e] = (w >> (8 * e)) & 255u;
@@ -267,7 +275,11 @@ static int paint_run(const char* who, const KvqQualityPaintArgs* a, const KvqQua
   if (p.band > p.Ho) p.band = p.Ho;
   if (a->overlay) {
     KVQ_REQUIRE(a->range, KVQ_ERR_NULL, "%s: an overlay needs the value range", who);
-    KVQ_REQUIRE(f->src_is_u8, KVQ_ERR_UNSUPPORTED, "%s: the overlay is drawn on uint8 frames", who);
+    KVQ_REQUIRE(f->src_is_u8 >= KVQ_SRC_U8 && f->src_is_u8 <= KVQ_SRC_I420_BT709_FULL, KVQ_ERR_UNSUPPORTED,
+                "%s: the overlay is drawn on uint8 or I420 frames", who);
+    p.i420 = yuv_format_ok(f->src_is_u8);
+    KVQ_REQUIRE(!p.i420 || i420_size_ok(f->Hs, f->Ws), KVQ_ERR_SHAPE, "%s: I420 frames of %dx%d", who, f->Hs, f->Ws);
+    if (p.i420) p.yuv = yuv420_coeffs(f->src_is_u8);
     KVQ_REQUIRE(a->n_ov >= 1 && a->n_ov <= 16 && a->alpha >= 0 && a->alpha <= 256 && a->dim >= 0 && a->dim <= 256, KVQ_ERR_SHAPE,
                 "%s: n_ov %d (1..16), alpha %d, dim %d (0..256)", who, a->n_ov, a->alpha, a->dim);
     for (int n = 0; n < a->n_ov; ++n) {

@@ -204,6 +204,7 @@ extern "C" int kvq_resize_bilinear_aa(const void* video, int src_is_u8, int C, i
                                       int cx, int oh, int ow, int round_u8, const float* host_mean, const float* host_std,
                                       float* out, void* stream) {
   using namespace kvq;
+  KVQ_REQUIRE(src_is_u8 == KVQ_SRC_F32 || src_is_u8 == KVQ_SRC_U8, KVQ_ERR_UNSUPPORTED, "kvq_resize_bilinear_aa: frame type %d (convert I420 frames first: kvq_yuv420_to_rgb)", src_is_u8);
   KVQ_REQUIRE(video && out, KVQ_ERR_NULL, "kvq_resize_bilinear_aa: NULL pointer");
   KVQ_REQUIRE(C > 0 && C <= 4 && T > 0 && H > 0 && W > 0 && rh > 0 && rw > 0 && oh > 0 && ow > 0 && cy >= 0 && cx >= 0 &&
                   cy + oh <= rh && cx + ow <= rw,

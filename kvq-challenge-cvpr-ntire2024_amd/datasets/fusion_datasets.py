@@ -4,7 +4,9 @@
   UnifiedFrameSampler     (:612-660)  temporal index sampler (host integers, numpy)
   ViewDecompositionDataset_KVQ (:930-1051), ViewDecompositionDataset_add_forSimpleVQA (:786-927)
                           the reference's dataset classes under their own names (annotation parsing, samplers, dict
-                          keys), fed by a frame reader (decord if present, uint8 .npy stacks otherwise)
+                          keys), fed by a frame reader (Y4M files, decord if present, uint8 .npy stacks otherwise)
+  Y4mFrameReader          uncompressed YUV4MPEG2 video, no codec library: its I420 frames go to the device as they are
+                          (1.5 B/pixel) and are converted where the pixels are first touched (``kernels.I420Frames``)
   SyntheticKVQDataset     build-only: seeded post-decode frame stacks (no dataset/decoder is reachable
                           offline — SURVEY.md §8d); same dict keys.
 
@@ -40,8 +42,10 @@ def _grid(res: int, fragments: int, fsize: int):
 def get_spatial_fragments(video, fragments_h=7, fragments_w=7, fsize_h=32, fsize_w=32, aligned=32, nfrags=1,
                           random=False, random_upsample=False, fallback_type="upsample", rnd_h=None, rnd_w=None,
                           mean=None, std=None, lazy=False, **kwargs):
-    """video (C,T,H,W) uint8|fp32 on a HIP device -> fp32 (C,T,Fh*fs,Fw*fs); ``lazy=True`` -> the draws and the frames as a
-    one-entry ``kernels.FragmentSource`` (the trunk's embedding launch samples while it reads; ``.materialise()[0]`` is the tensor).
+    """video (C,T,H,W) uint8|fp32 on a HIP device, or ``kernels.I420Frames`` -> fp32 (C,T,Fh*fs,Fw*fs); ``lazy=True`` -> the draws and
+    the frames as a one-entry ``kernels.FragmentSource`` (the trunk's embedding launch samples while it reads; ``.materialise()[0]`` is
+    the tensor).  I420 frames stay I420 (the sampler converts the pixels it reads); only a source smaller than the canvas is converted
+    first, for the upsample.
 
     ``rnd_h``/``rnd_w`` (Fh,Fw,T//aligned): offsets inside each grid cell; drawn with the reference's
     ``torch.randint`` calls when omitted.  ``mean``/``std`` fuse the dataset's normalisation (:1017-1020)."""
@@ -60,7 +64,7 @@ def get_spatial_fragments(video, fragments_h=7, fragments_w=7, fsize_h=32, fsize
         # The reference upsamples the frames (F.interpolate(video / 255, scale_factor = 1 / ratio, bilinear) * 255, cast back,
         # :43-50) but keeps res_h / res_w of the ORIGINAL frames (:41) for the grid and the draws below: the patches are cut from
         # the upsampled frames at the small source's offsets.  Reproduced as it is; kvq_upsample_frames is ATen-CPU-exact.
-        video = kernels.upsample_frames(video.contiguous(), 1 / ratio)
+        video = kernels.upsample_frames(_rgb_frames(video).contiguous(), 1 / ratio)
     assert T % aligned == 0, "Please provide match vclip and align index"
     nt = T // aligned
     hl, wl = H // fragments_h, W // fragments_w
@@ -83,6 +87,11 @@ def get_spatial_fragments(video, fragments_h=7, fragments_w=7, fsize_h=32, fsize
                                    fragments_w, fsize_h, fsize_w, aligned, mean=mean, std=std)
 
 
+def _rgb_frames(video):
+    """whole-frame consumers (the resize views, the upsample fallback) read RGB: I420 frames are converted once (cached)"""
+    return video.to_rgb() if isinstance(video, kernels.I420Frames) else video
+
+
 def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=False, mean=None, std=None, antialias=False,
                       **kwargs):
     """Reference ``get_resized_video`` (:244-252) on the GPU: (C,T,H,W) -> (C,T,size_h,size_w), bilinear; ``antialias``:
@@ -95,7 +104,7 @@ def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=Fals
             size_h = int(ratio * size_w)
         elif ratio < 1:
             size_w = int(size_h / ratio)
-    return kernels.resize_bilinear(video.contiguous(), size_h, size_w, mean=mean, std=std, antialias=antialias)
+    return kernels.resize_bilinear(_rgb_frames(video).contiguous(), size_h, size_w, mean=mean, std=std, antialias=antialias)
 
 
 def get_resizecrop_video(video, resize=520, crop=448, phase="test", mean=None, std=None, antialias=False, **kwargs):
@@ -105,7 +114,7 @@ def get_resizecrop_video(video, resize=520, crop=448, phase="test", mean=None, s
         raise NotImplementedError("random crop is a training augmentation")
     o = resize // 2 - crop // 2
     n = (resize // 2 + crop // 2) - o
-    return kernels.resize_bilinear(video.contiguous(), resize, resize, crop=(o, o, n, n), mean=mean, std=std,
+    return kernels.resize_bilinear(_rgb_frames(video).contiguous(), resize, resize, crop=(o, o, n, n), mean=mean, std=std,
                                    antialias=antialias)
 
 
@@ -306,11 +315,102 @@ class Cv2FrameReader:
         np.take(self.frames, np.asarray(indices, np.int64), axis=0, out=out)
 
 
-def open_video(path):
-    """Frame reader for ``path``: ``<path>`` itself or ``<path>.npy`` as a frame stack (this build's decode-free entry), else
+def yuv420_to_rgb_host(y, u, v, coeffs):
+    """The library's YUV 4:2:0 -> RGB conversion in numpy (include/kvq_hip.h: kvq_yuv420_to_rgb; ``coeffs`` =
+    ``kernels.yuv420_coeffs(format)``): planes y (H, W), u / v (ceil(H/2), ceil(W/2)) uint8 -> uint8 (H, W, 3)."""
+    qy, qrv, qgu, qgv, qbu, yoff = (np.int32(c) for c in coeffs)
+    H, W = y.shape
+    up = lambda c: np.repeat(np.repeat(np.asarray(c, np.int32) - 128, 2, axis=0), 2, axis=1)[:H, :W]     # noqa: E731  nearest chroma
+    uu, vv = up(u), up(v)
+    luma = qy * (np.asarray(y, np.int32) - yoff) + np.int32(32768)
+    rgb = np.stack([luma + qrv * vv, luma + qgu * uu + qgv * vv, luma + qbu * uu], axis=-1) >> 16
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+class Y4mFrameReader:
+    """An uncompressed YUV4MPEG2 (``.y4m``) file as a frame reader — no codec library.  8-bit 4:2:0 only (``C420``, ``C420jpeg``,
+    ``C420mpeg2``, ``C420paldv``, or no ``C`` tag: the format's default); any other chroma tag is a ValueError naming it.
+    ``XCOLORRANGE=FULL`` selects full range, ``matrix`` (``bt601`` | ``bt709``; the container does not say) the coefficients.
+    The frames are found by a fixed stride: every ``FRAME`` line must equal the first, and the file must end with a whole frame.
+
+    ``len(reader)`` frames; ``reader[i]`` -> uint8 RGB (H, W, 3) by the library's conversion on the host (generic consumers);
+    ``read_i420_into(indices, out)`` -> the frames' payload bytes, Y | U | V, which is the device layout of ``kernels.I420Frames``."""
+    CHROMA = ("420", "420jpeg", "420mpeg2", "420paldv")
+
+    def __init__(self, path, matrix="bt601"):
+        from .._abi import i420_format
+        with open(path, "rb") as f:                      # two lines, however long the X tags make them
+            line = f.readline(1 << 20)
+            first = f.readline(1 << 20)
+        end = len(line) - 1                              # offset of the stream header's newline
+        tags = line[:end].split(b" ") if line.endswith(b"\n") else []
+        if not tags or tags[0] != b"YUV4MPEG2":
+            raise ValueError(f"{path}: not a YUV4MPEG2 stream (no 'YUV4MPEG2' signature line)")
+        self.W = self.H = self.fps = None                # fps: the F tag's rate (frames per second), None when absent or 0:0
+        full = False
+        for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
+            if tag[0] in "WH":
+                if not tag[1:].isdigit():
+                    raise ValueError(f"{path}: malformed frame size tag {tag!r} in the stream header")
+                setattr(self, tag[0], int(tag[1:]))
+            elif tag[0] == "F":
+                num, _, den = tag[1:].partition(":")
+                if not (num.isdigit() and den.isdigit()):
+                    raise ValueError(f"{path}: malformed frame rate tag {tag!r} in the stream header")
+                self.fps = int(num) / int(den) if int(num) and int(den) else None
+            elif tag[0] == "C" and tag[1:] not in self.CHROMA:
+                raise ValueError(f"{path}: chroma format {tag!r} is not supported (8-bit 4:2:0 only: " + ", ".join("C" + c for c in self.CHROMA) + ")")
+            elif tag == "XCOLORRANGE=FULL":
+                full = True
+        if not self.W or not self.H:
+            raise ValueError(f"{path}: the stream header gives no frame size (W / H tags)")
+        self.format = i420_format(matrix, full)
+        self.frame_bytes = kernels.i420_frame_bytes(self.H, self.W)
+        size = os.path.getsize(path)
+        if not ((first == b"FRAME\n" or first.startswith(b"FRAME ")) and first.endswith(b"\n")):
+            raise ValueError(f"{path}: no FRAME header after the stream header" if size > end + 1 else f"{path}: the file holds no frame")
+        stride = len(first) + self.frame_bytes
+        n, rest = divmod(size - (end + 1), stride)
+        if n == 0 or rest:
+            raise ValueError(f"{path}: truncated — {size - (end + 1)} bytes after the stream header are not a whole number of "
+                             f"{self.W}x{self.H} 4:2:0 frames of {stride} bytes ({n} whole, {rest} bytes left)")
+        body = np.memmap(path, dtype=np.uint8, mode="r", offset=end + 1, shape=(n, stride))
+        bad = np.nonzero((body[:, :len(first)] != np.frombuffer(first, np.uint8)).any(axis=1))[0]
+        if bad.size:
+            raise ValueError(f"{path}: frame {int(bad[0])} does not start with the FRAME header of frame 0 ({first!r}): frames are "
+                             "found by a fixed stride")
+        self.payload = body[:, len(first):]              # (n, frame_bytes) view of the mapped file
+        self._coeffs = None
+
+    def __len__(self):
+        return self.payload.shape[0]
+
+    def planes(self, i):
+        """frame i as its (Y, U, V) planes: views of the mapped file"""
+        H, W = self.H, self.W
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        p = self.payload[int(i)]
+        return p[:H * W].reshape(H, W), p[H * W:H * W + ch * cw].reshape(ch, cw), p[H * W + ch * cw:].reshape(ch, cw)
+
+    def __getitem__(self, i):
+        if self._coeffs is None:
+            self._coeffs = kernels.yuv420_coeffs(self.format)
+        return yuv420_to_rgb_host(*self.planes(i), self._coeffs)
+
+    def read_i420_into(self, indices, out):
+        """payload[indices] -> out (len(indices), frame_bytes) uint8: one copy per frame straight from the mapped file"""
+        for j, i in enumerate(indices):
+            out[j] = self.payload[int(i)]
+
+
+def open_video(path, yuv_matrix="bt601"):
+    """Frame reader for ``path``: a ``*.y4m`` file by ``Y4mFrameReader`` (``yuv_matrix``: its conversion matrix); ``<path>`` itself or
+    ``<path>.npy`` as a frame stack (this build's decode-free entries), else
     decord.VideoReader (fusion_datasets.py:381-383), else — decord missing, or failing on this file: the reference wraps the decord
     branch in a bare ``try`` — the OpenCV fallback (:398-431, ``Cv2FrameReader``)."""
     import os
+    if path.endswith(".y4m") and (os.path.exists(path) or not os.path.exists(path + ".npy")):      # a missing file with a decoded
+        return Y4mFrameReader(path, yuv_matrix)                                                    # .npy beside its name: the stack
     if path.endswith(".npy"):
         return NpyFrameReader(path)
     if os.path.exists(path + ".npy"):
@@ -326,7 +426,7 @@ def open_video(path):
     except ImportError as e:
         raise ImportError(f"cannot read {path}: video decode needs decord or OpenCV (neither is part of this image: SURVEY.md §8 f2; "
                           f"decord: {type(decord_error).__name__}: {decord_error}) — or provide the decoded frames as a uint8 "
-                          f"[T,H,W,3] array in {path}.npy") from e
+                          f"[T,H,W,3] array in {path}.npy, or the video as an uncompressed .y4m file") from e
 
 
 class _Staging:
@@ -352,22 +452,29 @@ _COPY_THREADS = 4
 
 def _frames_to_device(vr, uniq, device):
     """The sampled frames ``uniq`` of a reader -> ONE uint8 (n, H, W, 3) device tensor: gathered into pinned staging memory
-    by a few host threads (numpy copies release the GIL), then a single asynchronous H2D copy on the current stream."""
+    by a few host threads (numpy copies release the GIL), then a single asynchronous H2D copy on the current stream.
+    A reader of I420 frames (``read_i420_into``: ``Y4mFrameReader``) stages its payload as it is — 1.5 B/pixel through the gather
+    and the copy instead of 3 — and the result is a ``kernels.I420Frames`` (n, frame_bytes)."""
     global _COPY_POOL
-    first = vr[int(uniq[0])]
-    first = first.asnumpy() if hasattr(first, "asnumpy") else np.asarray(first)
-    n, shape = len(uniq), tuple(first.shape)
+    i420 = hasattr(vr, "read_i420_into")
+    if i420:
+        first, read = None, vr.read_i420_into
+        n, shape = len(uniq), (vr.frame_bytes,)
+    else:
+        first = vr[int(uniq[0])]
+        first = first.asnumpy() if hasattr(first, "asnumpy") else np.asarray(first)
+        n, shape, read = len(uniq), tuple(first.shape), getattr(vr, "read_into", None)
     nbytes = n * int(np.prod(shape))
     st, k = _Staging.get(nbytes)
     stage = st["buf"][k][:nbytes].view((n,) + shape)
     host = stage.numpy()
-    if hasattr(vr, "read_into"):
+    if read is not None:
         if _COPY_POOL is None:
             from concurrent.futures import ThreadPoolExecutor
             _COPY_POOL = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix="kvq-copy")
         nt = max(1, min(_COPY_THREADS, n // 8))
         bounds = np.linspace(0, n, nt + 1).astype(int)
-        jobs = [_COPY_POOL.submit(vr.read_into, uniq[a:b], host[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+        jobs = [_COPY_POOL.submit(read, uniq[a:b], host[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
         for j in jobs:
             j.result()
     elif hasattr(vr, "get_batch"):                      # decord: one decode call for all frames
@@ -382,21 +489,22 @@ def _frames_to_device(vr, uniq, device):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev.device))
         st["ev"][k] = ev
-    return dev
+    return kernels.I420Frames(dev, vr.H, vr.W, vr.format) if i420 else dev
 
 
-def _sampled_clips(path, samplers, is_train, device):
+def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601"):
     """Reference ``spatial_temporal_view_decomposition`` (:376-397), decode half: one reader, every frame fetched once and
     sent to the device once, as uint8; per view a uint8 (3, T, H, W) device tensor (frame gather + layout change in HBM) +
-    the sampled indices."""
-    vr = open_video(path)
+    the sampled indices.  I420 frames (a ``.y4m`` file): per view a ``kernels.I420Frames`` — a gather of whole frames, no
+    layout change and no conversion here."""
+    vr = open_video(path, yuv_matrix)
     frame_inds = {k: s(len(vr), is_train) for k, s in samplers.items()}
     uniq = np.unique(np.concatenate(list(frame_inds.values()), 0))
     frames = _frames_to_device(vr, uniq, device)                               # (n, H, W, 3) uint8
     video = {}
     for k, inds in frame_inds.items():
         pos = torch.from_numpy(np.searchsorted(uniq, inds).astype(np.int64)).to(frames.device)
-        video[k] = frames.index_select(0, pos).permute(3, 0, 1, 2).contiguous()
+        video[k] = frames.select(pos) if isinstance(frames, kernels.I420Frames) else frames.index_select(0, pos).permute(3, 0, 1, 2).contiguous()
     return video, frame_inds
 
 
@@ -467,7 +575,7 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
     def __getitem__(self, index):
         info = self.video_infos[index]
         feat = self._features(info["video_name"])
-        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device)
+        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"))
         data = {}
         for stype, sopt in self.sample_types.items():
             kw = dict(sopt, phase="test")
@@ -521,7 +629,13 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
 
     def __getitem__(self, index):
         info = self.video_infos[index]
-        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device)
+        if self.opt.get("seed_per_item"):
+            # as SyntheticKVQDataset: the samplers draw from the process-global RNGs; seeded per item, item i is the same whatever
+            # was built before it (two runs over two trees of the same videos then draw the same frames and offsets)
+            np.random.seed(1234 + index)
+            _pyrandom.seed(1234 + index)
+            torch.manual_seed(1234 + index)
+        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"))
         data, k = {}, None
         resize = ori = None
         for stype, sopt in self.sample_types.items():       # order of the reference's three calls per view (:455-459)

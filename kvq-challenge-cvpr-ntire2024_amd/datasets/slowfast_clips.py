@@ -66,10 +66,12 @@ def read_video_names(videos_csv: str) -> List[str]:
 
 
 def frame_rate_of(reader, path: str, default_fps: Optional[float]) -> int:
-    """``int(round(cap.get(CAP_PROP_FPS)))`` (:64): from the decoder when it knows it, else ``<video>.fps`` (one number) beside
+    """``int(round(cap.get(CAP_PROP_FPS)))`` (:64): from the decoder / the container when it knows it, else ``<video>.fps`` (one number) beside
     a frame stack, else ``default_fps``."""
     if hasattr(reader, "get_avg_fps"):
         return int(round(float(reader.get_avg_fps())))
+    if getattr(reader, "fps", None):                     # a container that carries its rate (Y4mFrameReader: the F tag)
+        return int(round(float(reader.fps)))
     for side in (path + ".fps", os.path.splitext(path)[0] + ".fps"):
         if os.path.exists(side):
             return int(round(float(open(side).read().strip())))

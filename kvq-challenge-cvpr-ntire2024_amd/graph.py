@@ -29,11 +29,12 @@ def _slot_ok(v) -> bool:
 
 def _signature(inputs: Dict[str, torch.Tensor]) -> Tuple:
     """what a recording is valid for: tensor shapes / dtypes; for a lazily sampled batch also everything the embedding launch bakes
-    into its parameters — sampler geometry, source frame shape / stride / dtype and the normalisation constants — and whether
+    into its parameters — sampler geometry, source frame shape / stride / dtype / format (uint8 planes or one of the I420 formats)
+    and the normalisation constants — and whether
     the frames are the sampler's upsample of a smaller source (a forward that paints quality maps decides on it while it is recorded)"""
     def lazy_part(v):
         v0 = v.videos[0]
-        return (v.geometry, tuple(v0.shape), v0.stride(0), v0.dtype, None if v.mean is None else tuple(v.mean),
+        return (v.geometry, tuple(v0.shape), v.frame_stride, v0.dtype, v.frame_format, None if v.mean is None else tuple(v.mean),
                 None if v.std is None else tuple(v.std), bool(getattr(v, "upsampled", False)))
     return tuple((k, tuple(v.shape), v.dtype) + (lazy_part(v) if _is_lazy(v) else ()) for k, v in sorted(inputs.items()))
 

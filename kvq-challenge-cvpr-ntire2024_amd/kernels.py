@@ -255,9 +255,87 @@ def simple_vqa_head(feat: torch.Tensor, w1, b1, w2, b2):
     return score.reshape(B, 1)
 
 
-def fragment_gather(video: torch.Tensor, hoff: torch.Tensor, woff: torch.Tensor, fragments_h, fragments_w,
+def i420_frame_bytes(H: int, W: int) -> int:
+    """bytes of one I420 frame: Y (H x W) | U | V (ceil(H/2) x ceil(W/2) each)"""
+    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+
+
+def yuv420_coeffs(fmt: int):
+    """(qy, qrv, qgu, qgv, qbu, yoff): the integers of the library's YUV -> RGB conversion for an ``_abi.SRC_I420_*`` format
+    (``kvq_yuv420_coeffs``, host only)"""
+    out = (C.c_int32 * 6)()
+    check(lib().kvq_yuv420_coeffs(int(fmt), C.byref(out)), "kvq_yuv420_coeffs")
+    return tuple(out)
+
+
+class I420Frames:
+    """T planar YUV 4:2:0 frames on the device, "I420, frame-major": ``data`` uint8 (T, frame_bytes), every row one frame
+    Y | U | V (``i420_frame_bytes``), rows back to back — what a decoder hands over, 1.5 B/pixel.  ``fmt``: an
+    ``_abi.SRC_I420_*`` value (matrix and range).  Stands where a uint8 (3,T,H,W) frame tensor stands: the fragment sampler
+    (``fragment_gather``, ``FragmentSource`` and through it the fused embedding read and the quality paint) reads it as it is
+    and converts the pixels it touches; consumers of whole frames take ``to_rgb()``.  Bit-equal either way: one conversion."""
+
+    dtype = torch.uint8
+
+    def __init__(self, data: torch.Tensor, H: int, W: int, fmt: int):
+        H, W, fmt = int(H), int(W), int(fmt)
+        if fmt not in _abi.I420_FORMATS:
+            raise ValueError(f"I420Frames: format {fmt} is not one of _abi.I420_FORMATS")
+        fb = i420_frame_bytes(H, W)
+        if not (data.dtype == torch.uint8 and data.dim() == 2 and data.shape[0] > 0 and data.shape[1] == fb and data.stride(1) == 1
+                and (data.shape[0] == 1 or data.stride(0) == fb)):
+            raise ValueError(f"I420Frames: expected uint8 (T, {fb}) with the frames back to back, got {data.dtype} {tuple(data.shape)} "
+                             f"strides {data.stride()}")
+        self.data, self.H, self.W, self.format = data, H, W, fmt
+        self.shape = (3, data.shape[0], H, W)
+        self.device, self.is_cuda = data.device, data.is_cuda
+        self._rgb = None
+
+    def data_ptr(self):
+        return self.data.data_ptr()
+
+    def contiguous(self):
+        return self
+
+    def is_contiguous(self):
+        return True
+
+    def record_stream(self, stream):
+        self.data.record_stream(stream)
+        if self._rgb is not None:
+            self._rgb.record_stream(stream)
+
+    def to(self, device, non_blocking=False):
+        d = self.data.to(device, non_blocking=non_blocking)
+        return self if d is self.data else I420Frames(d, self.H, self.W, self.format)
+
+    def frames(self, lo: int, hi: int) -> "I420Frames":
+        """frames lo .. hi-1 as a view: a run of frames of a longer video is still one pointer"""
+        return I420Frames(self.data[lo:hi], self.H, self.W, self.format)
+
+    def select(self, index: torch.Tensor) -> "I420Frames":
+        """the frames ``index`` (int64, on the device) names, in that order, as new storage (one row gather)"""
+        return I420Frames(self.data.index_select(0, index), self.H, self.W, self.format)
+
+    def to_rgb(self) -> torch.Tensor:
+        """uint8 (3,T,H,W): ``kvq_yuv420_to_rgb``, one launch, converted once and kept"""
+        if self._rgb is None:
+            _need_gpu(self.data)
+            _, T, H, W = self.shape
+            out = torch.empty(3, T, H, W, dtype=torch.uint8, device=self.device)
+            check(lib().kvq_yuv420_to_rgb(ptr(self.data), T, H, W, self.format, ptr(out), stream_of(self.data)), "kvq_yuv420_to_rgb")
+            self._rgb = out
+        return self._rgb
+
+
+def _frame_format(v) -> int:
+    """KvqSrcFormat of a frame tensor / ``I420Frames``"""
+    return v.format if isinstance(v, I420Frames) else int(v.dtype == torch.uint8)
+
+
+def fragment_gather(video, hoff: torch.Tensor, woff: torch.Tensor, fragments_h, fragments_w,
                     fsize_h, fsize_w, aligned, mean=None, std=None, out=None):
-    """video uint8/fp32 (C,T,H,W) on device; hoff/woff int32 (Fh,Fw,T//aligned) ABSOLUTE patch origins.
+    """video uint8/fp32 (C,T,H,W) on device, or ``I420Frames``; hoff/woff int32 (Fh,Fw,T//aligned) ABSOLUTE patch origins.
     ``out``: optional fp32 (C,T,Fh*fs,Fw*fs) destination (e.g. one clip of a batch tensor) — no allocation, no copy."""
     _need_gpu(video, hoff, woff)
     assert video.dtype in (torch.uint8, torch.float32) and video.is_contiguous()
@@ -270,7 +348,7 @@ def fragment_gather(video: torch.Tensor, hoff: torch.Tensor, woff: torch.Tensor,
     m = (C.c_float * Cc)(*mean) if mean is not None else None
     s = (C.c_float * Cc)(*std) if std is not None else None
     hoff, woff = hoff.contiguous(), woff.contiguous()
-    check(lib().kvq_fragment_gather(ptr(video), int(video.dtype == torch.uint8), Cc, T, H, W, ptr(hoff), ptr(woff),
+    check(lib().kvq_fragment_gather(ptr(video), _frame_format(video), Cc, T, H, W, ptr(hoff), ptr(woff),
                                     fragments_h, fragments_w, fsize_h, fsize_w, aligned, m, s, ptr(out),
                                     stream_of(video)), "kvq_fragment_gather")
     return out
@@ -283,7 +361,8 @@ class FragmentSource:
     consumers that want the tensor.  Bit-identical either way.
 
     videos: uint8 (C,T,Hs,Ws) device tensors of one shape — contiguous, or runs of frames of a longer video (frames
-    contiguous, one common channel stride: what ``split_clips`` makes); hoffs / woffs: int32 (Fh,Fw,T//aligned) device tensors
+    contiguous, one common channel stride: what ``split_clips`` makes) — or ``I420Frames`` of one frame size and format (YUV
+    4:2:0 as the decoder left it: the pixels a launch touches are converted in its registers); hoffs / woffs: int32 (Fh,Fw,T//aligned) device tensors
     of ABSOLUTE patch origins (as ``fragment_gather``)."""
 
     def __init__(self, videos, hoffs, woffs, fragments_h, fragments_w, fsize_h, fsize_w, aligned, mean=None, std=None):
@@ -293,9 +372,13 @@ class FragmentSource:
         v0 = videos[0]
         Cc, T, Hs, Ws = v0.shape
         nt = T // aligned
+        # frame_format: KvqSrcFormat; frame_stride: elements between the channel planes (0 for I420: there are none)
+        self.frame_format = _frame_format(v0)
+        self.frame_stride = 0 if isinstance(v0, I420Frames) else v0.stride(0)
         for v, h, w in zip(videos, hoffs, woffs):
-            assert v.shape == v0.shape and v.dtype == v0.dtype and v.device == v0.device
-            assert v.stride()[1:] == (Hs * Ws, Ws, 1) and v.stride(0) == v0.stride(0) >= T * Hs * Ws, "frames must be contiguous"
+            assert v.shape == v0.shape and v.dtype == v0.dtype and v.device == v0.device and _frame_format(v) == self.frame_format
+            if not isinstance(v0, I420Frames):
+                assert v.stride()[1:] == (Hs * Ws, Ws, 1) and v.stride(0) == v0.stride(0) >= T * Hs * Ws, "frames must be contiguous"
             assert h.dtype == w.dtype == torch.int32 and tuple(h.shape) == tuple(w.shape) == (fragments_h, fragments_w, nt)
         assert (mean is None) == (std is None)
         self.videos, self.hoffs, self.woffs = videos, hoffs, woffs
@@ -330,7 +413,7 @@ class FragmentSource:
         vs, hs, ws = [], [], []
         for v, h, w in zip(self.videos, self.hoffs, self.woffs):
             for k in range(num_clips):
-                vs.append(v[:, k * t:(k + 1) * t])
+                vs.append(v.frames(k * t, (k + 1) * t) if isinstance(v, I420Frames) else v[:, k * t:(k + 1) * t])
                 hs.append(h[:, :, k * nt:(k + 1) * nt])
                 ws.append(w[:, :, k * nt:(k + 1) * nt])
         out = FragmentSource(vs, hs, ws, *self.geometry, mean=self.mean, std=self.std)
@@ -352,8 +435,8 @@ class FragmentSource:
         f = _abi.KvqFragmentSource()
         for i, (v, h, w) in enumerate(zip(self.videos, self.hoffs, self.woffs)):
             f.video[i], f.hoff[i], f.woff[i] = ptr(v), ptr(h), ptr(w)
-        f.chan_stride = v0.stride(0)
-        f.n_clips, f.src_is_u8, f.Hs, f.Ws = len(self.videos), int(v0.dtype == torch.uint8), v0.shape[2], v0.shape[3]
+        f.chan_stride = self.frame_stride
+        f.n_clips, f.src_is_u8, f.Hs, f.Ws = len(self.videos), self.frame_format, v0.shape[2], v0.shape[3]
         f.Fh, f.Fw, f.fs_h, f.fs_w, f.aligned = self.geometry
         f.normalise = int(self.mean is not None)
         if self.mean is not None:
@@ -398,23 +481,25 @@ class FragmentSlot(FragmentSource):
 
     def __init__(self, source: FragmentSource):
         if not (type(source) is FragmentSource and source.c_struct() is not None):
-            raise ValueError("FragmentSlot: uint8 frames, at most 16 clips")
+            raise ValueError("FragmentSlot: uint8 or I420 frames, at most 16 clips")
         self.geometry, self.mean, self.std = source.geometry, source.mean, source.std
         self.device, self.is_cuda, self.dtype, self.shape = source.device, True, source.dtype, source.shape
-        self._frame_shape, self._frame_stride = tuple(source.videos[0].shape), source.videos[0].stride(0)
+        self._frame_shape, self._frame_stride, self.frame_format = tuple(source.videos[0].shape), source.frame_stride, source.frame_format
+        self.frame_stride = self._frame_stride
         self.upsampled = source.upsampled
         self.table = torch.zeros(3 * _abi.FRAG_MAX_CLIPS, dtype=torch.int64, device=self.device)
         self._c = None
         self.load(source)
 
     def load(self, source: FragmentSource):
-        """point the slot at ``source`` (same geometry, frame shape and normalisation), in stream order"""
+        """point the slot at ``source`` (same geometry, frame shape, frame format and normalisation), in stream order"""
         if not (source.geometry == self.geometry and source.shape == self.shape and source.mean == self.mean and source.std == self.std
-                and tuple(source.videos[0].shape) == self._frame_shape and source.videos[0].stride(0) == self._frame_stride
-                and source.videos[0].dtype == torch.uint8 and source.upsampled == self.upsampled):
+                and tuple(source.videos[0].shape) == self._frame_shape and source.frame_stride == self._frame_stride
+                and source.frame_format == self.frame_format and source.upsampled == self.upsampled):
             # a real exception (not an assert: python -O must not replay a graph recorded with other constants)
-            raise ValueError("FragmentSlot.load: a slot serves one sampler geometry, frame shape / stride, uint8 frames and one "
-                             f"normalisation; got geometry {source.geometry} frames {tuple(source.videos[0].shape)} {source.videos[0].dtype}")
+            raise ValueError("FragmentSlot.load: a slot serves one sampler geometry, frame shape / stride, frame format and one "
+                             f"normalisation; got geometry {source.geometry} frames {tuple(source.videos[0].shape)} {source.videos[0].dtype} "
+                             f"format {source.frame_format} (the slot's: {self.frame_format})")
         self.table.copy_(source.pointer_table(), non_blocking=True)
         self.current = source                      # keeps the frames alive while the table names them
         self.videos, self.hoffs, self.woffs = source.videos, source.hoffs, source.woffs
@@ -437,7 +522,7 @@ class FragmentSlot(FragmentSource):
         if self._c is None:
             f = _abi.KvqFragmentSource()
             f.chan_stride = self._frame_stride
-            f.n_clips, f.src_is_u8, f.Hs, f.Ws = self.shape[0], 1, self._frame_shape[2], self._frame_shape[3]
+            f.n_clips, f.src_is_u8, f.Hs, f.Ws = self.shape[0], self.frame_format, self._frame_shape[2], self._frame_shape[3]
             f.Fh, f.Fw, f.fs_h, f.fs_w, f.aligned = self.geometry
             f.normalise = int(self.mean is not None)
             if self.mean is not None:

@@ -589,6 +589,8 @@ class SwinTransformer3D(nn.Module):
             elif kind == "embed":
                 sym = (f"patch_embed_kernel<{ename}, {self.embed_dim // 32}, 6, {str(bool(r.variant & 1)).lower()}, "
                        f"{str(bool(r.variant & 2)).lower()}>")          # ..., + norm1 of block 0, reads through the sampler
+                if r.variant & 4:                                       # ... out of I420 frames
+                    sym = f"patch_embed_i420_kernel<{ename}, {self.embed_dim // 32}, 6, {str(bool(r.variant & 1)).lower()}>"
             elif kind == "merge":
                 sym = f"patch_merge_kernel<{ename}, {str(bool(r.variant)).lower()}>"
             elif kind == "tail":
