@@ -467,7 +467,16 @@ int kvq_window_attention(const uint16_t* qkv, const int32_t* tok, const float* r
  *     separates the two halves of 196 tokens — so a q-block of one half passes over the 32-key blocks of the other half, whose scores
  *     are the image's -100 and leave the exponential as zeros (46 % fewer score blocks in those windows).  First-half rows come out bit
  *     for bit as with dsplit_from = -1; second-half rows start their running maximum at another block and may differ in the last bit of
- *     the 16-bit output.  The caller vouches for the geometry (the plan derives it from the window layout). */
+ *     the 16-bit output.  The caller vouches for the geometry (the plan derives it from the window layout).
+ *   - key ranges (kvq_window_attention32_ranges; shifted, un-padded partitions): the shift mask separates up to eight regions of a window
+ *     that is last along an axis.  With the window's rows stored SORTED BY REGION (kvq_attn32_row_order: attention does not depend on the
+ *     order of a window's rows as long as q, k, v, the image and the output rows share it) every region is one run of rows, and a 32-query
+ *     block needs one contiguous range of 32-key blocks.  `ranges` (device, uint8 [nW][13][2], window w of every clip) holds the first
+ *     and last such block per q-block; kvq_attn32_key_ranges derives it from the descriptors of the rows as stored, so no needed block
+ *     can be passed over whatever the layout — nobody vouches for a geometry.  The kernel widens a range outward to the nearest length
+ *     it holds a body for (4, 7 or 13 blocks; the added blocks are masked or padding ones) and passes over the rest exactly as
+ *     dsplit_from does: the depth split is one case of it.  Rows whose range starts at block 0 come out bit for bit as from
+ *     kvq_window_attention32; the others may differ in the last bit.  Excludes dsplit_from and pad_mask. */
 size_t kvq_attn_bias32_bytes(int n_types, int N, int num_heads);      /* 0 for N > 400 */
 int kvq_attn_bias32_build(const int32_t* tok, const float* rpb, const float* fpb, int table_len, int center,
                           int n_types, int N, int num_heads, int use_mask, void* out, float* max_abs, void* stream);
@@ -495,6 +504,14 @@ typedef struct {
   const uint32_t* pad_mask;
 } KvqAttnDenseArgs;
 int kvq_window_attention32(const KvqAttnDenseArgs* host_args, void* stream);
+int kvq_window_attention32_ranges(const KvqAttnDenseArgs* host_args, const uint8_t* ranges, void* stream);
+/* Host functions (host pointers, no launch).  tok_host: descriptors [n_windows*N][2] as kvq_window_attention takes them.
+ *   kvq_attn32_row_order: order[w*N + i] = the index n of the row of window w that the region order stores at position i (a stable sort
+ *     of the rows by the region byte of their descriptor: a permutation of 0..N-1 per window, regions contiguous).
+ *   kvq_attn32_key_ranges: ranges[w][qb] = {first, last} 32-key block holding a key < N that at least one valid query row of q-block qb
+ *     is not masked against (use_mask = 0: every key < N), for the rows in the order tok_host lists them; N <= 400. */
+int kvq_attn32_row_order(const int32_t* tok_host, int n_windows, int N, int32_t* order);
+int kvq_attn32_key_ranges(const int32_t* tok_host, int n_windows, int N, int use_mask, uint8_t* ranges);
 
 /* im2col of PatchEmbed3D's stride==kernel Conv3d (swin_backbone.py:715-726): zero pads the tail
  * of each axis, emits bf16 rows [B*D*H'*W'][in*pd*ph*pw] in (c,kd,kh,kw) order. */

@@ -234,6 +234,9 @@ SYMBOLS = {
     "kvq_attn_bias32_bytes": (sz, [i32, i32, i32]),
     "kvq_attn_bias32_build": (i32, [p_void, p_void, p_void, i32, i32, i32, i32, i32, i32, p_void, p_void, p_void]),
     "kvq_window_attention32": (i32, [C.POINTER(KvqAttnDenseArgs), p_void]),
+    "kvq_window_attention32_ranges": (i32, [C.POINTER(KvqAttnDenseArgs), p_void, p_void]),
+    "kvq_attn32_row_order": (i32, [p_void, i32, i32, p_void]),
+    "kvq_attn32_key_ranges": (i32, [p_void, i32, i32, i32, p_void]),
     "kvq_swin3d_bias_dense_bytes": (sz, [p_void, i32]),
     "kvq_swin3d_bias_dense_build": (i32, [p_void, i32, p_void, p_void, p_void, p_void, p_void]),
     "kvq_patch_im2col": (i32, [p_void, i32, i32, i32, i32, i32, i32, i32, i32, i32, p_void, p_void]),

@@ -80,8 +80,10 @@ __device__ __forceinline__ float a32_pair_sum(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// One 32-query block against the key blocks [T0, T1) of the LDS images at `slot`.  Compile-time range: the score / probability /
-// bias registers rotate through statically indexed sets.
+// One 32-query block against the LEN key blocks [t0, t0 + LEN) of the LDS images at `slot`.  Compile-time LENGTH: the score / probability /
+// bias registers rotate through statically indexed sets (by t - t0); the first block `t0` may be a run-time value — it only offsets the K
+// fragment base, the V transpose-read base and the bias tile pointer.  LAST: the range ends at block 12, the one block whose handling is
+// tied to its absolute index (rows 400..415 from the zero block, the SHORT registers, the two V fragments nobody reads); t0 is then 13 - LEN.
 // SHORT (round 6; N = 385..392, i.e. the (8,7,7) window): the 13th key block holds 8 valid keys, and they are registers 0..3 of both lane halves
 // (key = 384 + (r & 3) + 8 (r >> 2) + 4 hi) — its bias widening, row maximum, exponentials, packs and row sums run on those four registers only
 // (16 of the block's 56 VALU instructions; the MFMAs are whole tiles either way).  A KERNEL-level template argument: a launch holds one form of
@@ -117,23 +119,25 @@ __device__ __forceinline__ void a32_finish(const f32x16& O, float ls, uint16_t* 
   }
 }
 
-template <typename E, int T0, int T1, bool SHORT = false>
-__device__ __forceinline__ void a32_qblock(const unsigned char* slot, const int zero, const u32x4* bd, const typename E::v8 qf0,
+template <typename E, int LEN, bool LAST, bool SHORT = false>
+__device__ __forceinline__ void a32_qblock(const unsigned char* slot, const int zero, const u32x4* bd0, const int t0, const typename E::v8 qf0,
                                            const typename E::v8 qf1, const u32x4 (&pre)[2], uint16_t* orow, const bool store) {
   using V8 = typename E::v8;
-  static_assert(T0 >= 0 && T0 < T1 && T1 <= A32_KB, "key block range");
+  static_assert(LEN >= 1 && LEN <= A32_KB && (LAST || LEN < A32_KB) && (LAST || !SHORT), "key block range");
+  constexpr int T0 = 0, T1 = LEN;                    // t below counts from the range's first block
   const int lane = threadIdx.x & 63, q = lane & 31, hi = lane >> 5;
   const float kLog2e = 1.4426950408889634f;
   const int sw = (q >> 2) & 3;
   const u32x4* Ks = reinterpret_cast<const u32x4*>(slot);
-  const int ka0 = q * 4 + (hi ^ sw), ka1 = q * 4 + ((2 + hi) ^ sw);          // + 128 per key block
+  const u32x4* bd = bd0 + t0 * 128;
+  const int ka0 = q * 4 + (hi ^ sw) + t0 * 128, ka1 = q * 4 + ((2 + hi) ^ sw) + t0 * 128;          // + 128 per key block
   // the 13th block: rows 384..399 of the slot, then the zero block (`zero` = its offset from the slot, in 16-B units)
-  const int kz0 = q < 16 ? ka0 + (A32_KB - 1) * 128 : zero + (q - 16) * 4 + (hi ^ sw), kz1 = q < 16 ? ka1 + (A32_KB - 1) * 128 : zero + (q - 16) * 4 + ((2 + hi) ^ sw);
-  const a32_tr_t vtr = (a32_tr_t)(slot + A32_K_BYTES + (4 * hi + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
+  const int kz0 = q < 16 ? ka0 + (LEN - 1) * 128 : zero + (q - 16) * 4 + (hi ^ sw), kz1 = q < 16 ? ka1 + (LEN - 1) * 128 : zero + (q - 16) * 4 + ((2 + hi) ^ sw);
+  const a32_tr_t vtr = (a32_tr_t)(slot + A32_K_BYTES + (4 * hi + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8) + t0 * 256;
   const uint32_t one2 = (uint32_t)E::cvt(1.0f) * 0x10001u;
 
   constexpr int BR = A32_BDEPTH + 1;
-  constexpr int LASTB = A32_KB - 1;
+  constexpr int LASTB = LAST ? LEN - 1 : -1;         // the range's index of block 12, if it holds it
 #define A32_NR(t) ((SHORT && (t) == LASTB) ? 4 : 16)      // live score registers of key block t
   u32x4 braw[BR][2];
   auto load_bias = [&](int t) __attribute__((always_inline)) {
@@ -156,7 +160,7 @@ __device__ __forceinline__ void a32_qblock(const unsigned char* slot, const int 
     return c;
   };
   auto kfrag = [&](int t, int m) __attribute__((always_inline)) -> V8 {
-    if (t == A32_KB - 1) return __builtin_bit_cast(V8, Ks[(m ? kz1 : kz0)]);          // key rows 400..415 come from the zero block
+    if (t == LASTB) return __builtin_bit_cast(V8, Ks[(m ? kz1 : kz0)]);          // key rows 400..415 come from the zero block
     return __builtin_bit_cast(V8, Ks[(m ? ka1 : ka0) + ((A32_ABL & 16) ? 0 : t) * 128]);
   };
 
@@ -189,7 +193,7 @@ __device__ __forceinline__ void a32_qblock(const unsigned char* slot, const int 
     if (t < T1 && !((A32_ABL & 16) && t > T0)) {
       vf[cur][0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(vtr + t * 256);
       vf[cur][1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(vtr + t * 256 + 64);
-      if (t != A32_KB - 1) {                             // keys 400..415 are padding whatever N <= 400 is: their probabilities are zeros
+      if (t != LASTB) {                                  // keys 400..415 are padding whatever N <= 400 is: their probabilities are zeros
         vf[cur][2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(vtr + t * 256 + 128);
         vf[cur][3] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(vtr + t * 256 + 192);
       }
@@ -206,7 +210,7 @@ __device__ __forceinline__ void a32_qblock(const unsigned char* slot, const int 
       for (int r = 3; r < ((A32_ABL & 128) ? 4 : A32_NR(t) - 1); r += 2) mx = fmaxf(fmaxf(mx, S[cur][r]), S[cur][r + 1]);
       mx = fmaxf(mx, S[cur][A32_NR(t) - 1]);
     }
-    if (t > T0 && t - 1 != A32_KB - 1 && !(A32_ABL & 4))
+    if (t > T0 && t - 1 != LASTB && !(A32_ABL & 4))
       O = E::mfma32(__builtin_bit_cast(V8, __builtin_shufflevector(vf[(A32_ABL & 16) ? (T0 & 1) : nxt][2], vf[(A32_ABL & 16) ? (T0 & 1) : nxt][3], 0, 1, 2, 3, 4, 5, 6, 7)),
                     __builtin_bit_cast(V8, (u32x4){P[nxt][4], P[nxt][5], P[nxt][6], P[nxt][7]}), O);
     if (t == T1) break;
@@ -289,6 +293,7 @@ struct Attn32Params {
   uint16_t* out;               // [BW*N][nH*32]
   const uint32_t* tile_skip;   // optional [nW]: bit t = rows 16t..16t+15 of the window are padding only
   int dsplit_from;             // >= 0: windows >= it are depth-split at token 196 of 392
+  const uint8_t* ranges;       // optional [nW][13][2]: first and last 32-key block q-block qb of window w needs (kvq_attn32_key_ranges)
   // fused qkv projection (x_ln != NULL)
   const uint16_t* x_ln;        // [BW*N][C] 16-bit, window order
   const uint16_t* w_qkv;       // [3C][C]
@@ -365,7 +370,11 @@ __device__ __forceinline__ void a32_fused_qkv(const Attn32Params& p, unsigned ch
 }
 
 // Four waves, three workgroups per CU (rounds 4-6).
-template <typename E, bool FUSED, bool DSPLIT, bool SHORT = false>
+// MODE: which key blocks a q-block runs against — kAllKeys: all 13; kDepthSplit: dsplit_from's halves; kRanges: the table's range, widened
+// outward to the nearest body length the kernel holds (4, 7 or 13 blocks: the extra blocks are masked or padding ones, computed as every
+// block was before).  A launch holds the bodies of ONE mode.
+enum { kAllKeys = 0, kDepthSplit = 1, kRanges = 2 };
+template <typename E, bool FUSED, int MODE, bool SHORT = false>
 __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_eu(3, 3))) void window_attention32_kernel(Attn32Params p) {
   fp16_saturate_mode();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -394,6 +403,15 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
   const int C = p.nH * 32;
   const uint16_t* Qg = p.qkv + ((size_t)h * Mtot + (size_t)bw * N) * 32;
 
+  // kRanges: lane qb of every wave holds q-block qb's widened range, t0 | len << 8 — read once per wave, ahead of the K | V staging, and
+  // handed out by v_readlane: no load stands between a ticket and the first bias tile of its q-block
+  int range_of_lane = 0;
+  if (MODE == kRanges) {
+    const uint8_t* rg = p.ranges + ((size_t)w * A32_KB + min(lane, A32_KB - 1)) * 2;
+    const int first = rg[0], need = (int)rg[1] - first + 1;
+    const int len = need <= 4 ? 4 : need <= 7 ? 7 : A32_KB;
+    range_of_lane = min(first, A32_KB - len) | (len << 8);
+  }
   if (tid < 64) *reinterpret_cast<u32x4*>(smem + A32_OFF_ZERO + tid * 16) = (u32x4){0u, 0u, 0u, 0u};
   if (FUSED) {
     // rows N..399 of both images: zeros (the projection writes rows < N only)
@@ -435,7 +453,16 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
 
   const int q = lane & 31, hi = lane >> 5;
   const uint32_t skip = p.tile_skip ? p.tile_skip[w] : 0u;
-  const bool dsplit = DSPLIT && p.dsplit_from >= 0 && w >= p.dsplit_from;
+  const bool dsplit = MODE == kDepthSplit && p.dsplit_from >= 0 && w >= p.dsplit_from;
+  // the key blocks [t0, t0 + len) q-block qb runs against
+  auto key_range = [&](int qb, int& t0, int& len) __attribute__((always_inline)) {
+    t0 = 0; len = A32_KB;
+    if (MODE == kDepthSplit && dsplit && qb != 6) { t0 = qb < 6 ? 0 : 6; len = 7; }      // N = 392, halves of 196 tokens: q-block 6 sees both
+    if (MODE == kRanges) {
+      const int r = __builtin_amdgcn_readlane(range_of_lane, qb);
+      t0 = r & 0xff; len = r >> 8;
+    }
+  };
   auto take = [&]() -> int {
     int qb_;
     do {                                                        // q-blocks whose two 16-row tiles are padding only are passed over
@@ -447,7 +474,7 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
   };
   const u32x4* img = p.image + (size_t)(A32_DIAG_FLAG(p.image_one) ? h : pair) * nqb * (A32_KB * 128) + lane;
   // the ticket, the q fragments and the first bias tile of the NEXT q-block are requested while this one is computed
-  struct Req { V8 qf0, qf1; u32x4 pre[2]; };
+  struct Req { V8 qf0, qf1; u32x4 pre[2]; int t0, len; };
   auto request = [&](int qb, Req& r) __attribute__((always_inline)) {
     const int qrow = min(32 * qb + q, N - 1);
     r.qf0 = *reinterpret_cast<const V8*>(Qg + (size_t)qrow * 32 + 8 * hi);
@@ -456,8 +483,8 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
       r.qf0 = __builtin_bit_cast(V8, (u32x4){0u, 0u, 0u, 0u});
       r.qf1 = r.qf0;
     }
-    const int t0 = (dsplit && qb > 6) ? 6 : 0;                  // first key block of what will run
-    const u32x4* bd = img + (size_t)min(qb, nqb - 1) * (A32_KB * 128) + t0 * 128;
+    key_range(min(qb, nqb - 1), r.t0, r.len);                   // the first bias tile of what will run
+    const u32x4* bd = img + (size_t)min(qb, nqb - 1) * (A32_KB * 128) + r.t0 * 128;
     r.pre[0] = bd[0]; r.pre[1] = bd[64];
   };
   auto run = [&](int qb, const Req& r) __attribute__((always_inline)) {
@@ -465,12 +492,16 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
     uint16_t* orow = p.out + ((size_t)bw * N + 32 * qb + q) * C + h * 32;
     const bool store = 32 * qb + q < N;
     const int zero = A32_OFF_ZERO >> 4;
-    // depth-split window (N = 392, halves of 196 tokens): q-blocks 0..5 see key blocks 0..6, 7..12 see 6..12, q-block 6 all of them
-    if (dsplit && qb != 6) {
-      if (qb < 6) a32_qblock<E, 0, 7>(smem, zero, bd, r.qf0, r.qf1, r.pre, orow, store);
-      else a32_qblock<E, 6, A32_KB, SHORT>(smem, zero, bd, r.qf0, r.qf1, r.pre, orow, store);
+    // a range that ends at block 12 starts at 13 - len; the others start at a run-time block (the depth split's: block 0)
+    const int t0 = MODE == kRanges ? r.t0 : 0;
+    if (MODE != kAllKeys && r.len == 7) {
+      if (r.t0 == A32_KB - 7) a32_qblock<E, 7, true, SHORT>(smem, zero, bd, A32_KB - 7, r.qf0, r.qf1, r.pre, orow, store);
+      else a32_qblock<E, 7, false>(smem, zero, bd, t0, r.qf0, r.qf1, r.pre, orow, store);
+    } else if (MODE == kRanges && r.len == 4) {
+      if (r.t0 == A32_KB - 4) a32_qblock<E, 4, true, SHORT>(smem, zero, bd, A32_KB - 4, r.qf0, r.qf1, r.pre, orow, store);
+      else a32_qblock<E, 4, false>(smem, zero, bd, t0, r.qf0, r.qf1, r.pre, orow, store);
     } else {
-      a32_qblock<E, 0, A32_KB, SHORT>(smem, zero, bd, r.qf0, r.qf1, r.pre, orow, store);
+      a32_qblock<E, A32_KB, true, SHORT>(smem, zero, bd, 0, r.qf0, r.qf1, r.pre, orow, store);
     }
   };
   // ONE inlined body per kind of ticket (rounds 4-5 unrolled the loop twice to rotate two request sets; the copy below is 16 moves per q-block)
@@ -562,9 +593,9 @@ __global__ __launch_bounds__(256) void bias32_build_kernel(Bias32BuildParams p) 
   }
 }
 
-template <typename E, bool FUSED, bool DSPLIT, bool SHORT>
+template <typename E, bool FUSED, int MODE, bool SHORT>
 static int launch_attn32_form(const Attn32Params& p, hipStream_t st) {
-  auto kern = window_attention32_kernel<E, FUSED, DSPLIT, SHORT>;
+  auto kern = window_attention32_kernel<E, FUSED, MODE, SHORT>;
   LdsOptIn opt;
   if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), A32_LDS)) return rc;
   const int nclip = p.BW / p.nW, nrep = p.nW / p.n_types, npair = p.n_types * p.nH;
@@ -575,16 +606,17 @@ static int launch_attn32_form(const Attn32Params& p, hipStream_t st) {
   return KVQ_OK;
 }
 
-template <typename E, bool FUSED, bool DSPLIT>
+template <typename E, bool FUSED, int MODE>
 static int launch_attn32(const Attn32Params& p, hipStream_t st) {
   // N = 385..392 (the (8,7,7) window): the 13th key block holds 8 valid keys (SHORT; results agree to the last bit with the generic block)
-  return p.N > 384 && p.N <= 392 ? launch_attn32_form<E, FUSED, DSPLIT, true>(p, st) : launch_attn32_form<E, FUSED, DSPLIT, false>(p, st);
+  return p.N > 384 && p.N <= 392 ? launch_attn32_form<E, FUSED, MODE, true>(p, st) : launch_attn32_form<E, FUSED, MODE, false>(p, st);
 }
 
 template <typename E>
 static int launch_attn32_e(const Attn32Params& p, hipStream_t st) {
-  if (p.x_ln) return p.dsplit_from >= 0 ? launch_attn32<E, true, true>(p, st) : launch_attn32<E, true, false>(p, st);
-  return p.dsplit_from >= 0 ? launch_attn32<E, false, true>(p, st) : launch_attn32<E, false, false>(p, st);
+  if (p.ranges) return p.x_ln ? launch_attn32<E, true, kRanges>(p, st) : launch_attn32<E, false, kRanges>(p, st);
+  if (p.x_ln) return p.dsplit_from >= 0 ? launch_attn32<E, true, kDepthSplit>(p, st) : launch_attn32<E, true, kAllKeys>(p, st);
+  return p.dsplit_from >= 0 ? launch_attn32<E, false, kDepthSplit>(p, st) : launch_attn32<E, false, kAllKeys>(p, st);
 }
 
 }  // namespace kvq
@@ -609,17 +641,60 @@ extern "C" int kvq_attn_bias32_build(const int32_t* tok, const float* rpb, const
   return KVQ_OK;
 }
 
-extern "C" int kvq_window_attention32(const KvqAttnDenseArgs* a, void* stream) {
+// ---- region order and key ranges of shifted windows (host; the plan's and the tests' one source of both) ------------------------------
+// A window's rows sorted by the shift-mask region of their descriptor (stable: raster order inside a region): every region is one
+// contiguous run of rows, so the keys a 32-query block can see are one contiguous range of 32-key blocks.
+extern "C" int kvq_attn32_row_order(const int32_t* tok_host, int n_windows, int N, int32_t* order) {
+  KVQ_REQUIRE(tok_host && order, KVQ_ERR_NULL, "kvq_attn32_row_order: NULL pointer");
+  KVQ_REQUIRE(n_windows > 0 && N >= 1, KVQ_ERR_SHAPE, "kvq_attn32_row_order: bad shape n_windows=%d N=%d", n_windows, N);
+  for (int w = 0; w < n_windows; ++w) {
+    const int32_t* tk = tok_host + (size_t)w * N * 2;
+    int32_t* o = order + (size_t)w * N;
+    int count[257] = {0};                                           // counting sort by the 8-bit region id: stable
+    for (int n = 0; n < N; ++n) ++count[((tk[2 * n + 1] >> 16) & 0xff) + 1];
+    for (int r = 0; r < 256; ++r) count[r + 1] += count[r];
+    for (int n = 0; n < N; ++n) o[count[(tk[2 * n + 1] >> 16) & 0xff]++] = n;
+  }
+  return KVQ_OK;
+}
+
+// ranges[w][qb] = {first, last} 32-key block that holds a key (< N) some valid query row of the block is not masked against, read off the
+// descriptors of the rows AS STORED — no geometry formula: whatever the row order, a block outside the range holds only scores the image
+// stores as -100 (or padding keys), which leave the exponential as zeros.  Entries of q-blocks past the window's last are the full range.
+extern "C" int kvq_attn32_key_ranges(const int32_t* tok_host, int n_windows, int N, int use_mask, uint8_t* ranges) {
   using namespace kvq;
-  KVQ_REQUIRE(a && a->qkv && a->bias_dense && a->out, KVQ_ERR_NULL, "kvq_window_attention32: NULL pointer");
+  KVQ_REQUIRE(tok_host && ranges, KVQ_ERR_NULL, "kvq_attn32_key_ranges: NULL pointer");
+  KVQ_REQUIRE(n_windows > 0 && N >= 1 && N <= 400, KVQ_ERR_SHAPE, "kvq_attn32_key_ranges: bad shape n_windows=%d N=%d", n_windows, N);
+  const int nkb = (N + 31) / 32;
+  for (int w = 0; w < n_windows; ++w) {
+    const int32_t* tk = tok_host + (size_t)w * N * 2;
+    for (int qb = 0; qb < A32_KB; ++qb) {
+      int first = 0, last = nkb - 1;
+      if (use_mask && qb < nkb) {
+        bool in_block[256] = {false};                              // the regions of the block's query rows
+        for (int qq = 32 * qb; qq < N && qq < 32 * qb + 32; ++qq) in_block[(tk[2 * qq + 1] >> 16) & 0xff] = true;
+        first = nkb; last = -1;
+        for (int key = 0; key < N; ++key)
+          if (in_block[(tk[2 * key + 1] >> 16) & 0xff]) { first = first < (key >> 5) ? first : key >> 5; last = key >> 5; }
+      }
+      ranges[((size_t)w * A32_KB + qb) * 2] = (uint8_t)first;
+      ranges[((size_t)w * A32_KB + qb) * 2 + 1] = (uint8_t)last;
+    }
+  }
+  return KVQ_OK;
+}
+
+static int window_attention32(const char* who, const KvqAttnDenseArgs* a, const uint8_t* ranges, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(a && a->qkv && a->bias_dense && a->out, KVQ_ERR_NULL, "%s: NULL pointer", who);
   const int BW = a->BW, nW = a->nW, N = a->N, num_heads = a->num_heads, n_types = a->n_types;
   KVQ_REQUIRE(BW > 0 && nW > 0 && BW % nW == 0 && num_heads > 0 && n_types > 0 && nW % n_types == 0, KVQ_ERR_SHAPE,
-              "kvq_window_attention32: bad shape BW=%d nW=%d n_types=%d nH=%d", BW, nW, n_types, num_heads);
-  KVQ_REQUIRE(N >= 1 && N <= 400, KVQ_ERR_UNSUPPORTED, "kvq_window_attention32: window of %d tokens unsupported (1..400)", N);
-  KVQ_REQUIRE(((size_t)a->bias_dense & 15) == 0, KVQ_ERR_SHAPE, "kvq_window_attention32: the bias image must be 16-byte aligned");
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_window_attention32: dtype %d", a->dtype);
+              "%s: bad shape BW=%d nW=%d n_types=%d nH=%d", who, BW, nW, n_types, num_heads);
+  KVQ_REQUIRE(N >= 1 && N <= 400, KVQ_ERR_UNSUPPORTED, "%s: window of %d tokens unsupported (1..400)", who, N);
+  KVQ_REQUIRE(((size_t)a->bias_dense & 15) == 0, KVQ_ERR_SHAPE, "%s: the bias image must be 16-byte aligned", who);
+  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "%s: dtype %d", who, a->dtype);
   KVQ_REQUIRE(a->dsplit_from < 0 || (N == 392 && a->dsplit_from < nW), KVQ_ERR_UNSUPPORTED,
-              "kvq_window_attention32: depth-split windows need the (8,7,7) window (N = 392); got N=%d from=%d", N, a->dsplit_from);
+              "%s: depth-split windows need the (8,7,7) window (N = 392); got N=%d from=%d", who, N, a->dsplit_from);
   const int units = BW * num_heads, nqb = (N + 31) / 32;
   int qsplit = units >= 768 ? 1 : 768 / units;        // 768 = 256 CUs x 3 resident workgroups
   // Round 5: no q-split by default.  Splitting a (window, head) unit over 2-4 workgroups fills the chip when the launch is alone on it
@@ -635,18 +710,31 @@ extern "C" int kvq_window_attention32(const KvqAttnDenseArgs* a, void* stream) {
   { static const bool nq = getenv("KVQ_NO_Q_STORE") && atoi(getenv("KVQ_NO_Q_STORE")) == 1; p.no_q_store = nq; }
 #endif
   if (a->pad_mask) {
-    KVQ_REQUIRE(a->b_qkv && !a->x_ln, KVQ_ERR_NULL, "kvq_window_attention32: pad_mask needs b_qkv (and excludes the fused projection)");
+    KVQ_REQUIRE(a->b_qkv && !a->x_ln, KVQ_ERR_NULL, "%s: pad_mask needs b_qkv (and excludes the fused projection)", who);
     p.pad_mask = a->pad_mask; p.b_qkv = a->b_qkv;
   }
   if (a->x_ln) {
     const int C = 32 * num_heads;
-    KVQ_REQUIRE(a->w_qkv && a->b_qkv, KVQ_ERR_NULL, "kvq_window_attention32: x_ln without w_qkv / b_qkv");
-    KVQ_REQUIRE(C == 96, KVQ_ERR_UNSUPPORTED, "kvq_window_attention32: the fused qkv projection is built for C = 96 (got %d)", C);
+    KVQ_REQUIRE(a->w_qkv && a->b_qkv, KVQ_ERR_NULL, "%s: x_ln without w_qkv / b_qkv", who);
+    KVQ_REQUIRE(C == 96, KVQ_ERR_UNSUPPORTED, "%s: the fused qkv projection is built for C = 96 (got %d)", who, C);
     KVQ_REQUIRE((((size_t)a->x_ln | (size_t)a->w_qkv | (size_t)a->b_qkv) & 15) == 0, KVQ_ERR_SHAPE,
-                "kvq_window_attention32: x_ln / w_qkv / b_qkv must be 16-byte aligned");
+                "%s: x_ln / w_qkv / b_qkv must be 16-byte aligned", who);
     p.qsplit = 1;       // one workgroup per (window, head) whatever the batch: a block's path must not depend on what shares the launch
     p.x_ln = a->x_ln; p.w_qkv = a->w_qkv; p.b_qkv = a->b_qkv; p.q_scale = a->q_scale; p.q_out = const_cast<uint16_t*>(a->qkv);
   }
+  if (ranges) {
+    KVQ_REQUIRE(a->dsplit_from < 0 && !a->pad_mask, KVQ_ERR_UNSUPPORTED, "%s: key ranges exclude dsplit_from and pad_mask (un-padded partitions only)", who);
+    p.ranges = ranges;
+  }
   hipStream_t st = (hipStream_t)stream;
   return a->dtype == KVQ_DT_FP16 ? launch_attn32_e<Fp16>(p, st) : launch_attn32_e<Bf16>(p, st);
+}
+
+extern "C" int kvq_window_attention32(const KvqAttnDenseArgs* a, void* stream) {
+  return window_attention32("kvq_window_attention32", a, nullptr, stream);
+}
+
+extern "C" int kvq_window_attention32_ranges(const KvqAttnDenseArgs* a, const uint8_t* ranges, void* stream) {
+  KVQ_REQUIRE(ranges, KVQ_ERR_NULL, "kvq_window_attention32_ranges: NULL ranges");
+  return window_attention32("kvq_window_attention32_ranges", a, ranges, stream);
 }

@@ -52,6 +52,7 @@ struct StageGeom {
   int32_t* d_dst[2];  // [L] inverse of d_src (token -> window row).  A bijection — the next block's norm1 rows can be EMITTED through it —
                       // only when Lp == L (no padding)
   int32_t* d_tok[2];  // [nW*N][2]
+  uint8_t* d_ranges[2];  // [nW][13][2] key-block range of every 32-query block (kvq_attn32_key_ranges), or nullptr: region-ordered partitions only
   int32_t* d_merge;   // [L_next][4] or nullptr
   int Dn, Hn, Wn;     // dims after the merge
 };
@@ -159,8 +160,36 @@ static int build_stage_maps(KvqSwinPlan* pl, StageGeom& g, int par) {
               tok[2 * r + 1] = (fh & 0xff) | ((fw & 0xff) << 8) | ((region & 0xff) << 16);
             }
       }
+  // Shifted, un-padded partitions store a window's rows SORTED BY MASK REGION (stable: raster order inside a region).  Attention does not
+  // depend on the order of a window's rows as long as q, k, v, the bias image and the output rows share it, and every consumer reaches
+  // window rows through the maps built below from this order (a row keeps the bias code of its raster position: `tok` moves with it).
+  // Each region is then one contiguous run of rows, a 32-query block needs one contiguous range of 32-key blocks, and attention32 passes
+  // over the rest (d_ranges; the depth split falls out of the same table).  Un-shifted partitions have one region per window; PADDED
+  // partitions keep the raster order and dsplit_from: the 16-row tiles of d_skip / d_padmask are tiles of that order.
+  g.d_ranges[par] = nullptr;
+  std::vector<uint8_t> ranges;
+  if (par == 1 && g.shifted_any && g.Lp == g.L) {
+    std::vector<int32_t> order((size_t)g.Lp), src_r(src), tok_r(tok);
+    int rc = kvq_attn32_row_order(tok_r.data(), g.nW, g.N, order.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < (size_t)g.Lp; ++i) {
+      const size_t from = i - i % g.N + order[i];
+      src[i] = src_r[from]; tok[2 * i] = tok_r[2 * from]; tok[2 * i + 1] = tok_r[2 * from + 1];
+    }
+    ranges.resize((size_t)g.nW * 13 * 2);
+    rc = kvq_attn32_key_ranges(tok.data(), g.nW, g.N, 1, ranges.data());
+    if (rc) return rc;
+  }
   int rc = upload(pl, src, &g.d_src[par]);
   if (rc) return rc;
+  if (!ranges.empty()) {
+    std::vector<int32_t> packed((ranges.size() + 3) / 4, 0);
+    memcpy(packed.data(), ranges.data(), ranges.size());
+    int32_t* d = nullptr;
+    rc = upload(pl, packed, &d);
+    if (rc) return rc;
+    g.d_ranges[par] = reinterpret_cast<uint8_t*>(d);
+  }
   g.d_dst[par] = nullptr;
   g.d_pad[par] = nullptr;
   {
@@ -546,9 +575,10 @@ static int build_schedule(const KvqSwinPlan* pl, const KvqSwinWeights* w, bool f
       // reads them from the buffer
       t.pad_mask = padded && t.dense && g.d_padmask[t.par];
       t.fill_pad = t.qkv == kQkvGemmPadded && !t.pad_mask;
-      // shifted blocks of the (8,7,7) window with a half-window depth shift: the last window slab along D is depth-split
+      // shifted blocks of the (8,7,7) window with a half-window depth shift: the last window slab along D is depth-split.  Region-ordered
+      // partitions (d_ranges) take the split from their key ranges instead
       const int slabs = g.Dp / g.ws[0];
-      t.dsplit_from = (t.par == 1 && g.N == 392 && g.ws[0] == 8 && g.ws[1] == 7 && g.ws[2] == 7 && g.ss[0] == 4 && slabs >= 1)
+      t.dsplit_from = (t.par == 1 && !g.d_ranges[t.par] && g.N == 392 && g.ws[0] == 8 && g.ws[1] == 7 && g.ws[2] == 7 && g.ss[0] == 4 && slabs >= 1)
                           ? g.nW - g.nW / slabs : -1;
       t.fused_tail = bw.tail_pack && kvq_block_tail_supported(g.C, hidden);
       x16 = x16 && t.fused_tail && g.d_dst[t.par];
@@ -648,7 +678,8 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
     aa.num_heads = g.nH; aa.dtype = pl->dtype; aa.out = bo; aa.tile_skip = (const uint32_t*)g.d_skip[t.par]; aa.dsplit_from = t.dsplit_from;
     if (fq) { aa.x_ln = bln; aa.w_qkv = bw.qkv_w; aa.b_qkv = bw.qkv_b; aa.q_scale = kQScaleLog2; }
     if (t.pad_mask) { aa.pad_mask = (const uint32_t*)g.d_padmask[t.par]; aa.b_qkv = bw.qkv_b; }
-    KVQ_TRY_UNLESS(1 | (t.i == last ? 32 : 0), kvq_window_attention32(&aa, st));
+    if (g.d_ranges[t.par]) KVQ_TRY_UNLESS(1 | (t.i == last ? 32 : 0), kvq_window_attention32_ranges(&aa, g.d_ranges[t.par], st));
+    else KVQ_TRY_UNLESS(1 | (t.i == last ? 32 : 0), kvq_window_attention32(&aa, st));
     return KVQ_OK;
   };
 

@@ -147,15 +147,16 @@ def attn_bias32(tok: torch.Tensor, rpb: torch.Tensor, fpb: Optional[torch.Tensor
 def window_attention32(qkv: torch.Tensor, image: torch.Tensor, nW: int, N: int, n_types: Optional[int] = None,
                        tile_skip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dsplit_from: int = -1,
                        x_ln: Optional[torch.Tensor] = None, w_qkv: Optional[torch.Tensor] = None, b_qkv: Optional[torch.Tensor] = None,
-                       q_scale: float = 1.0, pad_mask: Optional[torch.Tensor] = None):
+                       q_scale: float = 1.0, pad_mask: Optional[torch.Tensor] = None, ranges: Optional[torch.Tensor] = None):
     """qkv fp16|bf16 [3,nH,BW*N,32] with q scaled by head_dim^-0.5 * log2(e) + the pre-built bias image of ``attn_bias32``; returns
     [BW*N, nH*32].  ``n_types`` (default nW): window w uses bias w % n_types.  ``tile_skip`` int32 [nW]: bit t = rows 16t..16t+15 of the
     window are padding only (a 32-row q-block is passed over when both its tiles are; such rows keep what ``out`` held).
     ``dsplit_from`` >= 0: windows >= it are depth-split (shifted (8,7,7) blocks).  ``x_ln`` [BW*N, C] + ``w_qkv`` [3C, C] + ``b_qkv`` [3C]:
     the launch computes q | k | v itself (``qkv`` = a [1|3, nH, BW*N, 32] buffer whose first third receives q; ``q_scale`` =
     head_dim^-0.5 * log2(e)).  ``pad_mask`` int32 [nW, 13] (+ ``b_qkv``): bit r of window w = row r is a padding row — its k | v are
-    written by the kernel (= the bias), its q taken as zero; those rows of ``qkv`` are not read."""
-    _need_gpu(qkv, image, tile_skip, out, pad_mask)
+    written by the kernel (= the bias), its q taken as zero; those rows of ``qkv`` are not read.  ``ranges`` uint8 [nW, 13, 2]
+    (``attn32_key_ranges``; rows in region order): a q-block passes over the key blocks outside its range."""
+    _need_gpu(qkv, image, tile_skip, out, pad_mask, ranges)
     assert qkv.dtype in HALF_TYPES and qkv.is_contiguous()
     nH = qkv.shape[1]
     BW = qkv.shape[2] // N
@@ -172,8 +173,32 @@ def window_attention32(qkv: torch.Tensor, image: torch.Tensor, nW: int, N: int, 
         _need_gpu(b_qkv)
         assert pad_mask.dtype == torch.int32 and pad_mask.is_contiguous() and (b_qkv is None or b_qkv.dtype == torch.float32)
         a.pad_mask, a.b_qkv = ptr(pad_mask), ptr(b_qkv)
+    if ranges is not None:
+        assert ranges.dtype == torch.uint8 and ranges.is_contiguous() and ranges.numel() == nW * 26
+        check(lib().kvq_window_attention32_ranges(C.byref(a), ptr(ranges), current_stream()), "kvq_window_attention32_ranges")
+        return out
     check(lib().kvq_window_attention32(C.byref(a), current_stream()), "kvq_window_attention32")
     return out
+
+
+def attn32_row_order(tok, n_windows: int, N: int):
+    """Host: the region order of every window's rows — int32 [n_windows, N], entry i = the index (in ``tok``'s order) of the row the
+    order stores at position i (``tok`` int32 [n_windows*N, 2] descriptors, numpy or CPU tensor)."""
+    import numpy as np
+    tok = np.ascontiguousarray(np.asarray(tok, dtype=np.int32).reshape(n_windows * N, 2))
+    order = np.empty((n_windows, N), np.int32)
+    check(lib().kvq_attn32_row_order(tok.ctypes.data, n_windows, N, order.ctypes.data), "kvq_attn32_row_order")
+    return order
+
+
+def attn32_key_ranges(tok, n_windows: int, N: int, use_mask: bool):
+    """Host: uint8 [n_windows, 13, 2] = first and last 32-key block every 32-query block needs, from the descriptors ``tok`` of the
+    rows in the order they are stored (numpy or CPU tensor)."""
+    import numpy as np
+    tok = np.ascontiguousarray(np.asarray(tok, dtype=np.int32).reshape(n_windows * N, 2))
+    ranges = np.empty((n_windows, 13, 2), np.uint8)
+    check(lib().kvq_attn32_key_ranges(tok.ctypes.data, n_windows, N, int(use_mask), ranges.ctypes.data), "kvq_attn32_key_ranges")
+    return ranges
 
 
 def patch_im2col(x: torch.Tensor, patch: Sequence[int], out_dtype=torch.float16):
