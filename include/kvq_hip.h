@@ -272,7 +272,8 @@ typedef enum {
   KVQ_EPI_RESID_F32 = 3,   /* out_f32[row(m)][n] += acc + bias, row(m) via scatter map (:472-488,509,514) */
   KVQ_EPI_STORE_F32 = 4,   /* out_f32[m][n] = acc (+ bias if non-NULL)         (reduction :553, embed) */
   KVQ_EPI_RELU_BF16 = 5,   /* out_bf16[m][n] = relu(acc + bias [+ resid_bf16[m][n]])   conv+BN(+identity)+ReLU */
-  KVQ_EPI_QGELU_BF16 = 6   /* out_bf16[m][n] = y * sigmoid(1.702 y), y = acc + bias     CLIP QuickGELU (clip/model.py:179-181) */
+  KVQ_EPI_QGELU_BF16 = 6,  /* out_bf16[m][n] = y * sigmoid(1.702 y), y = acc + bias     CLIP QuickGELU (clip/model.py:179-181) */
+  KVQ_EPI_RESID_SCALE_F32 = 7 /* out_f32[m][n] += scale[n] * (acc + bias): kvq_gemm_resid_scaled only (the scale is its argument) */
 } KvqEpilogue;
 
 typedef struct {
@@ -312,6 +313,12 @@ int kvq_gemm_splitk_factor(int M, int N, int K);
 size_t kvq_gemm_splitk_bytes(int M, int N, int K);
 
 int kvq_gemm_bf16(const KvqGemmArgs* host_args, void* stream);
+/* Residual GEMM with a per-column scale — ConvNeXt's pwconv2, layer scale and residual add (conv_backbone.py:182-187) in one launch:
+ *   out_f32[m][n] += col_scale[n] * (acc + bias[n])          col_scale fp32 [N], applied in fp32 in the epilogue
+ * (nothing is folded into the 16-bit weights: an initial gamma of 1e-6 times a weight of N(0, 0.02^2) lies below fp16's smallest
+ * subnormal).  host_args as for KVQ_EPI_RESID_F32 — `epilogue` must be KVQ_EPI_RESID_F32 or KVQ_EPI_RESID_SCALE_F32, the scatter map
+ * and split-K apply as there; with col_scale == 1 the result is bit-equal to KVQ_EPI_RESID_F32.  KvqGemmArgs is unchanged. */
+int kvq_gemm_resid_scaled(const KvqGemmArgs* host_args, const float* col_scale, void* stream);
 /* Which main loop kvq_gemm_bf16 / kvq_conv_implicit take (process-wide; returns the previous mode): -1 = by shape (default; the
  * 256 x 256 x 64 eight-phase kernel of csrc/gemm256.hip when the tile grid fills the chip, else the 128 x 128 x 32 ring kernel),
  * 0 = never the wide tile, 1 = the wide tile whenever the shape is eligible (K % 64 == 0, K >= 128).  Any other value only reads.
@@ -321,6 +328,26 @@ int kvq_gemm_tile_mode(int mode);
  * dev_buf[8*b + {0:start, 1:first slice landed, 2:K loop done, 3:epilogue done}] (shader clock) and
  * [4] = XCC id << 32 | HW_ID.  Pass NULL to switch it off. */
 int kvq_debug_gemm_trace(void* dev_buf, int max_blocks);
+
+/* Depthwise (kt,7,7) Conv3d + LayerNorm over C as one launch (csrc/dwconv.hip): Block3D.dwconv + Block3D.norm of the ConvNeXt-3D
+ * trunk (conv_backbone.py:166-167, :177-179).  Zero padding kt/2 in T and 3 in H and W, no halo across batch elements; fp32
+ * throughout, taps accumulated in one fixed order (two launches are bit-equal), biased variance as F.layer_norm; the conv
+ * result stays in registers.  Shapes: C in {96, 192, 384, 768}, kt in {1, 3}, any B, T, H, W >= 1 (kvq_dwconv3d_ln_supported, host
+ * only, 1 / 0); anything else returns KVQ_ERR_UNSUPPORTED without a launch. */
+typedef struct {
+  const float* x;       /* fp32 channels-last (B, T, H, W, C): the residual stream, read only        */
+  const float* w;       /* fp32 [kt*7*7][C], tap-major: w[(dt*7 + ky)*7 + kx][c] = weight[c][0][dt][ky][kx] */
+  const float* bias;    /* conv bias [C]                                                             */
+  const float* ln_w;    /* LayerNorm weight / bias [C]                                               */
+  const float* ln_b;
+  int32_t B, T, H, W, C, kt;
+  float eps;
+  int32_t dtype;        /* KvqDtype of out_h                                                         */
+  uint16_t* out_h;      /* 16-bit rows [B*T*H*W][C], or                                              */
+  float* out_f32;       /* fp32 rows: exactly one of the two is non-NULL                             */
+} KvqDwconvLnArgs;
+int kvq_dwconv3d_ln_supported(int C, int kt, int T, int H, int W);
+int kvq_dwconv3d_ln(const KvqDwconvLnArgs* host_args, void* stream);
 
 /* PatchEmbed3D (swin_backbone.py:715-733) as one launch, token-per-lane MFMA (csrc/embed.hip): the strided
  * Conv3d reads its patches straight from the clip (no im2col buffer), + bias + LayerNorm(E), optionally + the

@@ -17,7 +17,7 @@ K_NAMES = ["im2col", "layernorm", "gemm_qkv", "attn", "gemm_proj", "gemm_fc1", "
            "gemm_embed", "tail", "embed", "merge"]
 K_COUNT = len(K_NAMES)
 
-EPI_BIAS_BF16, EPI_GELU_BF16, EPI_QKV_BF16, EPI_RESID_F32, EPI_STORE_F32, EPI_RELU_BF16, EPI_QGELU_BF16 = range(7)
+EPI_BIAS_BF16, EPI_GELU_BF16, EPI_QKV_BF16, EPI_RESID_F32, EPI_STORE_F32, EPI_RELU_BF16, EPI_QGELU_BF16, EPI_RESID_SCALE_F32 = range(8)
 DT_BF16, DT_FP16 = 0, 1
 ABI_VERSION = 31
 
@@ -83,6 +83,12 @@ class KvqConvArgs(C.Structure):
                 ("N", C.c_int32), ("epilogue", C.c_int32), ("dtype", C.c_int32), ("out_bf16", p_void), ("out_f32", p_void),
                 ("resid_bf16", p_void), ("resid_f32", p_void), ("splitk_ws", p_void), ("splitk_ws_bytes", C.c_size_t),
                 ("ldc", C.c_int32), ("col_off", C.c_int32)]
+
+
+class KvqDwconvLnArgs(C.Structure):
+    _fields_ = [("x", p_void), ("w", p_void), ("bias", p_void), ("ln_w", p_void), ("ln_b", p_void), ("B", C.c_int32), ("T", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("kt", C.c_int32), ("eps", C.c_float), ("dtype", C.c_int32),
+                ("out_h", p_void), ("out_f32", p_void)]
 
 
 class KvqNetTensor(C.Structure):
@@ -209,6 +215,9 @@ SYMBOLS = {
     "kvq_layernorm_rows": (i32, [p_void, p_void, i32, i32, i32, i32, i32, p_void, p_void, f32, p_void, i32, p_void,
                                  p_void]),
     "kvq_gemm_bf16": (i32, [C.POINTER(KvqGemmArgs), p_void]),
+    "kvq_gemm_resid_scaled": (i32, [C.POINTER(KvqGemmArgs), p_void, p_void]),
+    "kvq_dwconv3d_ln_supported": (i32, [i32] * 5),
+    "kvq_dwconv3d_ln": (i32, [C.POINTER(KvqDwconvLnArgs), p_void]),
     "kvq_gemm_splitk_factor": (i32, [i32, i32, i32]),
     "kvq_gemm_splitk_bytes": (sz, [i32, i32, i32]),
     "kvq_debug_gemm_trace": (i32, [p_void, i32]),

@@ -141,7 +141,7 @@ __device__ __forceinline__ void range_flush(uint32_t m, uint32_t* word, uint32_t
 // (and kvq_block_tail, tail.hpp) are these with {NULL, 0}: the public argument structs stay as they are.
 int patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStream_t st);
 int patch_merge_launch(const KvqPatchMergeArgs* a, RangeFlag range, hipStream_t st);
-int gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t st);
+int gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t st, const float* col_scale = nullptr);   // col_scale: kvq_gemm_resid_scaled
 
 // exact GELU (erf), as nn.GELU() default (swin_backbone.py:72, head.py:56)
 __device__ __forceinline__ float gelu_erf(float x) {

@@ -342,16 +342,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p, const 
 #pragma unroll
     for (int k = 0; k < 4; ++k) { v[k] += a[k]; v[4 + k] += b[k]; }
   }
-  if (epi == KVQ_EPI_STORE_F32 || epi == KVQ_EPI_RESID_F32) {
+  if (epi == KVQ_EPI_STORE_F32 || epi == KVQ_EPI_RESID_F32 || epi == KVQ_EPI_RESID_SCALE_F32) {
     long orow = m;
-    if (epi == KVQ_EPI_RESID_F32 && p.scatter_map) {
+    if (epi != KVQ_EPI_STORE_F32 && p.scatter_map) {
       const int b = m / p.map_rows, s3 = p.scatter_map[m - b * p.map_rows];
       if (s3 < 0) return;
       orow = (long)b * p.out_rows + s3;
     }
     f32x4* o = reinterpret_cast<f32x4*>(p.out_f32 + (size_t)orow * p.N + n);
     f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
-    if (epi == KVQ_EPI_RESID_F32) { x0 += o[0]; x1 += o[1]; }
+    if (epi == KVQ_EPI_RESID_SCALE_F32) {
+      x0 *= *reinterpret_cast<const f32x4*>(p.col_scale + n);
+      x1 *= *reinterpret_cast<const f32x4*>(p.col_scale + n + 4);
+    }
+    if (epi != KVQ_EPI_STORE_F32) { x0 += o[0]; x1 += o[1]; }
     o[0] = x0; o[1] = x1;
     return;
   }
@@ -564,7 +568,15 @@ extern "C" int kvq_gemm_bf16(const KvqGemmArgs* a, void* stream) {
   return kvq::gemm_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream);
 }
 
-int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream) {
+extern "C" int kvq_gemm_resid_scaled(const KvqGemmArgs* a, const float* col_scale, void* stream) {
+  KVQ_REQUIRE(a && col_scale, KVQ_ERR_NULL, "kvq_gemm_resid_scaled: NULL args / col_scale");
+  KVQ_REQUIRE(a->epilogue == KVQ_EPI_RESID_F32 || a->epilogue == KVQ_EPI_RESID_SCALE_F32, KVQ_ERR_UNSUPPORTED,
+              "kvq_gemm_resid_scaled: epilogue %d is not a residual epilogue", a->epilogue);
+  KVQ_REQUIRE(((size_t)col_scale & 15) == 0, KVQ_ERR_SHAPE, "kvq_gemm_resid_scaled: col_scale must be 16-byte aligned");
+  return kvq::gemm_launch(a, kvq::RangeFlag{nullptr, 0}, (hipStream_t)stream, col_scale);
+}
+
+int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream, const float* col_scale) {
   using namespace kvq;
   KVQ_REQUIRE(a && a->A && a->W, KVQ_ERR_NULL, "kvq_gemm_bf16: NULL A/W");
   KVQ_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->N % 8 == 0 && a->K % 32 == 0, KVQ_ERR_SHAPE,
@@ -581,6 +593,7 @@ int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream) 
   KVQ_REQUIRE(!range.word || (a->epilogue == KVQ_EPI_BIAS_BF16 && a->dtype == KVQ_DT_FP16 && !a->splitk_ws), KVQ_ERR_UNSUPPORTED,
               "kvq_gemm_bf16: the range detector needs the fp16 bias epilogue without split-K");
   p.range = range;
+  p.col_scale = col_scale;
   KVQ_REQUIRE(!a->a_gather || (a->a_rows > 0 && a->a_phys_rows >= a->a_rows && a->M % a->a_rows == 0 && !a->splitk_ws), KVQ_ERR_SHAPE,
               "kvq_gemm_bf16: a_gather needs M = n_batch * a_rows, a_phys_rows >= a_rows, no split-K");
   KVQ_REQUIRE(a->ldc != 0 || a->col_off == 0, KVQ_ERR_SHAPE, "kvq_gemm_bf16: col_off = %d without ldc (the epilogue would write outside the row)",
@@ -608,9 +621,13 @@ int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream) 
                   "kvq_gemm_bf16: QKV epilogue needs N == 3*32*num_heads (N=%d nH=%d)", a->N, a->num_heads);
       return launch_dt<KVQ_EPI_QKV_BF16>(a->dtype, p, st);
     case KVQ_EPI_RESID_F32:
+    case KVQ_EPI_RESID_SCALE_F32:
       KVQ_REQUIRE(a->out_f32, KVQ_ERR_NULL, "kvq_gemm_bf16: out_f32 NULL");
       KVQ_REQUIRE(!a->scatter_map || (a->map_rows > 0 && a->out_rows > 0), KVQ_ERR_SHAPE,
                   "kvq_gemm_bf16: scatter map needs map_rows/out_rows");
+      KVQ_REQUIRE(col_scale || a->epilogue == KVQ_EPI_RESID_F32, KVQ_ERR_NULL,
+                  "kvq_gemm_bf16: KVQ_EPI_RESID_SCALE_F32 takes its scale through kvq_gemm_resid_scaled");
+      if (col_scale) return launch_dt<KVQ_EPI_RESID_SCALE_F32>(a->dtype, p, st);
       return launch_dt<KVQ_EPI_RESID_F32>(a->dtype, p, st);
     case KVQ_EPI_STORE_F32:
       KVQ_REQUIRE(a->out_f32, KVQ_ERR_NULL, "kvq_gemm_bf16: out_f32 NULL");

@@ -78,6 +78,7 @@ KVQ_INST8P(KVQ_EPI_RESID_F32)
 KVQ_INST8P(KVQ_EPI_STORE_F32)
 KVQ_INST8P(KVQ_EPI_RELU_BF16)
 KVQ_INST8P(KVQ_EPI_QGELU_BF16)
+KVQ_INST8P(KVQ_EPI_RESID_SCALE_F32)      // ConvNeXt stage 3 (N = 768, K = 3072) fills the tile grid from 16 clips of 32 x 224 x 224
 
 // Which shapes take the wide tile.  A 256 x 256 tile keeps a CU at 5-7 TFLOP/s when its K loop is long enough to amortise the
 // 7-half-tile prologue and the epilogue; what it cannot do is fill the chip with few tiles.  KVQ_GEMM8P = 0: never, 1: whenever

@@ -38,6 +38,7 @@ struct GemmParams {
   int a_rows, a_phys_rows;
   RangeFlag range;             // fp16 KVQ_EPI_BIAS_BF16 writing the residual stream (an un-fused merge's reduction): the range detector
                                // of common.hpp over the stored halves; word NULL = off (the split-K reduction does not take it)
+  const float* col_scale;      // KVQ_EPI_RESID_SCALE_F32: fp32 [N] (kvq_gemm_resid_scaled; not part of KvqGemmArgs)
 };
 
 // ---- epilogue.  C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
@@ -60,6 +61,7 @@ struct GemmEpilogue {
   int col_in, row_hi, ch, rsub, n;
   bool col_live;
   float bias[CW];
+  float cscale[4];                                               // KVQ_EPI_RESID_SCALE_F32: col_scale of this lane's columns
   int which, head, e0;
   float scale;
   uint32_t rmax;                                                 // RANGE: packed magnitude max of the stored halves
@@ -83,6 +85,11 @@ struct GemmEpilogue {
     }
     which = 0; head = 0; e0 = 0; scale = 1.f;
     rmax = 0;
+    if (EPI == KVQ_EPI_RESID_SCALE_F32) {
+      const f32x4 s4 = col_live ? *reinterpret_cast<const f32x4*>(p.col_scale + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cscale[k] = s4[k];
+    }
     if (EPI == KVQ_EPI_QKV_BF16 && col_live) {                   // a 32-column tile = one head of q|k|v
       const int C = p.N / 3;
       which = n / C;
@@ -162,7 +169,7 @@ struct GemmEpilogue {
                          E::pack2(v[6 % CW], v[7 % CW])};
         *reinterpret_cast<u32x4*>(dst) = o;
         if (RANGE) rmax = range_fold(range_fold(range_fold(range_fold(rmax, o[0]), o[1]), o[2]), o[3]);   // in sequence: see range_fold
-      } else if (EPI == KVQ_EPI_RESID_F32) {
+      } else if (EPI == KVQ_EPI_RESID_F32 || EPI == KVQ_EPI_RESID_SCALE_F32) {
         long orow = m;
         if (p.scatter_map) {
           const int b = m / p.map_rows, rr = m - b * p.map_rows;
@@ -173,7 +180,7 @@ struct GemmEpilogue {
         f32x4* o = reinterpret_cast<f32x4*>(p.out_f32 + (size_t)orow * p.N + n);
         f32x4 x = *o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] += v[k];
+        for (int k = 0; k < 4; ++k) x[k] += EPI == KVQ_EPI_RESID_SCALE_F32 ? cscale[k] * v[k] : v[k];
         *o = x;
       } else {  // KVQ_EPI_STORE_F32 (split-K: partial tile of K range ksl)
         *reinterpret_cast<f32x4*>(p.out_f32 + ((size_t)ksl * p.M + m) * p.N + n) = (f32x4){v[0], v[1], v[2], v[3]};

@@ -217,17 +217,21 @@ class SyntheticKVQDataset(torch.utils.data.Dataset):
     """Seeded stand-in for ``ViewDecompositionDataset_KVQ``: item i is a uint8 frame stack drawn from
     PCG64(1234+i) sampled into the ``technical`` view on the GPU.  ``args``:
     ``num_videos, frames, height, width, labels (optional list), sample_types.technical.{fragments_h,
-    fragments_w, fsize_h, fsize_w, aligned, clip_len, frame_interval, num_clips}``."""
+    fragments_w, fsize_h, fsize_w, aligned, clip_len, frame_interval, num_clips}``.  An ``aesthetic`` entry in
+    ``sample_types`` (``size_h, size_w, clip_len, frame_interval, num_clips[, antialias]``: the resized view the ConvNeXt-3D
+    trunk reads) adds ``data["aesthetic"]`` through ``get_single_view``, from its own frame sampler as in the reference; with
+    it, ``technical`` may be left out."""
 
     def __init__(self, opt, namelist=None, device=None):
         self.opt, self.device = opt, _default_device(device)
         self.n = int(opt.get("num_videos", 8))
         self.frames, self.h, self.w = int(opt.get("frames", 256)), int(opt.get("height", 540)), int(opt.get("width", 960))
-        self.sopt = dict(opt["sample_types"]["technical"])
-        s = self.sopt
+        self.aopt = dict(opt["sample_types"]["aesthetic"]) if "aesthetic" in opt["sample_types"] else None
+        self.sopt = dict(opt["sample_types"]["technical"]) if ("technical" in opt["sample_types"] or self.aopt is None) else None
         # the reference passes (clip_len, num_clips, frame_interval) positionally (fusion_datasets.py:962-964):
         # num_clips lands in fragments_t, so T = clip_len * num_clips frames, split into clips by the harness
-        self.sampler = UnifiedFrameSampler(s["clip_len"], s.get("num_clips", 1), s.get("frame_interval", 1))
+        self.sampler, self.asampler = (None if s is None else UnifiedFrameSampler(s["clip_len"], s.get("num_clips", 1), s.get("frame_interval", 1))
+                                       for s in (self.sopt, self.aopt))
         g = np.random.Generator(np.random.PCG64(4321))
         self.labels = list(opt.get("labels") or g.uniform(1.0, 5.0, self.n))
 
@@ -244,12 +248,22 @@ class SyntheticKVQDataset(torch.utils.data.Dataset):
             np.random.seed(1234 + i)
             _pyrandom.seed(1234 + i)
             torch.manual_seed(1234 + i)
-        inds = self.sampler(self.frames)
-        clip = frames[:, torch.from_numpy(inds.astype(np.int64))].to(self.device)
-        tech = get_spatial_fragments(clip, s["fragments_h"], s["fragments_w"], s["fsize_h"], s["fsize_w"],
-                                     aligned=s.get("aligned", 8), mean=KVQ_MEAN, std=KVQ_STD, lazy=bool(s.get("lazy", False)))
-        return {"technical": tech, "num_clips": {"technical": s.get("num_clips", 1)}, "frame_inds": inds,
-                "label": float(self.labels[i]), "name": f"synthetic_{i:05d}", "video_name": f"synthetic_{i:05d}.mp4"}
+        item = {"num_clips": {}}
+        if s is not None:
+            inds = self.sampler(self.frames)
+            clip = frames[:, torch.from_numpy(inds.astype(np.int64))].to(self.device)
+            item["technical"] = get_spatial_fragments(clip, s["fragments_h"], s["fragments_w"], s["fsize_h"], s["fsize_w"],
+                                                      aligned=s.get("aligned", 8), mean=KVQ_MEAN, std=KVQ_STD, lazy=bool(s.get("lazy", False)))
+            item["num_clips"]["technical"] = s.get("num_clips", 1)
+            item["frame_inds"] = inds
+        if self.aopt is not None:
+            ainds = self.asampler(self.frames)
+            clip = frames[:, torch.from_numpy(ainds.astype(np.int64))].to(self.device)
+            item["aesthetic"] = get_single_view(clip, "aesthetic", mean=KVQ_MEAN, std=KVQ_STD, **self.aopt)
+            item["num_clips"]["aesthetic"] = self.aopt.get("num_clips", 1)
+            item.setdefault("frame_inds", ainds)
+        item.update(label=float(self.labels[i]), name=f"synthetic_{i:05d}", video_name=f"synthetic_{i:05d}.mp4")
+        return item
 
 
 # ------------------------------------------------------------------------------------------------------------------

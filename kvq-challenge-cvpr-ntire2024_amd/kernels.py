@@ -61,13 +61,19 @@ def _splitk_scratch(a, M: int, N: int, K: int, device):
 
 
 def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], epilogue: int, *, out=None,
-         num_heads=0, q_scale=1.0, scatter_map=None, map_rows=0, out_rows=0, a_gather=None, a_rows=0, rows=None):
+         num_heads=0, q_scale=1.0, scatter_map=None, map_rows=0, out_rows=0, a_gather=None, a_rows=0, rows=None, col_scale=None):
     """A [M,K], W [N,K], both fp16 or both bf16.  Returns the output tensor (allocated unless given).
+    ``col_scale`` (fp32 [N], residual epilogue only): out += col_scale * (A W^T + bias) — ``kvq_gemm_resid_scaled``.
     ``a_gather`` (+ ``a_rows``, ``rows`` = GEMM rows): row m reads A row (m // a_rows) * (A rows per batch) + a_gather[m % a_rows].
     QKV epilogue with ``scatter_map``: GEMM row m lands in row (m // map_rows) * out_rows + scatter_map[m % map_rows] of a buffer
     with out_rows rows per batch element (the other rows are ``qkv_fill_pad``'s)."""
-    _need_gpu(A, W, bias, out, scatter_map, a_gather)
+    _need_gpu(A, W, bias, out, scatter_map, a_gather, col_scale)
     assert A.dtype in HALF_TYPES and W.dtype == A.dtype and A.is_contiguous() and W.is_contiguous()
+    if col_scale is not None:
+        if epilogue not in (_abi.EPI_RESID_F32, _abi.EPI_RESID_SCALE_F32):
+            raise ValueError("col_scale belongs to the residual epilogue")
+        assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() == W.shape[0]
+        epilogue = _abi.EPI_RESID_SCALE_F32
     M, K = A.shape
     a_phys = 0
     if a_gather is not None:
@@ -95,7 +101,41 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], epilogu
     a.a_gather, a.a_rows, a.a_phys_rows = ptr(a_gather), a_rows, a_phys
     a.dtype = dtype_code(A.dtype)
     _ws = _splitk_scratch(a, a.M, a.N, a.K, A.device) if (a.epilogue != _abi.EPI_QKV_BF16 and a_gather is None) else None   # noqa: F841
-    check(lib().kvq_gemm_bf16(C.byref(a), current_stream()), "kvq_gemm_bf16")
+    if col_scale is not None:
+        check(lib().kvq_gemm_resid_scaled(C.byref(a), ptr(col_scale), current_stream()), "kvq_gemm_resid_scaled")
+    else:
+        check(lib().kvq_gemm_bf16(C.byref(a), current_stream()), "kvq_gemm_bf16")
+    return out
+
+
+def dwconv3d_ln_supported(C_: int, kt: int, T: int, H: int, W: int) -> bool:
+    return bool(lib().kvq_dwconv3d_ln_supported(C_, kt, T, H, W))
+
+
+def dwconv_weight_taps(w: torch.Tensor) -> torch.Tensor:
+    """Depthwise Conv3d weight (C, 1, kt, 7, 7) -> the tap-major fp32 [kt*7*7, C] that ``dwconv3d_ln`` streams."""
+    Cc = w.shape[0]
+    return w.reshape(Cc, -1).t().contiguous()
+
+
+def dwconv3d_ln(x: torch.Tensor, w_taps: torch.Tensor, bias, ln_w, ln_b, *, eps=1e-6, out_dtype=torch.float16):
+    """Depthwise (kt,7,7) conv (zero padding kt//2, 3, 3) + LayerNorm over C in one launch.  x fp32 channels-last (B, T, H, W, C),
+    w_taps fp32 [kt*49, C] (``dwconv_weight_taps``) -> rows [B*T*H*W, C] in ``out_dtype`` (fp16 / bf16 operand rows, or fp32)."""
+    _need_gpu(x, w_taps, bias, ln_w, ln_b)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5
+    assert w_taps.dtype == torch.float32 and w_taps.is_contiguous() and w_taps.shape[0] % 49 == 0
+    B, T, H, W, Cc = x.shape
+    kt = w_taps.shape[0] // 49
+    half = out_dtype in HALF_TYPES
+    a = _abi.KvqDwconvLnArgs()
+    a.x, a.w, a.bias, a.ln_w, a.ln_b = ptr(x), ptr(w_taps), ptr(bias), ptr(ln_w), ptr(ln_b)
+    a.B, a.T, a.H, a.W, a.C, a.kt, a.eps = B, T, H, W, Cc, kt, eps
+    if w_taps.shape[1] != Cc or not lib().kvq_dwconv3d_ln_supported(Cc, kt, T, H, W):
+        raise _abi.KvqError(f"kvq_dwconv3d_ln: unsupported shape (C={Cc}, kt={kt}, weight {tuple(w_taps.shape)}; C in 96/192/384/768, kt in 1/3)")
+    out = torch.empty(B * T * H * W, Cc, dtype=out_dtype, device=x.device)
+    a.dtype = dtype_code(out_dtype) if half else 0
+    a.out_h, a.out_f32 = (ptr(out), None) if half else (None, ptr(out))
+    check(lib().kvq_dwconv3d_ln(C.byref(a), current_stream()), "kvq_dwconv3d_ln")
     return out
 
 

@@ -47,7 +47,15 @@ class VQA_Network(nn.Module):  # noqa: N801  (reference spelling)
                                           frozen_stages=bk.get("frozen_stages", -1))
                 head = VQAHead(**(hypers.get("head") or {}))
             elif key == "conv_tiny":
-                raise NotImplementedError("model key 'conv_tiny' (ConvNeXt-3D) is outside the built scope (SURVEY.md §8)")
+                # the reference's key calls convnext_3d_tiny(pretrained=True) (model.py:49-50), which downloads ImageNet weights; an
+                # offline engine wants the choice spelled out
+                bk = hypers.get("backbone") or {}
+                if "pretrained" not in bk or bk["pretrained"] is True:
+                    raise NotImplementedError("conv_tiny: the reference downloads ImageNet weights from a URL here; set "
+                                              "backbone.pretrained to a local checkpoint or false")
+                from .backbones.conv_backbone import convnext_3d_tiny
+                backbone = convnext_3d_tiny(**bk)
+                head = VQAHead(**(hypers.get("head") or {}))
             else:
                 raise NotImplementedError
             self.key_names.append(key)

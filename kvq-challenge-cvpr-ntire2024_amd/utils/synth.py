@@ -16,6 +16,7 @@ Two schemes:
 """
 from __future__ import annotations
 
+import re
 import zlib
 from collections import OrderedDict
 from dataclasses import dataclass, field
@@ -150,6 +151,10 @@ def synth_resnet50_weights(seed: int = 0, scheme: str = "stress"):
     return synth_params(resnet50_param_shapes(), seed, scheme, prefix="resnet.")
 
 
+# the LayerNorms of ConvNeXt's downsample_layers (conv_backbone.py:368-378): index 1 of the stem, index 0 of the other three
+_CONVNEXT_DS_NORM = re.compile(r"downsample_layers\.(0\.1|[123]\.0)\.")
+
+
 def _draw(name: str, shape, seed: int, scheme: str) -> np.ndarray:
     g = _gen(seed, name)
     leaf = name.rsplit(".", 1)[-1]
@@ -160,7 +165,13 @@ def _draw(name: str, shape, seed: int, scheme: str) -> np.ndarray:
     if leaf == "running_var":
         return g.uniform(0.5, 1.5, shape).astype(np.float32) if scheme == "stress" else np.ones(shape, np.float32)
     is_norm = (".norm" in name or name.startswith("norm.") or ".bn" in name
-               or "downsample.1." in name)
+               or "downsample.1." in name or _CONVNEXT_DS_NORM.search(name) is not None)
+    if leaf == "gamma":        # ConvNeXt's layer scale (conv_backbone.py:171): the reference's initial value, or O(1) so that every block shows
+        if scheme == "init":
+            return np.full(shape, 1e-6, np.float32)
+        if scheme != "stress":
+            raise ValueError(f"unknown scheme {scheme!r}")
+        return g.uniform(0.5, 1.5, shape).astype(np.float32)
     if scheme == "init":
         if "position_bias_table" in name:
             return (g.standard_normal(shape) * 0.02).astype(np.float32)
@@ -187,6 +198,49 @@ def synth_params(shapes: Dict[str, Tuple[int, ...]], seed: int = 0, scheme: str 
                  prefix: str = "") -> "OrderedDict[str, np.ndarray]":
     """Draw every tensor in ``shapes`` from its own PCG64 stream (keyed by name)."""
     return OrderedDict((k, _draw(prefix + k, shp, seed, scheme)) for k, shp in shapes.items())
+
+
+def convnext_param_shapes(depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), inflate="131") -> "OrderedDict[str, Tuple[int, ...]]":
+    """state_dict key -> shape of the reference's ConvNeXt3D (conv_backbone.py:347-394), in its registration order."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    s["downsample_layers.0.0.weight"] = (dims[0], 3, 2, 4, 4)
+    s["downsample_layers.0.0.bias"] = (dims[0],)
+    s["downsample_layers.0.1.weight"] = (dims[0],)
+    s["downsample_layers.0.1.bias"] = (dims[0],)
+    for i in range(3):
+        s[f"downsample_layers.{i + 1}.0.weight"] = (dims[i],)
+        s[f"downsample_layers.{i + 1}.0.bias"] = (dims[i],)
+        s[f"downsample_layers.{i + 1}.1.weight"] = (dims[i + 1], dims[i], 1, 2, 2)
+        s[f"downsample_layers.{i + 1}.1.bias"] = (dims[i + 1],)
+    for i in range(4):
+        C = dims[i]
+        for j in range(depths[i]):
+            p = f"stages.{i}.{j}."
+            s[p + "gamma"] = (C,)
+            s[p + "dwconv.weight"] = (C, 1, int(inflate[j % len(inflate)]), 7, 7)
+            s[p + "dwconv.bias"] = (C,)
+            s[p + "norm.weight"] = (C,)
+            s[p + "norm.bias"] = (C,)
+            s[p + "pwconv1.weight"] = (4 * C, C)
+            s[p + "pwconv1.bias"] = (4 * C,)
+            s[p + "pwconv2.weight"] = (C, 4 * C)
+            s[p + "pwconv2.bias"] = (C,)
+    s["norm.weight"] = (dims[-1],)
+    s["norm.bias"] = (dims[-1],)
+    return s
+
+
+def synth_convnext_weights(seed: int = 0, scheme: str = "stress", depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), inflate="131"):
+    return synth_params(convnext_param_shapes(depths, dims, inflate), seed, scheme, prefix="convnext.")
+
+
+def synth_convnext2d_checkpoint(seed: int = 0, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768)):
+    """A 2D ConvNeXt state dict (what ``ConvNeXt3D.inflate_weights`` takes): the 3D keys with the depth axis of every conv weight
+    removed, plus the classifier head a real checkpoint carries and the 3D model ignores."""
+    shapes = OrderedDict((k, shp[:2] + shp[3:] if len(shp) == 5 else shp) for k, shp in convnext_param_shapes(depths, dims).items())
+    shapes["head.weight"] = (10, dims[-1])
+    shapes["head.bias"] = (10,)
+    return synth_params(shapes, seed, "stress", prefix="convnext2d.")
 
 
 def synth_swin_weights(cfg: SwinCfg = SWIN_T_GRPB, seed: int = 0, scheme: str = "stress"):
