@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "rows.hpp"
 #include "yuv.hpp"
 
 namespace kvq {
@@ -47,13 +48,11 @@ struct EmbedParams {
   float* out;                // [B*L0][E] fp32
   int out16;                 // round 6: the residual stream leaves as fp16 rows of 2 E bytes (same pointer)
   RangeFlag range;           // out16: range detector of the stream rows written (common.hpp), word NULL = off
-  const float* nn_w;         // first block's norm1 (EMIT)
-  const float* nn_b;
-  const int32_t* next_dst;   // token -> window row
-  uint16_t* next_ln;         // [B*next_rows][E]
-  int next_rows;
+  NextRows nr;               // the first block's norm1 rows (EMIT)
   float eps;
 };
+
+KVQ_NEXT_ROWS_ALIGNED(EmbedParams);
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(1))) const void* gbl_ptr_t;
@@ -104,7 +103,7 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   f32x4 nn_reg = {0.f, 0.f, 0.f, 0.f};
-  if (EMIT && tid < E / 2) nn_reg = *reinterpret_cast<const f32x4*>((tid < E / 4 ? p.nn_w : p.nn_b - E) + 4 * tid);
+  if (EMIT && tid < E / 2) nn_reg = *next_norm_piece<E>(p.nr, tid);
   constexpr int NQ = (WBYTES + 3 * E * 4 + 1023) / 1024;     // weights + parameters, 1 KB wave-loads
   for (int q = wave; q < NQ; q += 4)
     __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + q * 1024 + lane * 16), (lds_ptr_t)(lds + q * 1024), 16, 0, 0);
@@ -269,6 +268,7 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
         for (int e = 0; e < 4; ++e) acc[i][4 * q + e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
       }
   }
+  auto xv = [&](int i, int q) __attribute__((always_inline)) -> f32x4 { return (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]}; };
   if constexpr (STAGED) {
     // The wave's 32 tokens are 32 consecutive rows of the residual stream: one contiguous 32 * E * 4 bytes.  Stored from the
     // accumulator layout every store instruction touches 64 different rows (64 cycles in the texture addresser, 24 of them per
@@ -292,52 +292,26 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
       if (t < nrow) *reinterpret_cast<f32x4*>(gb + off) = v;
     }
   } else if (live && p.out16) {
-    uint16_t* o = reinterpret_cast<uint16_t*>(p.out) + (size_t)rc * E + 4 * h;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x2 v = {Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
-        *reinterpret_cast<u32x2*>(o + 32 * i + 8 * q) = v;
-        rmax = range_fold(range_fold(rmax, v[0]), v[1]);
-      }
+    rmax = stream_row_store<true, CM>(p.out, (size_t)rc * E + 4 * h, true, rmax, xv);
   } else if (live) {
-    float* o = p.out + (size_t)rc * E + 4 * h;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f32x4*>(o + 32 * i + 8 * q) =
-            (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
+    stream_row_store<false, CM>(p.out, (size_t)rc * E + 4 * h, true, rmax, xv);
   }
   if (p.out16 && p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   if (EMIT) {
     float mean, rstd;
     stats(mean, rstd);
-    // 16 bytes per lane: the lane pair (h = 0 | 1) of a token exchanges the 8-byte pieces of (q, q + 1) by v_permlane32_swap, lane h
-    // then owns channels 8 (2 t + h) .. + 7 of a tile — half the row-divergent store instructions (one row per cycle in the addresser)
-    const long drow = (long)b * p.next_rows + p.next_dst[tl];
-    uint16_t* o = p.next_ln + (size_t)drow * E;
+    const long drow = (long)b * p.nr.next_rows + p.nr.next_dst[tl];
+    uint16_t* o = p.nr.next_ln + (size_t)drow * E;
 #pragma unroll
     for (int i = 0; i < CM; ++i)
+      tile_store16_pairswap<E_, false>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
+        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + E + 32 * i + 8 * q + 4 * h);
+        f32x4 y;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        uint32_t pk[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int q = 2 * t + u;
-          const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + E + 32 * i + 8 * q + 4 * h);
-          float y[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) y[e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
-          pk[u][0] = E_::pack2(y[0], y[1]);
-          pk[u][1] = E_::pack2(y[2], y[3]);
-        }
-        const auto s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-        if (live) *reinterpret_cast<u32x4*>(o + 32 * i + 8 * (2 * t + h)) = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-      }
+        for (int e = 0; e < 4; ++e) y[e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
+        return y;
+      });
   }
   }      // tiles
 }
@@ -365,9 +339,9 @@ static int launch_embed(const EmbedParams& p, hipStream_t st) {
     return KVQ_OK;
   };
   int rc;
-  if (p.x == nullptr && p.frag.i420) rc = p.next_ln ? go(patch_embed_i420_kernel<E_, CM, KS, true>) : go(patch_embed_i420_kernel<E_, CM, KS, false>);
-  else if (p.x == nullptr) rc = p.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, true>) : go(patch_embed_kernel<E_, CM, KS, false, true>);
-  else rc = p.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, false>) : go(patch_embed_kernel<E_, CM, KS, false, false>);
+  if (p.x == nullptr && p.frag.i420) rc = p.nr.next_ln ? go(patch_embed_i420_kernel<E_, CM, KS, true>) : go(patch_embed_i420_kernel<E_, CM, KS, false>);
+  else if (p.x == nullptr) rc = p.nr.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, true>) : go(patch_embed_kernel<E_, CM, KS, false, true>);
+  else rc = p.nr.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, false>) : go(patch_embed_kernel<E_, CM, KS, false, false>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("patch_embed_kernel");
   return KVQ_OK;
@@ -423,10 +397,9 @@ int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStre
               "kvq_patch_embed: patch (%d,%d,%d) x %d channels -> %d on %dx%dx%d is not the fused shape", a->pd, a->ph, a->pw,
               a->in_chans, a->embed_dim, a->T, a->H, a->W);
   KVQ_REQUIRE(a->B > 0, KVQ_ERR_SHAPE, "kvq_patch_embed: B=%d", a->B);
-  KVQ_REQUIRE(!a->next_ln || (a->next_norm_w && a->next_norm_b && a->next_dst && a->next_rows > 0), KVQ_ERR_NULL,
-              "kvq_patch_embed: next_ln without its norm / map");
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_embed: dtype %d", a->dtype);
   EmbedParams p{};
+  if (int rc = next_rows_fill(p.nr, a, "kvq_patch_embed")) return rc;
+  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_embed: dtype %d", a->dtype);
   if (a->frag) {
     const KvqFragmentSource* f = a->frag;
     KVQ_REQUIRE(kvq_patch_embed_fragments_supported(f, a->B, a->in_chans, a->pd, a->T, a->H, a->W), KVQ_ERR_UNSUPPORTED,
@@ -445,8 +418,7 @@ int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStre
   }
   p.x = a->x; p.B = a->B; p.Cin = a->in_chans; p.T = a->T; p.H = a->H; p.W = a->W; p.pd = a->pd;
   p.D0 = a->T / a->pd; p.H0 = a->H / 4; p.W0 = a->W / 4;
-  p.pack = (const unsigned char*)a->pack; p.has_ln = a->has_norm; p.out = a->out; p.out16 = a->out_f16; p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b;
-  p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln; p.next_rows = a->next_rows; p.eps = a->eps;
+  p.pack = (const unsigned char*)a->pack; p.has_ln = a->has_norm; p.out = a->out; p.out16 = a->out_f16; p.eps = a->eps;
   if (a->out_f16) p.range = range;
   if (a->embed_dim == 96)
     return a->dtype == KVQ_DT_FP16 ? launch_embed<Fp16, 3, 6>(p, st) : launch_embed<Bf16, 3, 6>(p, st);

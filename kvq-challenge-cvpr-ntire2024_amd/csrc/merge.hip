@@ -16,6 +16,7 @@
 // A lane owns all 2C outputs of its token: the epilogue applies rstd, the two corrections, stores the fp32 residual stream of the
 // next stage and, in registers, the next block's norm1 row in ITS window order.
 #include "common.hpp"
+#include "rows.hpp"
 
 namespace kvq {
 
@@ -27,13 +28,11 @@ struct MergeParams {
   float* out;                // [B*Ln][2C]
   int x16, out16;            // round 6: x / out are fp16 residual streams (rows of 2 C / 4 C bytes behind the same pointers)
   RangeFlag range;           // out16: range detector of the stream rows written (common.hpp), word NULL = off
-  const float* nn_w;         // next block's norm1 (EMIT)
-  const float* nn_b;
-  const int32_t* next_dst;   // merged token -> window row
-  uint16_t* next_ln;         // [B*next_rows][2C]
-  int next_rows;
+  NextRows nr;               // the next stage's first norm1 rows (EMIT), [B*next_rows][2C]
   float eps;
 };
+
+KVQ_NEXT_ROWS_ALIGNED(MergeParams);
 
 typedef __attribute__((address_space(3))) void* mg_lds_t;
 typedef __attribute__((address_space(1))) const void* mg_gbl_t;
@@ -109,8 +108,7 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
     __builtin_amdgcn_global_load_lds((mg_gbl_t)(p.pack + G::WBYTES + q * 1024 + lane * 16), (mg_lds_t)(lds + 2 * CHUNK + q * 1024), 16, 0, 0);
   issue_chunk(0);
   if (NCH > 1) issue_chunk(1);
-  if (EMIT && tid < 2 * N / 4)
-    *reinterpret_cast<f32x4*>(s_nn + 4 * tid) = *reinterpret_cast<const f32x4*>((tid < N / 4 ? p.nn_w : p.nn_b - N) + 4 * tid);
+  if (EMIT && tid < 2 * N / 4) *reinterpret_cast<f32x4*>(s_nn + 4 * tid) = *next_norm_piece<N>(p.nr, tid);
 
   // this lane's merged token and its four neighbour rows (channels 8 h .. 8 h + 7 of every 16)
   const long total = (long)p.B * p.Ln;
@@ -255,33 +253,19 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
       }
     t2 += __shfl_xor(t2, 32);
     const float r2 = rsqrtf(t2 * (1.0f / (float)N) + p.eps);
-    // 16-bit rows leave as 16 bytes per lane: a lane pair (h = 0 | 1) holds 4 + 4 consecutive channels of every 8; the pair
-    // exchanges the 8-byte pieces of (q, q + 1) by v_permlane32_swap, lane h then owns channels 8 (2 t + h) .. + 7 — half the
-    // row-divergent store instructions
-    const long drow = (long)b * p.next_rows + p.next_dst[r];
-    uint16_t* o = p.next_ln + (size_t)drow * N;
+    const long drow = (long)b * p.nr.next_rows + p.nr.next_dst[r];
+    uint16_t* o = p.nr.next_ln + (size_t)drow * N;
 #pragma unroll
     for (int i = 0; i < CM; ++i)
+      tile_store16_pairswap<E, true>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
+        const f32x4 v = outv(i, q);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
+        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + N + 32 * i + 8 * q + 4 * h);
+        f32x4 y;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        uint32_t pk[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int q = 2 * t + u;
-          const f32x4 v = outv(i, q);
-          const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + N + 32 * i + 8 * q + 4 * h);
-          float y[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) y[e] = (v[e] - m2) * r2 * g[e] + be[e];
-          pk[u][0] = E::pack2(y[0], y[1]);
-          pk[u][1] = E::pack2(y[2], y[3]);
-        }
-        const auto s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-        if (live) *reinterpret_cast<u32x4*>(o + 32 * i + 8 * (2 * t + h)) = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-        __builtin_amdgcn_sched_barrier(0);
-      }
+        for (int e = 0; e < 4; ++e) y[e] = (v[e] - m2) * r2 * g[e] + be[e];
+        return y;
+      });
   }
 }
 
@@ -297,7 +281,7 @@ static int launch_merge(const MergeParams& p, hipStream_t st) {
     return KVQ_OK;
   };
   int rc;
-  if (p.next_ln) rc = p.x16 ? go(patch_merge_kernel<E, true, C_, true>) : go(patch_merge_kernel<E, true, C_, false>);
+  if (p.nr.next_ln) rc = p.x16 ? go(patch_merge_kernel<E, true, C_, true>) : go(patch_merge_kernel<E, true, C_, false>);
   else rc = p.x16 ? go(patch_merge_kernel<E, false, C_, true>) : go(patch_merge_kernel<E, false, C_, false>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("patch_merge_kernel");
@@ -354,13 +338,11 @@ int kvq::patch_merge_launch(const KvqPatchMergeArgs* a, RangeFlag range, hipStre
   KVQ_REQUIRE(a && a->x && a->merge_map && a->pack && a->out, KVQ_ERR_NULL, "kvq_patch_merge: NULL pointer");
   KVQ_REQUIRE(kvq_patch_merge_supported(a->C), KVQ_ERR_UNSUPPORTED, "kvq_patch_merge: C=%d is not a fused width", a->C);
   KVQ_REQUIRE(a->B > 0 && a->L > 0 && a->Ln > 0, KVQ_ERR_SHAPE, "kvq_patch_merge: B=%d L=%d Ln=%d", a->B, a->L, a->Ln);
-  KVQ_REQUIRE(!a->next_ln || (a->next_norm_w && a->next_norm_b && a->next_dst && a->next_rows > 0), KVQ_ERR_NULL,
-              "kvq_patch_merge: next_ln without its norm / map");
+  MergeParams p{};
+  if (int rc = next_rows_fill(p.nr, a, "kvq_patch_merge")) return rc;
   KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_merge: dtype %d", a->dtype);
   KVQ_REQUIRE((((size_t)a->x | (size_t)a->out | (size_t)a->merge_map) & 15) == 0, KVQ_ERR_SHAPE, "kvq_patch_merge: 16-byte aligned buffers");
-  MergeParams p{};
   p.x = a->x; p.map = a->merge_map; p.B = a->B; p.L = a->L; p.Ln = a->Ln; p.pack = (const unsigned char*)a->pack; p.out = a->out; p.x16 = a->x_f16; p.out16 = a->out_f16;
-  p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b; p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln; p.next_rows = a->next_rows;
   p.eps = a->eps;
   if (a->out_f16) p.range = range;
   return a->dtype == KVQ_DT_FP16 ? launch_merge_c<Fp16>(a->C, p, stream) : launch_merge_c<Bf16>(a->C, p, stream);

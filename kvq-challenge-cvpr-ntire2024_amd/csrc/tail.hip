@@ -152,7 +152,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
 
   // oldest in the queue: the next block's norm1 vectors (registers -> LDS below) and the fp32 parameters (DMA)
   f32x4 nn_reg = {0.f, 0.f, 0.f, 0.f};
-  if (EMIT && tid < C / 2) nn_reg = *reinterpret_cast<const f32x4*>((tid < C / 4 ? p.nn_w : p.nn_b - C) + 4 * tid);
+  if (EMIT && tid < C / 2) nn_reg = *next_norm_piece<C>(p.nr, tid);
   {
     const unsigned char* src = p.pack + (size_t)NI * SLOT;
     for (int q = wave; q < NQ; q += NW)      // uneven per wave is fine: these are OLDER than every counted item
@@ -398,29 +398,11 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
       for (int e = 0; e < 4; ++e) acc[i][4 * q + e] += fb[e];
       if (q & 1) __builtin_amdgcn_sched_barrier(0);
     }
+  auto xv = [&](int i, int q) __attribute__((always_inline)) -> f32x4 { return (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]}; };
   if (p.x16) {
-    uint16_t* xr = reinterpret_cast<uint16_t*>(p.x) + (size_t)orig * C + 4 * h;
-    uint32_t rmax = 0;                 // range detector: packed magnitude max of the stored halves
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32x2 v = {Fp16::pack2(acc[i][4 * q], acc[i][4 * q + 1]), Fp16::pack2(acc[i][4 * q + 2], acc[i][4 * q + 3])};
-        if (live) {
-          *reinterpret_cast<u32x2*>(xr + 32 * i + 8 * q) = v;
-          rmax = range_fold(range_fold(rmax, v[0]), v[1]);
-        }
-      }
+    const uint32_t rmax = stream_row_store<true, CM>(p.x, (size_t)orig * C + 4 * h, live, 0, xv);      // range detector: packed magnitude max of the stored halves
     if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
-  } else if (live) {
-    float* xr = p.x + (size_t)orig * C + 4 * h;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f32x4*>(xr + 32 * i + 8 * q) =
-            (f32x4){acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
-  }
+  } else stream_row_store<false, CM>(p.x, (size_t)orig * C + 4 * h, live, 0, xv);
   if (EMIT) {
     float s = 0.f;
 #pragma unroll
@@ -442,9 +424,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     float mu_n = mu;
     asm volatile("" : "+v"(mu_n));
     const float nmr2 = -mu_n * rs;
-    // 16 bytes per lane: the lane pair (h = 0 | 1) of a token exchanges the 8-byte pieces of (q, q + 1) by v_permlane32_swap, lane h
-    // then owns channels 8 (2 t + h) .. + 7 of a tile — half the row-divergent store instructions (one row per cycle in the addresser)
-    const long drow = (long)tb * p.next_rows + p.next_dst[tloc];
+    const long drow = (long)tb * p.nr.next_rows + p.nr.next_dst[tloc];
     if (QKV) {
       // ---- the next block's q | k | v (swin_backbone.py:252-260 of block b + 1): its norm1 row becomes the B operand in registers (k order
       // = accumulator order, as norm2's), then one 32-channel panel = one head of q, k or v at a time from 3C / 32 more ring panels ----
@@ -485,46 +465,23 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
           }
           const float sc = which == 0 ? p.q_scale : 1.f;
           uint16_t* o = p.qkv_out + ((size_t)(which * nH + head) * p.qkv_rows + (size_t)drow) * 32;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            uint32_t pk[2][2];
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-              const int q = 2 * t + v;
-              pk[v][0] = E::pack2(ha[4 * q] * sc, ha[4 * q + 1] * sc);
-              pk[v][1] = E::pack2(ha[4 * q + 2] * sc, ha[4 * q + 3] * sc);
-            }
-            const auto s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-            if (live) *reinterpret_cast<u32x4*>(o + 8 * (2 * t + h)) = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-          }
+          tile_store16_pairswap<E, false>(o, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
+            return (f32x4){ha[4 * q] * sc, ha[4 * q + 1] * sc, ha[4 * q + 2] * sc, ha[4 * q + 3] * sc};
+          });
         }
       }
     }
-    uint16_t* o = p.next_ln + (size_t)drow * C;
+    uint16_t* o = p.nr.next_ln + (size_t)drow * C;
 #pragma unroll
-    for (int i = 0; i < (QKV ? 0 : CM); ++i) {
+    for (int i = 0; i < (QKV ? 0 : CM); ++i)
+      tile_store16_pairswap<E, true>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
+        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + C + 32 * i + 8 * q + 4 * h);
+        f32x4 y;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        uint32_t pk[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int q = 2 * t + u;
-          const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + C + 32 * i + 8 * q + 4 * h);
-          float y[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs, nmr2), g[e], be[e]);
-          pk[u][0] = E::pack2(y[0], y[1]);
-          pk[u][1] = E::pack2(y[2], y[3]);
-        }
-        const auto s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-        const u32x4 piece = {s0[0], s1[0], s0[1], s1[1]};
-        if (live) *reinterpret_cast<u32x4*>(o + 32 * i + 8 * (2 * t + h)) = piece;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+        for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs, nmr2), g[e], be[e]);
+        return y;
+      });
   }
 #ifdef KVQ_TAIL_TRACE
   __builtin_amdgcn_s_waitcnt(0);
@@ -552,7 +509,7 @@ static int launch_tail(const TailParams& p, hipStream_t st) {
   if (p.qkv_out) {
     KVQ_REQUIRE((3 * C / 32) % 2 == 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: q | k | v emission with an odd panel count");
     rc = go(block_tail_kernel<E, CM, NW, 2>);
-  } else if (p.next_ln) rc = go(block_tail_kernel<E, CM, NW, 1>);
+  } else if (p.nr.next_ln) rc = go(block_tail_kernel<E, CM, NW, 1>);
   else rc = go(block_tail_kernel<E, CM, NW, 0>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("block_tail_kernel");
@@ -653,14 +610,12 @@ int kvq::block_tail_launch(const KvqBlockTailArgs* a, RangeFlag range, hipStream
   KVQ_REQUIRE(kvq_block_tail_supported(a->C, a->hidden), KVQ_ERR_UNSUPPORTED, "kvq_block_tail: C=%d hidden=%d", a->C,
               a->hidden);
   KVQ_REQUIRE(a->M > 0 && a->out_rows > 0 && (!a->scatter_map || a->map_rows > 0), KVQ_ERR_SHAPE, "kvq_block_tail: bad rows");
-  KVQ_REQUIRE(!a->next_ln || (a->next_norm_w && a->next_norm_b && a->next_dst && a->next_rows > 0), KVQ_ERR_NULL,
-              "kvq_block_tail: next_ln without its norm / map");
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: dtype %d", a->dtype);
   TailParams p{};
+  if (int rc = next_rows_fill(p.nr, a, "kvq_block_tail")) return rc;
+  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: dtype %d", a->dtype);
   p.attn = (const uint16_t*)a->attn; p.x = a->x; p.x16 = a->x_f16; p.map = a->scatter_map; p.map_rows = a->map_rows; p.out_rows = a->out_rows;
   p.M = a->M; p.hidden = a->hidden; p.pack = (const unsigned char*)a->pack;
-  p.nn_w = a->next_norm_w; p.nn_b = a->next_norm_b; p.next_dst = a->next_dst; p.next_ln = (uint16_t*)a->next_ln;
-  p.next_rows = a->next_rows; p.eps = a->eps; p.trace = g_trace; p.trace_blocks = g_trace_blocks;
+  p.eps = a->eps; p.trace = g_trace; p.trace_blocks = g_trace_blocks;
   if (a->x_f16) p.range = range;
   if (a->qkv_out) {
     KVQ_REQUIRE(kvq_block_tail_qkv_pack_bytes(a->C, a->hidden) > 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: C=%d cannot emit q | k | v", a->C);

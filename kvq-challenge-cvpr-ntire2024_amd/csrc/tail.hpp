@@ -2,6 +2,7 @@
 // post-attention launch and the entry points of the wide variant.
 #pragma once
 #include "common.hpp"
+#include "rows.hpp"
 
 namespace kvq {
 
@@ -14,11 +15,7 @@ struct TailParams {
   int n_tok;
   int map_rows, out_rows, M, hidden;
   const unsigned char* pack; // kvq_block_tail_pack image
-  const float* nn_w;         // next block's norm1 (EMIT)
-  const float* nn_b;
-  const int32_t* next_dst;   // token -> window row of the next block's partition
-  uint16_t* next_ln;         // [n_batch*next_rows][C]
-  int next_rows;
+  NextRows nr;               // the next block's norm1 rows (EMIT); with qkv_out its norm and map alone (next_ln NULL)
   // instead of next_ln: the next block's q | k | v, head-major [3][nH][n_batch*next_rows][32] in ITS window order (tailmm.hip, round 5)
   const unsigned char* qkv_pack;   // kvq_block_tail_qkv_pack image of the NEXT block's qkv weight
   const float* qkv_b;              // [3C]
@@ -31,6 +28,8 @@ struct TailParams {
   unsigned long long* trace;   // diagnostic stamps (kvq_debug_gemm_trace; -DKVQ_TAIL_TRACE builds only)
   int trace_blocks;
 };
+
+KVQ_NEXT_ROWS_ALIGNED(TailParams);
 
 // csrc/tailmm.hip: the same launch for C = 256 / 384 / 512 as a register-blocked 32x32x16 GEMM chain
 bool tailmm_supported(int C, int hidden);

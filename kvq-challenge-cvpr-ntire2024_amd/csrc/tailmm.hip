@@ -583,43 +583,31 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
 
   MM_STAMP(3);
   // ---- write the residual stream back; optionally the next block's norm1 rows in ITS window order ----------------------
+  auto xv = [&](int tt, int ft, int q) __attribute__((always_inline)) -> f32x4 {
+    return (f32x4){acc[ft][tt][4 * q], acc[ft][tt][4 * q + 1], acc[ft][tt][4 * q + 2], acc[ft][tt][4 * q + 3]};
+  };
   if (p.x16) {
     uint32_t rmax = 0;                 // range detector: packed magnitude max of the stored halves
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
-      if (live[tt]) {
-        uint16_t* xr = reinterpret_cast<uint16_t*>(p.x) + (size_t)orig[tt] * C + FW * wave + 4 * half;
-#pragma unroll
-        for (int ft = 0; ft < CF; ++ft)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const u32x2 v = {Fp16::pack2(acc[ft][tt][4 * q], acc[ft][tt][4 * q + 1]), Fp16::pack2(acc[ft][tt][4 * q + 2], acc[ft][tt][4 * q + 3])};
-            *reinterpret_cast<u32x2*>(xr + 32 * ft + 8 * q) = v;
-            rmax = range_fold(range_fold(rmax, v[0]), v[1]);
-          }
-      }
+      if (live[tt]) rmax = stream_row_store<true, CF>(p.x, (size_t)orig[tt] * C + FW * wave + 4 * half, true, rmax,
+                                                         [&](int ft, int q) __attribute__((always_inline)) -> f32x4 { return xv(tt, ft, q); });
     if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   } else
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt)
-    if (live[tt]) {
-      float* xr = p.x + (size_t)orig[tt] * C + FW * wave + 4 * half;
-#pragma unroll
-      for (int ft = 0; ft < CF; ++ft)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<f32x4*>(xr + 32 * ft + 8 * q) = (f32x4){acc[ft][tt][4 * q], acc[ft][tt][4 * q + 1], acc[ft][tt][4 * q + 2], acc[ft][tt][4 * q + 3]};
-    }
+    if (live[tt]) stream_row_store<false, CF>(p.x, (size_t)orig[tt] * C + FW * wave + 4 * half, true, 0,
+                                                [&](int ft, int q) __attribute__((always_inline)) -> f32x4 { return xv(tt, ft, q); });
   if (QKV) {
     // ---- the next block's q | k | v (swin_backbone.py:252-260 of block b + 1): norm1 rows -> B fragments in the activation tile (every
     // wave is past its last read of the norm2 rows: the barrier behind the last fc1), then three passes of the proj-shaped GEMM phase
     // over the wave's feature slice of q, k and v; a 32-feature tile is one head.  Rows leave head-major in the next block's window order.
     TV mean, rstd;
     token_stats(mean, rstd);
-    write_norm(mean, rstd, p.nn_w, p.nn_b, lds + MM_OFF_X);
+    write_norm(mean, rstd, p.nr.nn_w, p.nr.nn_b, lds + MM_OFF_X);
     long drow[TT];
 #pragma unroll
-    for (int tt = 0; tt < TT; ++tt) drow[tt] = (long)tb_[tt] * p.next_rows + p.next_dst[tloc_[tt]];
+    for (int tt = 0; tt < TT; ++tt) drow[tt] = (long)tb_[tt] * p.nr.next_rows + p.nr.next_dst[tloc_[tt]];
     MM_BARRIER();                                      // norm1 rows complete
 #pragma unroll 1
     for (int which = 0; which < 3; ++which) {
@@ -635,7 +623,8 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
         }
       gemm_phase(T3{}, KC{}, lds + MM_OFF_X, [&](int ft, int tt, V8 a, V8 b) { acc[ft][tt] = E::mfma32(a, b, acc[ft][tt]); }, nothing);
       const float sc = which == 0 ? p.q_scale : 1.f;
-      // as the norm1 rows below: the lane pair of a token swaps 8-byte pieces, lane `half` then owns head dims 8 (2 t + half) .. + 7
+      // the pair swap of rows.hpp's tile_store16_pairswap, written out here and for the norm1 rows below: through the helper these kernels
+      // come out of another length (profiles/rows_refactor_isa.txt); lane `half` owns head dims / features 8 (2 t + half) .. + 7 of a tile
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -660,12 +649,10 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
   if (EMIT) {
     TV mean, rstd;
     token_stats(mean, rstd);
-    // 16 bytes per lane: the lane pair (half = 0 | 1) of a token exchanges the 8-byte pieces of (q, q + 1) by v_permlane32_swap, lane
-    // `half` then owns features 8 (2 t + half) .. + 7 of a tile — half the row-divergent store instructions
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
-      const long drow = (long)tb_[tt] * p.next_rows + p.next_dst[tloc_[tt]];
-      uint16_t* o = p.next_ln + (size_t)drow * C + FW * wave;
+      const long drow = (long)tb_[tt] * p.nr.next_rows + p.nr.next_dst[tloc_[tt]];
+      uint16_t* o = p.nr.next_ln + (size_t)drow * C + FW * wave;
 #pragma unroll
       for (int ft = 0; ft < CF; ++ft)
 #pragma unroll
@@ -675,7 +662,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
           for (int u = 0; u < 2; ++u) {
             const int q = 2 * t + u;
             const int f0 = FW * wave + 32 * ft + 8 * q + 4 * half;
-            const f32x4 gm = *reinterpret_cast<const f32x4*>(p.nn_w + f0), be = *reinterpret_cast<const f32x4*>(p.nn_b + f0);
+            const f32x4 gm = *reinterpret_cast<const f32x4*>(p.nr.nn_w + f0), be = *reinterpret_cast<const f32x4*>(p.nr.nn_b + f0);
             float y[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[i] = fmaf(fmaf(acc[ft][tt][4 * q + i], rstd[tt], -mean[tt] * rstd[tt]), gm[i], be[i]);
@@ -711,7 +698,7 @@ static int launch_mm_cf(const TailParams& p, hipStream_t st) {
   };
   int rc;
   if (p.qkv_out) rc = go(block_tailmm_kernel<E, 2, CF, HC>);
-  else if (p.next_ln) rc = go(block_tailmm_kernel<E, 1, CF, HC>);
+  else if (p.nr.next_ln) rc = go(block_tailmm_kernel<E, 1, CF, HC>);
   else rc = go(block_tailmm_kernel<E, 0, CF, HC>);
   if (rc) return rc;
   KVQ_CHECK_LAUNCH("block_tailmm_kernel");

@@ -1121,6 +1121,11 @@ def block_tail_qkv_pack(qkv_w: torch.Tensor, hidden: int):
     return pack
 
 
+def _set_next(a, next_norm, next_dst, next_rows):
+    """the next block's norm1 and window map on the args struct of a launch that emits its rows (next_ln / qkv_out: the caller's)"""
+    a.next_norm_w, a.next_norm_b, a.next_dst, a.next_rows = ptr(next_norm[0]), ptr(next_norm[1]), ptr(next_dst), next_rows
+
+
 def block_tail(attn: torch.Tensor, x: torch.Tensor, pack: torch.Tensor, hidden: int, *, scatter_map=None, map_rows=0,
                out_rows=0, next_norm=None, next_dst=None, next_rows=0, eps=1e-5, attn_gather=None, next_qkv=None):
     """x (fp32 [n_batch*out_rows, C], in place — or fp16 at C <= 192: the round-6 residual stream of stages 0-1, ``x_f16``)
@@ -1138,7 +1143,7 @@ def block_tail(attn: torch.Tensor, x: torch.Tensor, pack: torch.Tensor, hidden: 
     nxt = None
     if next_norm is not None:
         n_batch = x.shape[0] // a.out_rows
-        a.next_norm_w, a.next_norm_b, a.next_dst, a.next_rows = ptr(next_norm[0]), ptr(next_norm[1]), ptr(next_dst), next_rows
+        _set_next(a, next_norm, next_dst, next_rows)
         if next_qkv is not None:
             nxt = torch.empty(3, Cc // 32, n_batch * next_rows, 32, dtype=attn.dtype, device=x.device)
             a.next_qkv_pack, a.next_qkv_b, a.qkv_out, a.q_scale, a.num_heads = ptr(next_qkv[0]), ptr(next_qkv[1]), ptr(nxt), float(next_qkv[2]), Cc // 32
@@ -1182,8 +1187,8 @@ def patch_embed(x, w: torch.Tensor, bias, ln_w, ln_b, patch, *, next_norm=None, 
     nxt = None
     if next_norm is not None:
         nxt = torch.empty(B * next_rows, Ed, dtype=w.dtype, device=x.device)
-        a.next_norm_w, a.next_norm_b, a.next_dst, a.next_ln, a.next_rows = (ptr(next_norm[0]), ptr(next_norm[1]),
-                                                                            ptr(next_dst), ptr(nxt), next_rows)
+        _set_next(a, next_norm, next_dst, next_rows)
+        a.next_ln = ptr(nxt)
     check(lib().kvq_patch_embed(C.byref(a), current_stream()), "kvq_patch_embed")
     return out, nxt
 
@@ -1211,8 +1216,8 @@ def patch_merge(x: torch.Tensor, merge_map: torch.Tensor, n_batch: int, red_w: t
     nxt = None
     if next_norm is not None:
         nxt = torch.empty(n_batch * next_rows, 2 * Cc, dtype=out_dtype, device=x.device)
-        a.next_norm_w, a.next_norm_b, a.next_dst, a.next_ln, a.next_rows = (ptr(next_norm[0]), ptr(next_norm[1]), ptr(next_dst),
-                                                                            ptr(nxt), next_rows)
+        _set_next(a, next_norm, next_dst, next_rows)
+        a.next_ln = ptr(nxt)
     check(lib().kvq_patch_merge(C.byref(a), current_stream()), "kvq_patch_merge")
     return out, nxt
 
