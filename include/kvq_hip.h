@@ -349,6 +349,33 @@ typedef struct {
 int kvq_dwconv3d_ln_supported(int C, int kt, int T, int H, int W);
 int kvq_dwconv3d_ln(const KvqDwconvLnArgs* host_args, void* stream);
 
+/* Global Response Normalization between the two pointwise GEMMs of a ConvNeXt-V2 3D block (csrc/grn.hip): BlockV23D.grn of the
+ * reference (conv_backbone.py:7-18, :245).  x: the 16-bit rows [B*D*H*W][N] the GELU GEMM writes, tokens in (b, d, h, w) order.
+ *   Gx[b][w][n] = sqrt(sum over (d, h) of x^2)      over_w = 0, the reference: its 2D GRN module reduces dim=(1, 2) of (N, T, H, W, C)
+ *   Gx[b][n]    = sqrt(sum over (d, h, w) of x^2)   over_w = 1, the GRN of the ConvNeXt-V2 paper carried to 3D
+ *   y = round16(x * (1 + gamma[n] * Gx / (mean over n of Gx + 1e-6)) + beta[n])
+ * kvq_grn_stats enqueues two launches (fp32 partial sums of squares over chunks of (d, h) rows; then per (b, w) the chunk sums in
+ * ascending order, the roots, the mean over n, and scale = 1 + gamma * Nx into ws; over_w: a third adds the sums over w),
+ * kvq_grn_apply one (streams x, writes y).  fp32 arithmetic, no atomics, no counters: two runs are bit-equal and a sample's result does
+ * not depend on the batch it is in; an all-zero slab gives Nx = 0.  Shapes: N in {384, 768, 1536, 3072}, any
+ * D, H, W >= 1 (kvq_grn_supported, host only, 1 / 0), B, W <= 65535; anything else returns KVQ_ERR_UNSUPPORTED / KVQ_ERR_SHAPE
+ * without a launch.  x, y, ws, gamma and beta are 16-byte aligned.  Both calls take the same struct; ws carries the result of the first to the
+ * second and is not read afterwards. */
+typedef struct {
+  const uint16_t* x;    /* 16-bit rows [B*D*H*W][N]                                                  */
+  uint16_t* y;          /* output rows, or NULL: in place                                            */
+  const float* gamma;   /* GRN gamma / beta [N]                                                      */
+  const float* beta;
+  float* ws;            /* kvq_grn_workspace_bytes(B, D, H, W, N) bytes of device memory             */
+  int32_t B, D, H, W, N;
+  int32_t dtype;        /* KvqDtype of x and y                                                       */
+  int32_t over_w;       /* 0: statistics over (d, h) per w column; 1: over (d, h, w)                 */
+} KvqGrnArgs;
+int kvq_grn_supported(int N, int D, int H, int W);
+size_t kvq_grn_workspace_bytes(int B, int D, int H, int W, int N);
+int kvq_grn_stats(const KvqGrnArgs* host_args, void* stream);
+int kvq_grn_apply(const KvqGrnArgs* host_args, void* stream);
+
 /* PatchEmbed3D (swin_backbone.py:715-733) as one launch, token-per-lane MFMA (csrc/embed.hip): the strided
  * Conv3d reads its patches straight from the clip (no im2col buffer), + bias + LayerNorm(E), optionally + the
  * first block's norm1 in its window order.  Fused shape: patch (pd,4,4), in_chans*pd == 6, E in {96,128}, clip

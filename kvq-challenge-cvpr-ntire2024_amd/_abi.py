@@ -91,6 +91,11 @@ class KvqDwconvLnArgs(C.Structure):
                 ("out_h", p_void), ("out_f32", p_void)]
 
 
+class KvqGrnArgs(C.Structure):
+    _fields_ = [("x", p_void), ("y", p_void), ("gamma", p_void), ("beta", p_void), ("ws", p_void), ("B", C.c_int32), ("D", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("N", C.c_int32), ("dtype", C.c_int32), ("over_w", C.c_int32)]
+
+
 class KvqNetTensor(C.Structure):
     _fields_ = [("B", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("kind", C.c_int32)]
 
@@ -218,6 +223,10 @@ SYMBOLS = {
     "kvq_gemm_resid_scaled": (i32, [C.POINTER(KvqGemmArgs), p_void, p_void]),
     "kvq_dwconv3d_ln_supported": (i32, [i32] * 5),
     "kvq_dwconv3d_ln": (i32, [C.POINTER(KvqDwconvLnArgs), p_void]),
+    "kvq_grn_supported": (i32, [i32] * 4),
+    "kvq_grn_workspace_bytes": (sz, [i32] * 5),
+    "kvq_grn_stats": (i32, [C.POINTER(KvqGrnArgs), p_void]),
+    "kvq_grn_apply": (i32, [C.POINTER(KvqGrnArgs), p_void]),
     "kvq_gemm_splitk_factor": (i32, [i32, i32, i32]),
     "kvq_gemm_splitk_bytes": (sz, [i32, i32, i32]),
     "kvq_debug_gemm_trace": (i32, [p_void, i32]),

@@ -139,6 +139,36 @@ def dwconv3d_ln(x: torch.Tensor, w_taps: torch.Tensor, bias, ln_w, ln_b, *, eps=
     return out
 
 
+def grn_supported(N: int, D: int, H: int, W: int) -> bool:
+    return bool(lib().kvq_grn_supported(N, D, H, W))
+
+
+def grn(hid: torch.Tensor, shape, gamma, beta, *, over="th", out=None):
+    """Global Response Normalization of the 16-bit rows ``hid`` [B*D*H*W, N] (tokens in (b, d, h, w) order, ``shape`` = (B, D, H, W)):
+    ``x * (1 + gamma * Nx) + beta`` with ``Nx = Gx / (mean_n Gx + 1e-6)`` and ``Gx`` the L2 norm over (d, h) per (b, w, n) —
+    ``over="th"``, what the reference's BlockV23D computes — or over (d, h, w) per (b, n) — ``over="thw"``.  In place unless ``out`` is
+    given; returns the tensor written.  gamma / beta: fp32 with N elements (any shape)."""
+    _need_gpu(hid, gamma, beta)
+    if over not in ("th", "thw"):
+        raise ValueError(f"grn: over must be 'th' or 'thw', got {over!r}")
+    B, D, H, W = (int(v) for v in shape)
+    assert hid.dtype in HALF_TYPES and hid.is_contiguous() and hid.dim() == 2 and hid.shape[0] == B * D * H * W
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and beta.is_contiguous()
+    N = hid.shape[1]
+    if gamma.numel() != N or beta.numel() != N or not lib().kvq_grn_supported(N, D, H, W):
+        raise _abi.KvqError(f"kvq_grn: unsupported shape (N={N}, (B, D, H, W)={(B, D, H, W)}, gamma {tuple(gamma.shape)}; "
+                            "N in 384/768/1536/3072)")
+    y = hid if out is None else out
+    assert y.dtype == hid.dtype and y.shape == hid.shape and y.is_contiguous()
+    ws = torch.empty(lib().kvq_grn_workspace_bytes(B, D, H, W, N) // 4, dtype=torch.float32, device=hid.device)
+    a = _abi.KvqGrnArgs()
+    a.x, a.y, a.gamma, a.beta, a.ws = ptr(hid), (None if out is None else ptr(out)), ptr(gamma), ptr(beta), ptr(ws)
+    a.B, a.D, a.H, a.W, a.N, a.dtype, a.over_w = B, D, H, W, N, dtype_code(hid.dtype), int(over == "thw")
+    check(lib().kvq_grn_stats(C.byref(a), current_stream()), "kvq_grn_stats")
+    check(lib().kvq_grn_apply(C.byref(a), current_stream()), "kvq_grn_apply")
+    return y
+
+
 def gemm_tile_mode(mode: int) -> int:
     """-1: main loop by shape (default), 0: never the 256 x 256 eight-phase tile, 1: whenever eligible.  Returns the previous mode."""
     return lib().kvq_gemm_tile_mode(mode)

@@ -56,6 +56,11 @@ class VQA_Network(nn.Module):  # noqa: N801  (reference spelling)
                 from .backbones.conv_backbone import convnext_3d_tiny
                 backbone = convnext_3d_tiny(**bk)
                 head = VQAHead(**(hypers.get("head") or {}))
+            elif key == "conv_v2_tiny":
+                # the reference's V2 factories never download (conv_backbone.py:603-625): a missing ``pretrained`` means false
+                from .backbones.conv_backbone import convnextv2_3d_tiny
+                backbone = convnextv2_3d_tiny(**(hypers.get("backbone") or {}))
+                head = VQAHead(**(hypers.get("head") or {}))
             else:
                 raise NotImplementedError
             self.key_names.append(key)

@@ -113,8 +113,8 @@ class Trainer:
         ksvqe = self.config["model"]["type"] == "KSVQE"
         # KSVQE reads resize_video / fragment / dis_label only (key_list = ['KSVQE'], trainer.py:56,259-260): the 'technical'
         # view (the same pixels as 'fragment', ~95 MB fp32 per 96-frame sample) is neither reshaped nor copied
-        # the ConvNeXt-3D trunk (model key conv_tiny) reads the 'aesthetic' view
-        views = ("technical", "aesthetic") if "conv_tiny" in self.key_list else ("technical",)
+        # the ConvNeXt-3D trunks (model keys conv_tiny, conv_v2_tiny) read the 'aesthetic' view
+        views = ("technical", "aesthetic") if ("conv_tiny" in self.key_list or "conv_v2_tiny" in self.key_list) else ("technical",)
         for key in ([] if ksvqe else list(data)):
             if key in self.key_list or key in views:
                 x = data[key]

@@ -243,6 +243,55 @@ def synth_convnext2d_checkpoint(seed: int = 0, depths=(3, 3, 9, 3), dims=(96, 19
     return synth_params(shapes, seed, "stress", prefix="convnext2d.")
 
 
+def convnextv2_param_shapes(depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), inflate="131", num_classes=1000):
+    """state_dict key -> shape of the reference's ConvNeXtV23D (conv_backbone.py:437-485), in its registration order: no layer scale,
+    ``grn.gamma`` / ``grn.beta`` (1, 1, 1, 4C) between pwconv1 and pwconv2, and the classifier ``head`` behind the final norm."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    for k, shp in convnext_param_shapes(depths, dims, inflate).items():
+        if k.endswith(".gamma"):
+            continue
+        if k.endswith(".pwconv2.weight"):
+            s[k[:-len("pwconv2.weight")] + "grn.gamma"] = (1, 1, 1, shp[1])
+            s[k[:-len("pwconv2.weight")] + "grn.beta"] = (1, 1, 1, shp[1])
+        s[k] = shp
+    s["head.weight"] = (num_classes, dims[-1])
+    s["head.bias"] = (num_classes,)
+    return s
+
+
+def _draw_convnextv2(shapes, seed, scheme, prefix):
+    """``synth_params`` with GRN's own rule: the reference's zeros for "init"; for "stress" an O(1) gamma and a non-zero beta, so that
+    the GRN term is visible in every block."""
+    out = OrderedDict()
+    for k, shp in shapes.items():
+        leaf = k.rsplit(".", 1)[-1]
+        if ".grn." in k:
+            if scheme == "init":
+                out[k] = np.zeros(shp, np.float32)
+            elif scheme == "stress":
+                g = _gen(seed, prefix + k)
+                out[k] = (g.uniform(0.5, 1.5, shp) * g.choice([-1.0, 1.0], shp) if leaf == "gamma"
+                          else 0.2 * g.standard_normal(shp)).astype(np.float32)
+            else:
+                raise ValueError(f"unknown scheme {scheme!r}")
+        else:
+            out[k] = _draw(prefix + k, shp, seed, scheme)
+    return out
+
+
+def synth_convnextv2_weights(seed: int = 0, scheme: str = "stress", depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), inflate="131",
+                             num_classes=1000):
+    return _draw_convnextv2(convnextv2_param_shapes(depths, dims, inflate, num_classes), seed, scheme, "convnextv2.")
+
+
+def synth_convnextv2_2d_checkpoint(seed: int = 0, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), num_classes=1000):
+    """A 2D ConvNeXt-V2 state dict (what ``ConvNeXtV23D.inflate_weights`` finds under ``"model"``): the 3D keys with the depth axis of
+    every conv weight removed; GRN parameters and the head have the 3D model's shapes already."""
+    shapes = OrderedDict((k, shp[:2] + shp[3:] if len(shp) == 5 else shp)
+                         for k, shp in convnextv2_param_shapes(depths, dims, num_classes=num_classes).items())
+    return _draw_convnextv2(shapes, seed, "stress", "convnextv2_2d.")
+
+
 def synth_swin_weights(cfg: SwinCfg = SWIN_T_GRPB, seed: int = 0, scheme: str = "stress"):
     return synth_params(swin_param_shapes(cfg), seed, scheme)
 
