@@ -269,13 +269,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void window_attention_kernel(Att
 
 template <typename E, bool GATED, bool MASK, bool FULL>
 static int launch_attn2(const AttnParams& p, size_t lds, hipStream_t st) {
-  auto kern = window_attention_kernel<E, GATED, MASK, FULL>;
-  static LdsOptIn opt;            // per instantiation and device: opt in to > 64 KiB of dynamic LDS once
-  if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), (int)lds)) return rc;
-  dim3 grid((unsigned)(p.BW * p.nH)), block(ATT_WAVES * 64);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, p);
-  KVQ_CHECK_LAUNCH("window_attention_kernel");
-  return KVQ_OK;
+  return launch("window_attention_kernel", window_attention_kernel<E, GATED, MASK, FULL>, dim3((unsigned)(p.BW * p.nH)), dim3(ATT_WAVES * 64), lds, st,
+                p);
 }
 
 template <typename E, bool GATED, bool MASK>
@@ -302,15 +297,12 @@ extern "C" int kvq_window_attention(const uint16_t* qkv, const int32_t* tok, con
   AttnParams p{qkv, tok, rpb, fpb, bias_pack, table_len, center, BW, nW, N, num_heads, use_mask, out, g_trace, g_trace_blocks};
   hipStream_t st = (hipStream_t)stream;
   const bool gated = fpb != nullptr, mask = use_mask != 0;
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_window_attention: dtype %d", dtype);
-  if (dtype == KVQ_DT_FP16) {
-    if (gated && mask) return launch_attn<Fp16, true, true>(p, lds, st);
-    if (gated) return launch_attn<Fp16, true, false>(p, lds, st);
-    if (mask) return launch_attn<Fp16, false, true>(p, lds, st);
-    return launch_attn<Fp16, false, false>(p, lds, st);
-  }
-  if (gated && mask) return launch_attn<Bf16, true, true>(p, lds, st);
-  if (gated) return launch_attn<Bf16, true, false>(p, lds, st);
-  if (mask) return launch_attn<Bf16, false, true>(p, lds, st);
-  return launch_attn<Bf16, false, false>(p, lds, st);
+  KVQ_REQUIRE_OPERAND("kvq_window_attention", dtype);
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    if (gated && mask) return launch_attn<E, true, true>(p, lds, st);
+    if (gated) return launch_attn<E, true, false>(p, lds, st);
+    if (mask) return launch_attn<E, false, true>(p, lds, st);
+    return launch_attn<E, false, false>(p, lds, st);
+  });
 }

@@ -595,15 +595,10 @@ __global__ __launch_bounds__(256) void bias32_build_kernel(Bias32BuildParams p) 
 
 template <typename E, bool FUSED, int MODE, bool SHORT>
 static int launch_attn32_form(const Attn32Params& p, hipStream_t st) {
-  auto kern = window_attention32_kernel<E, FUSED, MODE, SHORT>;
-  LdsOptIn opt;
-  if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), A32_LDS)) return rc;
   const int nclip = p.BW / p.nW, nrep = p.nW / p.n_types, npair = p.n_types * p.nH;
   unsigned grid = (unsigned)(8 * ceil_div(npair, 8) * nclip * nrep * p.qsplit);
   if (FUSED) grid = (unsigned)(8 * ceil_div(p.n_types, 8) * p.nH * nclip * nrep);      // XCDs take whole window types
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(A32_WAVES * 64), A32_LDS, st, p);
-  KVQ_CHECK_LAUNCH("window_attention32_kernel");
-  return KVQ_OK;
+  return launch("window_attention32_kernel", window_attention32_kernel<E, FUSED, MODE, SHORT>, dim3(grid), dim3(A32_WAVES * 64), A32_LDS, st, p);
 }
 
 template <typename E, bool FUSED, int MODE>
@@ -636,9 +631,7 @@ extern "C" int kvq_attn_bias32_build(const int32_t* tok, const float* rpb, const
   Bias32BuildParams p{tok, rpb, fpb, table_len, center, nW, N, num_heads, use_mask, (uint16_t*)out, (unsigned*)max_abs};
   const size_t lds = (size_t)table_len * 8 + (size_t)N * 12;
   KVQ_REQUIRE(lds <= 64 * 1024, KVQ_ERR_UNSUPPORTED, "kvq_attn_bias32_build: table of %d entries does not fit the builder's LDS", table_len);
-  hipLaunchKernelGGL(bias32_build_kernel, dim3((unsigned)num_heads, (unsigned)nW), dim3(256), lds, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("bias32_build_kernel");
-  return KVQ_OK;
+  return launch("bias32_build_kernel", bias32_build_kernel, dim3((unsigned)num_heads, (unsigned)nW), dim3(256), lds, stream, p);
 }
 
 // ---- region order and key ranges of shifted windows (host; the plan's and the tests' one source of both) ------------------------------
@@ -692,7 +685,7 @@ static int window_attention32(const char* who, const KvqAttnDenseArgs* a, const 
               "%s: bad shape BW=%d nW=%d n_types=%d nH=%d", who, BW, nW, n_types, num_heads);
   KVQ_REQUIRE(N >= 1 && N <= 400, KVQ_ERR_UNSUPPORTED, "%s: window of %d tokens unsupported (1..400)", who, N);
   KVQ_REQUIRE(((size_t)a->bias_dense & 15) == 0, KVQ_ERR_SHAPE, "%s: the bias image must be 16-byte aligned", who);
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "%s: dtype %d", who, a->dtype);
+  KVQ_REQUIRE_OPERAND(who, a->dtype);
   KVQ_REQUIRE(a->dsplit_from < 0 || (N == 392 && a->dsplit_from < nW), KVQ_ERR_UNSUPPORTED,
               "%s: depth-split windows need the (8,7,7) window (N = 392); got N=%d from=%d", who, N, a->dsplit_from);
   const int units = BW * num_heads, nqb = (N + 31) / 32;
@@ -726,8 +719,7 @@ static int window_attention32(const char* who, const KvqAttnDenseArgs* a, const 
     KVQ_REQUIRE(a->dsplit_from < 0 && !a->pad_mask, KVQ_ERR_UNSUPPORTED, "%s: key ranges exclude dsplit_from and pad_mask (un-padded partitions only)", who);
     p.ranges = ranges;
   }
-  hipStream_t st = (hipStream_t)stream;
-  return a->dtype == KVQ_DT_FP16 ? launch_attn32_e<Fp16>(p, st) : launch_attn32_e<Bf16>(p, st);
+  return with_operand(a->dtype, [&](auto e) { return launch_attn32_e<decltype(e)>(p, (hipStream_t)stream); });
 }
 
 extern "C" int kvq_window_attention32(const KvqAttnDenseArgs* a, void* stream) {

@@ -230,20 +230,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void fast_bottleneck_kern
   }
 }
 
-template <typename E, int CIN, int CI, int COUT, bool SC, int STRIDE, int NW>
-static int launch_bneck(const BneckParams& p, hipStream_t st) {
-  using L = BnLayout<CIN, CI, COUT, SC>;
-  auto k = fast_bottleneck_kernel<E, CIN, CI, COUT, SC, STRIDE, NW>;
-  static LdsOptIn opt;
-  if (int rc = opt.ensure(reinterpret_cast<const void*>(k), L::LDS_BYTES)) return rc;
-  hipLaunchKernelGGL(k, dim3((unsigned)((long)p.B * p.T * p.tiles_y * p.tiles_x)), dim3(NW * 64), L::LDS_BYTES, st, p);
-  KVQ_CHECK_LAUNCH("fast_bottleneck_kernel");
-  return KVQ_OK;
-}
-
 template <int CIN, int CI, int COUT, bool SC, int STRIDE = 1, int NW = 4>
-static int launch_bneck_dt(const BneckParams& p, int dtype, hipStream_t st) {
-  return dtype == KVQ_DT_FP16 ? launch_bneck<Fp16, CIN, CI, COUT, SC, STRIDE, NW>(p, st) : launch_bneck<Bf16, CIN, CI, COUT, SC, STRIDE, NW>(p, st);
+static int launch_bneck(const BneckParams& p, int dtype, hipStream_t st) {
+  return with_operand(dtype, [&](auto e) {
+    return launch("fast_bottleneck_kernel", fast_bottleneck_kernel<decltype(e), CIN, CI, COUT, SC, STRIDE, NW>,
+                  dim3((unsigned)((long)p.B * p.T * p.tiles_y * p.tiles_x)), dim3(NW * 64), BnLayout<CIN, CI, COUT, SC>::LDS_BYTES, st, p);
+  });
 }
 
 // the supported (input, inner, output) channel triples: SlowFast-R50's fast pathway, res2 .. res4
@@ -276,7 +268,7 @@ extern "C" int kvq_fast_bottleneck(const uint16_t* x, const int32_t dims4[4], in
                                    const void* pack, int dtype, uint16_t* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims4 && pack && out, KVQ_ERR_NULL, "kvq_fast_bottleneck: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_fast_bottleneck: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_fast_bottleneck", dtype);
   const int B = dims4[0], T = dims4[1], H = dims4[2], W = dims4[3];
   KVQ_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && (long)B * T * ceil_div(H, 7) * ceil_div(W, 7) < (1L << 31),
               KVQ_ERR_SHAPE, "kvq_fast_bottleneck: bad shape (%d,%d,%d,%d) stride %d", B, T, H, W, stride);
@@ -289,13 +281,13 @@ extern "C" int kvq_fast_bottleneck(const uint16_t* x, const int32_t dims4[4], in
   BneckParams p{x, out, (const unsigned char*)pack, B, T, H, W, Ho, Wo, ceil_div(Ho, tile), ceil_div(Wo, tile)};
   hipStream_t st = (hipStream_t)stream;
   switch (var) {
-    case 1: return launch_bneck_dt<8, 8, 32, true>(p, dtype, st);
-    case 2: return launch_bneck_dt<32, 8, 32, false>(p, dtype, st);
-    case 3: return launch_bneck_dt<64, 16, 64, false>(p, dtype, st);
+    case 1: return launch_bneck<8, 8, 32, true>(p, dtype, st);
+    case 2: return launch_bneck<32, 8, 32, false>(p, dtype, st);
+    case 3: return launch_bneck<64, 16, 64, false>(p, dtype, st);
     case 4:      // res4: 14 x 14 maps, one tile per frame - few tiles: the 8-wave form (one conv_a tile per wave, b / c tiles in one round)
-      return (long)p.B * p.T * p.tiles_y * p.tiles_x <= 512 ? launch_bneck_dt<128, 32, 128, false, 1, 8>(p, dtype, st)
-                                                             : launch_bneck_dt<128, 32, 128, false>(p, dtype, st);
-    case 5: return launch_bneck_dt<32, 16, 64, true, 2>(p, dtype, st);
-    default: return launch_bneck_dt<64, 32, 128, true, 2>(p, dtype, st);
+      return (long)p.B * p.T * p.tiles_y * p.tiles_x <= 512 ? launch_bneck<128, 32, 128, false, 1, 8>(p, dtype, st)
+                                                             : launch_bneck<128, 32, 128, false>(p, dtype, st);
+    case 5: return launch_bneck<32, 16, 64, true, 2>(p, dtype, st);
+    default: return launch_bneck<64, 32, 128, true, 2>(p, dtype, st);
   }
 }

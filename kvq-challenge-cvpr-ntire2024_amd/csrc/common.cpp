@@ -22,10 +22,9 @@ int hip_fail(hipError_t e, const char* what) {
   set_error("HIP error %d (%s) at %s", (int)e, hipGetErrorString(e), what);
   return KVQ_ERR_HIP;
 }
-// Keyed by (kernel address, device ordinal), not by the call site: a generic lambda `go(auto k)` over kernels that all decay to the same
-// pointer type is instantiated ONCE, so a `static LdsOptIn` inside it is shared by every kernel passed through it (embed.hip, conv.hip,
-// slowneck.hip) — the first kernel's opt-in must not stand for the others.
-int LdsOptIn::ensure(const void* kernel, int want) {
+// hipFuncAttributeMaxDynamicSharedMemorySize is a property of a kernel on one device, so the largest grant so far is kept per
+// (kernel address, device ordinal).
+int lds_opt_in(const void* kernel, int want) {
   static std::mutex mu;
   static std::map<std::pair<const void*, int>, int> granted;
   int dev = 0;

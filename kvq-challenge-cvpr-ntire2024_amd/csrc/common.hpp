@@ -29,12 +29,6 @@ int hip_fail(hipError_t e, const char* what);
     if (_e != hipSuccess) return kvq::hip_fail(_e, #expr);    \
   } while (0)
 
-#define KVQ_CHECK_LAUNCH(name)                                \
-  do {                                                        \
-    hipError_t _e = hipGetLastError();                        \
-    if (_e != hipSuccess) return kvq::hip_fail(_e, name);     \
-  } while (0)
-
 #define KVQ_REQUIRE(cond, code, ...)                          \
   do {                                                        \
     if (!(cond)) {                                            \
@@ -42,6 +36,10 @@ int hip_fail(hipError_t e, const char* what);
       return code;                                            \
     }                                                         \
   } while (0)
+
+// the operand type of an exported entry: KVQ_DT_BF16 or KVQ_DT_FP16 (with_operand below)
+#define KVQ_REQUIRE_OPERAND(entry, dtype) \
+  KVQ_REQUIRE((dtype) == KVQ_DT_BF16 || (dtype) == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "%s: dtype %d", entry, dtype)
 
 __device__ __forceinline__ uint16_t f2bf(float f) {
   __bf16 b = (__bf16)f;                       // v_cvt_pk_bf16_f32: round-to-nearest-even
@@ -210,13 +208,25 @@ int gemm_variant(int M, int N, int K);
 // true: kvq_gemm_bf16 takes the 256 x 256 x 64 eight-phase kernel for this shape (gemm256.hip); profile records carry tile code 4464
 bool gemm8p_wanted(int M, int N, int K);
 
-// The opt-in to more than 64 KiB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) is a per-DEVICE property of a KERNEL:
-// the largest request granted so far is remembered per (kernel address, device ordinal) in one table (common.cpp) — the object itself
-// carries no state, so it does not matter how many kernels share one call site (a generic lambda over kernels of one pointer type
-// is a single instantiation).
-struct LdsOptIn {
-  int ensure(const void* kernel, int want);      // KVQ_OK, or the HIP failure
-};
+// f(Fp16{}) or f(Bf16{}) for a dtype that passed KVQ_REQUIRE_OPERAND: a launch site names its kernel once, as kernel<decltype(e), ...>
+template <class F>
+int with_operand(int dtype, F&& f) {
+  return dtype == KVQ_DT_FP16 ? f(Fp16{}) : f(Bf16{});
+}
+
+// Opt `kernel` in to `want` bytes of dynamic LDS on the current device (common.cpp); KVQ_OK, or the HIP failure.
+int lds_opt_in(const void* kernel, int want);
+
+// The one launch path: opt in when the request is above the 64 KiB every kernel may have, launch, and turn the launch status into
+// KVQ_OK or hip_fail(e, name).  The arguments convert to the kernel's parameter types as at a direct call.
+template <class... KArgs, class... Args>
+int launch(const char* name, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, void* stream, Args&&... args) {
+  if (lds > 64 * 1024)
+    if (int rc = lds_opt_in(reinterpret_cast<const void*>(kernel), (int)lds)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, static_cast<KArgs>(args)...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KVQ_OK : hip_fail(e, name);
+}
 
 // KVQ_LATENCY=1: the launch geometries that are fastest for ONE step alone on the chip (q-split attention at the late stages, the
 // stage-3 GEMM chain, the C = 384 tail at one 512-VGPR workgroup per CU) instead of the defaults, which minimise CU x time for several
@@ -233,5 +243,12 @@ bool stem_pool_shape_ok(int B, int T, int H, int W, int kd);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// output extent of a convolution or pooling window: n inputs, kernel k, stride s, padding p on both sides
+static inline int conv_out(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
+// 1-D grid of `block`-thread workgroups over `total` items, at most `cap` of them (the kernels launched with a cap stride over the rest)
+static inline dim3 grid_1d(long total, int block = 256, long cap = 0) {
+  const long n = (total + block - 1) / block;
+  return dim3((unsigned)(cap > 0 && n > cap ? cap : n));
+}
 
 }  // namespace kvq

@@ -888,16 +888,15 @@ __global__ __launch_bounds__(S6_THREADS) void conv_stem64_pool_kernel(Stem64Para
 extern "C" int kvq_pack_clip_cl4(const float* x, const int32_t dims5[5], int border, int dtype, uint16_t* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims5 && out, KVQ_ERR_NULL, "kvq_pack_clip_cl4: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_pack_clip_cl4: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_pack_clip_cl4", dtype);
   const int B = dims5[0], Cc = dims5[1], T = dims5[2], H = dims5[3], W = dims5[4];
   KVQ_REQUIRE(B > 0 && Cc > 0 && Cc <= 4 && T > 0 && H > 0 && W > 0 && border >= 0, KVQ_ERR_SHAPE,
               "kvq_pack_clip_cl4: bad shape B=%d C=%d (1..4) T=%d H=%d W=%d border=%d", B, Cc, T, H, W, border);
   const long total = (long)B * T * H * (W + 2 * border);
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(pack_cl4_border_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, x, Cc, T, H, W, border, out, total);
-  else hipLaunchKernelGGL(pack_cl4_border_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, x, Cc, T, H, W, border, out, total);
-  KVQ_CHECK_LAUNCH("pack_cl4_border_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("pack_cl4_border_kernel", pack_cl4_border_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, x, Cc, T, H, W, border, out,
+                  total);
+  });
 }
 
 extern "C" int kvq_conv_stem_mfma(const uint16_t* x4, const int32_t dims4[4], const uint16_t* wpack, const float* bias8,
@@ -905,7 +904,7 @@ extern "C" int kvq_conv_stem_mfma(const uint16_t* x4, const int32_t dims4[4], co
                                   uint16_t* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x4 && dims4 && wpack && bias8 && kernel3 && stride3 && pad3 && out, KVQ_ERR_NULL, "kvq_conv_stem_mfma: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_mfma: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_conv_stem_mfma", dtype);
   KVQ_REQUIRE(kernel3[2] == 7 && stride3[2] == 2 && pad3[2] == 3, KVQ_ERR_UNSUPPORTED,
               "kvq_conv_stem_mfma: kernel width 7 / stride 2 / pad 3 along W only (got %d / %d / %d)", kernel3[2], stride3[2], pad3[2]);
   StemMfmaParams p{};
@@ -913,24 +912,22 @@ extern "C" int kvq_conv_stem_mfma(const uint16_t* x4, const int32_t dims4[4], co
   p.kd = kernel3[0]; p.kh = kernel3[1]; p.sd = stride3[0]; p.sh = stride3[1]; p.pd = pad3[0]; p.ph = pad3[1]; p.relu = relu; p.out = out;
   KVQ_REQUIRE(p.B > 0 && p.T > 0 && p.H > 0 && dims4[3] > 0 && p.kd > 0 && p.kh > 0 && p.sd > 0 && p.sh > 0, KVQ_ERR_SHAPE,
               "kvq_conv_stem_mfma: bad shape");
-  p.Do = (p.T + 2 * p.pd - p.kd) / p.sd + 1; p.Ho = (p.H + 2 * p.ph - p.kh) / p.sh + 1; p.Wo = (dims4[3] + 6 - 7) / 2 + 1;
+  p.Do = conv_out(p.T, p.kd, p.sd, p.pd); p.Ho = conv_out(p.H, p.kh, p.sh, p.ph); p.Wo = conv_out(dims4[3], 7, 2, 3);
   KVQ_REQUIRE(p.Do > 0 && p.Ho > 0 && p.Wo > 0, KVQ_ERR_SHAPE, "kvq_conv_stem_mfma: empty output");
   const size_t lds = (size_t)p.kd * p.kh * 16 * 32 * 2 + 4 * 2048;       // weights + a 2 KB row segment per wave
   KVQ_REQUIRE(lds <= 64 * 1024, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_mfma: %zu B of weights exceed LDS", lds);
   KVQ_REQUIRE(p.Wp % 2 == 0 && (((size_t)x4) & 15) == 0, KVQ_ERR_SHAPE, "kvq_conv_stem_mfma: W must be even and x4 16-byte aligned");
   const long rows = (long)p.B * p.Do * p.Ho;
-  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(conv_stem_mfma_kernel<Fp16>, grid, block, lds, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(conv_stem_mfma_kernel<Bf16>, grid, block, lds, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("conv_stem_mfma_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("conv_stem_mfma_kernel", conv_stem_mfma_kernel<decltype(e)>, grid_1d(rows, 4), dim3(256), lds, stream, p);
+  });
 }
 
 // the shape limits of kvq_conv_stem_pool (everything but the pointers' alignment): also asked by kvq_convnet_create, so that a plan
 // outside them is refused when it is built, not inside every forward
 bool kvq::stem_pool_shape_ok(int B, int T, int H, int W, int kd) {
   if (!(B > 0 && T > 0 && H >= 7 && W >= 8 && kd >= 1 && kd <= 7 && (kd & 1) && W % 4 == 0)) return false;
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1;
+  const int Ho = conv_out(H, 7, 2, 3), Wo = conv_out(W, 7, 2, 3), Hp = conv_out(Ho, 3, 2, 1);
   if (!(Wo <= 128 && (long)B * T * Hp < (1L << 30) && (long)T * H * W < (1L << 27))) return false;
   return (size_t)SP_NR * (W + 8) * 8 + (size_t)SP_SR * Wo * 16 + (size_t)kd * 7 * 512 <= 96 * 1024;
 }
@@ -939,35 +936,29 @@ extern "C" int kvq_conv_stem_pool(const float* x, const int32_t dims5[5], const 
                                   int dtype, uint16_t* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims5 && wpack && bias8 && out, KVQ_ERR_NULL, "kvq_conv_stem_pool: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_pool: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_conv_stem_pool", dtype);
   StemPoolParams p{};
   p.x = x; p.wp = wpack; p.bias = bias8; p.B = dims5[0]; p.T = dims5[2]; p.H = dims5[3]; p.W = dims5[4]; p.kd = kd; p.relu = relu; p.out = out;
   KVQ_REQUIRE(dims5[1] == 3 && p.B > 0 && p.T > 0 && p.H >= 7 && p.W >= 8 && kd >= 1 && kd <= 7 && (kd & 1), KVQ_ERR_SHAPE,
               "kvq_conv_stem_pool: needs a 3-channel clip and an odd temporal kernel (got C=%d kd=%d)", dims5[1], kd);
   KVQ_REQUIRE(p.W % 4 == 0 && (((size_t)x) & 15) == 0 && (((size_t)out) & 15) == 0, KVQ_ERR_SHAPE,
               "kvq_conv_stem_pool: W %% 4 == 0 and 16-byte aligned clip / output (got W=%d)", p.W);
-  p.Ho = (p.H + 6 - 7) / 2 + 1; p.Wo = (p.W + 6 - 7) / 2 + 1;
-  p.Hp = (p.Ho + 2 - 3) / 2 + 1; p.Wp = (p.Wo + 2 - 3) / 2 + 1;
+  p.Ho = conv_out(p.H, 7, 2, 3); p.Wo = conv_out(p.W, 7, 2, 3);
+  p.Hp = conv_out(p.Ho, 3, 2, 1); p.Wp = conv_out(p.Wo, 3, 2, 1);
   KVQ_REQUIRE(p.Wo <= 128 && (long)p.B * p.T * p.Hp < (1L << 30) && (long)p.T * p.H * p.W < (1L << 27), KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_pool: stem rows of at most 128 columns (W <= 256; got %d)", p.W);
   const size_t lds = (size_t)SP_NR * (p.W + 8) * 8 + (size_t)SP_SR * p.Wo * 16 + (size_t)kd * 7 * 512;
   KVQ_REQUIRE(lds <= 96 * 1024, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_pool: %zu B of LDS", lds);
-  auto launch = [&](auto kern) -> int {
-    static LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), 96 * 1024)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ceil_div(ceil_div(p.Hp, SP_PR) * p.T * p.B, 8))), dim3(256), lds, (hipStream_t)stream, p);
-    return KVQ_OK;
-  };
-  const int rc = dtype == KVQ_DT_FP16 ? launch(conv_stem_pool_kernel<Fp16>) : launch(conv_stem_pool_kernel<Bf16>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("conv_stem_pool_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("conv_stem_pool_kernel", conv_stem_pool_kernel<decltype(e)>, dim3((unsigned)(8 * ceil_div(ceil_div(p.Hp, SP_PR) * p.T * p.B, 8))),
+                  dim3(256), lds, stream, p);
+  });
 }
 
 extern "C" int kvq_conv_stem64_pool(const float* x, const int32_t dims5[5], const int32_t* t_index, int n_frames, const uint16_t* wimg,
                                     const float* bias64, int relu, int dtype, uint16_t* out, int out_C, int out_coff, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims5 && wimg && bias64 && out, KVQ_ERR_NULL, "kvq_conv_stem64_pool: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem64_pool: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_conv_stem64_pool", dtype);
   Stem64Params p{};
   p.x = x; p.t_index = t_index; p.wimg = wimg; p.bias = bias64; p.B = dims5[0]; p.T = dims5[2]; p.H = dims5[3]; p.W = dims5[4];
   p.F = n_frames; p.relu = relu; p.out = out; p.out_C = out_C; p.out_coff = out_coff;
@@ -976,21 +967,15 @@ extern "C" int kvq_conv_stem64_pool(const float* x, const int32_t dims5[5], cons
   KVQ_REQUIRE(p.W % 4 == 0 && p.W <= 224 && (((size_t)x) & 15) == 0 && (((size_t)out) & 15) == 0 && out_C % 8 == 0 && out_coff % 8 == 0 &&
                   out_coff >= 0 && out_coff + 64 <= out_C, KVQ_ERR_SHAPE,
               "kvq_conv_stem64_pool: W %% 4 == 0, W <= 224, 16-byte aligned clip / output channel slice (got W=%d, C=%d, offset %d)", p.W, out_C, out_coff);
-  p.Ho = (p.H - 1) / 2 + 1; p.Wo = (p.W - 1) / 2 + 1;
-  p.Hp = (p.Ho - 1) / 2 + 1; p.Wp = (p.Wo - 1) / 2 + 1;
+  p.Ho = conv_out(p.H, 7, 2, 3); p.Wo = conv_out(p.W, 7, 2, 3);
+  p.Hp = conv_out(p.Ho, 3, 2, 1); p.Wp = conv_out(p.Wo, 3, 2, 1);
   KVQ_REQUIRE((long)p.B * p.F * p.Hp < (1L << 30), KVQ_ERR_UNSUPPORTED, "kvq_conv_stem64_pool: %d clips x %d frames", p.B, p.F);
   const size_t lds = (size_t)S6_NR * (p.W + 8) * 8 + (size_t)S6_PR * p.Wo * 128 + (size_t)3 * S6_ITEMS * S6_THREADS * 16 + 7 * 64 * 64;
-  auto launch = [&](auto kern) -> int {
-    static LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), 144 * 1024)) return rc;
-    const int total = ceil_div(p.Hp, S6_PR) * p.F * p.B;          // one persistent workgroup per CU (256 on gfx950)
-    hipLaunchKernelGGL(kern, dim3((unsigned)std::min(total, 256)), dim3(S6_THREADS), lds, (hipStream_t)stream, p);
-    return KVQ_OK;
-  };
-  const int rc = dtype == KVQ_DT_FP16 ? launch(conv_stem64_pool_kernel<Fp16>) : launch(conv_stem64_pool_kernel<Bf16>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("conv_stem64_pool_kernel");
-  return KVQ_OK;
+  const int total = ceil_div(p.Hp, S6_PR) * p.F * p.B;          // one persistent workgroup per CU (256 on gfx950)
+  return with_operand(dtype, [&](auto e) {
+    return launch("conv_stem64_pool_kernel", conv_stem64_pool_kernel<decltype(e)>, dim3((unsigned)std::min(total, 256)), dim3(S6_THREADS), lds, stream,
+                  p);
+  });
 }
 
 extern "C" int kvq_im2col_nd(const void* x, int src_f32, int dtype, const int64_t strides5[5], const int32_t dims5[5],
@@ -998,7 +983,7 @@ extern "C" int kvq_im2col_nd(const void* x, int src_f32, int dtype, const int64_
                              uint16_t* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && out && strides5 && dims5 && kernel3 && stride3 && pad3, KVQ_ERR_NULL, "kvq_im2col_nd: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_im2col_nd: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_im2col_nd", dtype);
   Im2colParams p{};
   p.x = x; p.src_f32 = src_f32;
   p.sb = strides5[0]; p.sc = strides5[1]; p.sd = strides5[2]; p.sh = strides5[3]; p.sw = strides5[4];
@@ -1009,19 +994,17 @@ extern "C" int kvq_im2col_nd(const void* x, int src_f32, int dtype, const int64_
   KVQ_REQUIRE(p.B > 0 && p.C > 0 && p.D > 0 && p.H > 0 && p.W > 0 && p.kd > 0 && p.kh > 0 && p.kw > 0 && p.sdd > 0 &&
                   p.shh > 0 && p.sww > 0,
               KVQ_ERR_SHAPE, "kvq_im2col_nd: bad shape");
-  p.Do = (p.D + 2 * p.pd - p.kd) / p.sdd + 1;
-  p.Ho = (p.H + 2 * p.ph - p.kh) / p.shh + 1;
-  p.Wo = (p.W + 2 * p.pw - p.kw) / p.sww + 1;
+  p.Do = conv_out(p.D, p.kd, p.sdd, p.pd);
+  p.Ho = conv_out(p.H, p.kh, p.shh, p.ph);
+  p.Wo = conv_out(p.W, p.kw, p.sww, p.pw);
   p.K = p.kd * p.kh * p.kw * p.C;
   KVQ_REQUIRE(p.Do > 0 && p.Ho > 0 && p.Wo > 0 && Kpad >= p.K && Kpad % 32 == 0, KVQ_ERR_SHAPE,
               "kvq_im2col_nd: Kpad=%d must be a multiple of 32 and >= K=%d", Kpad, p.K);
   p.Kpad = Kpad; p.out = out;
   const long total = (long)p.B * p.Do * p.Ho * p.Wo * (Kpad / 8);
-  const int grid = (int)((total + 255) / 256 < 131072 ? (total + 255) / 256 : 131072);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(im2col_nd_kernel<Fp16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(im2col_nd_kernel<Bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("im2col_nd_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("im2col_nd_kernel", im2col_nd_kernel<decltype(e)>, grid_1d(total, 256, 131072), dim3(256), 0, stream, p);
+  });
 }
 
 extern "C" int kvq_pool_nd_strided(const uint16_t* x, int dtype, const int32_t dims5[5], const int32_t kernel3[3],
@@ -1029,7 +1012,7 @@ extern "C" int kvq_pool_nd_strided(const uint16_t* x, int dtype, const int32_t d
                                    void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && out && dims5 && kernel3 && stride3 && pad3, KVQ_ERR_NULL, "kvq_pool_nd: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_pool_nd: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_pool_nd", dtype);
   PoolParams p{};
   p.x = x; p.out = out;
   p.B = dims5[0]; p.C = dims5[1]; p.D = dims5[2]; p.H = dims5[3]; p.W = dims5[4];
@@ -1042,24 +1025,17 @@ extern "C" int kvq_pool_nd_strided(const uint16_t* x, int dtype, const int32_t d
               "kvq_pool_nd: ldc / col_off must be multiples of 8 with col_off + C <= ldc");
   KVQ_REQUIRE(p.B > 0 && p.C > 0 && p.kd > 0 && p.kh > 0 && p.kw > 0 && p.sdd > 0 && p.shh > 0 && p.sww > 0,
               KVQ_ERR_SHAPE, "kvq_pool_nd: bad shape");
-  p.Do = (p.D + 2 * p.pd - p.kd) / p.sdd + 1;
-  p.Ho = (p.H + 2 * p.ph - p.kh) / p.shh + 1;
-  p.Wo = (p.W + 2 * p.pw - p.kw) / p.sww + 1;
+  p.Do = conv_out(p.D, p.kd, p.sdd, p.pd);
+  p.Ho = conv_out(p.H, p.kh, p.shh, p.ph);
+  p.Wo = conv_out(p.W, p.kw, p.sww, p.pw);
   KVQ_REQUIRE(p.Do > 0 && p.Ho > 0 && p.Wo > 0, KVQ_ERR_SHAPE, "kvq_pool_nd: empty output");
-  if (p.C % 8 == 0 && (((size_t)p.x | (size_t)p.out) & 15) == 0) {
-    const long tot8 = (long)p.B * p.Do * p.Ho * p.Wo * (p.C / 8);
-    const int g8 = (int)((tot8 + 255) / 256 < 131072 ? (tot8 + 255) / 256 : 131072);
-    if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(pool_nd_vec8_kernel<Fp16>, dim3(g8), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(pool_nd_vec8_kernel<Bf16>, dim3(g8), dim3(256), 0, (hipStream_t)stream, p);
-    KVQ_CHECK_LAUNCH("pool_nd_vec8_kernel");
-    return KVQ_OK;
-  }
-  const long total = (long)p.B * p.Do * p.Ho * p.Wo * p.C;
-  const int grid = (int)((total + 255) / 256 < 131072 ? (total + 255) / 256 : 131072);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(pool_nd_kernel<Fp16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(pool_nd_kernel<Bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("pool_nd_kernel");
-  return KVQ_OK;
+  const long sites = (long)p.B * p.Do * p.Ho * p.Wo;
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    if (p.C % 8 == 0 && (((size_t)p.x | (size_t)p.out) & 15) == 0)
+      return launch("pool_nd_vec8_kernel", pool_nd_vec8_kernel<E>, grid_1d(sites * (p.C / 8), 256, 131072), dim3(256), 0, stream, p);
+    return launch("pool_nd_kernel", pool_nd_kernel<E>, grid_1d(sites * p.C, 256, 131072), dim3(256), 0, stream, p);
+  });
 }
 
 extern "C" int kvq_pool_nd(const uint16_t* x, int dtype, const int32_t dims5[5], const int32_t kernel3[3],
@@ -1071,54 +1047,40 @@ extern "C" int kvq_pack_channels_last8(const float* x, const int32_t dims5[5], c
                                        void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims5 && strides5 && out, KVQ_ERR_NULL, "kvq_pack_channels_last8: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_pack_channels_last8: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_pack_channels_last8", dtype);
   const int B = dims5[0], T = dims5[1], Cc = dims5[2], H = dims5[3], W = dims5[4];
   KVQ_REQUIRE(B > 0 && T > 0 && Cc > 0 && Cc <= 8 && H > 0 && W > 0, KVQ_ERR_SHAPE,
               "kvq_pack_channels_last8: bad shape B=%d T=%d C=%d (1..8) H=%d W=%d", B, T, Cc, H, W);
   KVQ_REQUIRE(((size_t)out & 15) == 0, KVQ_ERR_SHAPE, "kvq_pack_channels_last8: out must be 16-byte aligned");
   const long total = (long)B * T * H * W;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL(pack_cl8_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, x, T, Cc, H, W, (long)strides5[0], (long)strides5[1],
-                       (long)strides5[2], (long)strides5[3], (long)strides5[4], out, total);
-  else
-    hipLaunchKernelGGL(pack_cl8_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, x, T, Cc, H, W, (long)strides5[0], (long)strides5[1],
-                       (long)strides5[2], (long)strides5[3], (long)strides5[4], out, total);
-  KVQ_CHECK_LAUNCH("pack_cl8_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("pack_cl8_kernel", pack_cl8_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, x, T, Cc, H, W, strides5[0], strides5[1],
+                  strides5[2], strides5[3], strides5[4], out, total);
+  });
 }
 
 extern "C" int kvq_mean_std_pool(const uint16_t* x, int dtype, int rows, int HW, int C, float* out, int64_t out_stride,
                                  int mean_off, int std_off, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && out, KVQ_ERR_NULL, "kvq_mean_std_pool: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_mean_std_pool: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_mean_std_pool", dtype);
   KVQ_REQUIRE(rows > 0 && HW > 0 && C > 0 && (std_off < 0 || HW > 1), KVQ_ERR_SHAPE, "kvq_mean_std_pool: bad shape");
   // The kernel (and with it the order the positions are summed in) is chosen from HW, C and the pointer's alignment ONLY — never
   // from `rows`, which is the batch in the extractors' head pools: a clip's features must not change in their last bits with what
   // else shares the launch (kvq_convnet_splitk is off there for the same reason).
-  hipStream_t st = (hipStream_t)stream;
   // 16-byte loads, a block per 8 channels: maps of >= 256 positions (KSVQE: 4 rows x 3136 positions; SlowFast's slow head pool:
   // 8 rows x 392 positions x 2048 channels, 45.8 -> 8 us); 16-channel tiles when the channels cannot be taken 8 at a time
   const bool wide = C % 8 == 0 && ((size_t)x & 15) == 0 && HW >= 256;
   const bool narrow = HW >= 256;
-  if (wide) {
-    dim3 g8(rows, C / 8);
-    if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(mean_std_pool_vec8_kernel<Fp16>, g8, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-    else hipLaunchKernelGGL(mean_std_pool_vec8_kernel<Bf16>, g8, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-    KVQ_CHECK_LAUNCH("mean_std_pool_vec8_kernel");
-    return KVQ_OK;
-  }
-  dim3 grid(rows, ceil_div(C, narrow ? 16 : 64));
-  if (dtype == KVQ_DT_FP16) {
-    if (narrow) hipLaunchKernelGGL((mean_std_pool_kernel<Fp16, 16>), grid, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-    else hipLaunchKernelGGL((mean_std_pool_kernel<Fp16, 64>), grid, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-  } else {
-    if (narrow) hipLaunchKernelGGL((mean_std_pool_kernel<Bf16, 16>), grid, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-    else hipLaunchKernelGGL((mean_std_pool_kernel<Bf16, 64>), grid, dim3(256), 0, st, x, HW, C, out, (long)out_stride, mean_off, std_off);
-  }
-  KVQ_CHECK_LAUNCH("mean_std_pool_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    auto go = [&](const char* name, auto kern, dim3 grid) {
+      return launch(name, kern, grid, dim3(256), 0, stream, x, HW, C, out, out_stride, mean_off, std_off);
+    };
+    if (wide) return go("mean_std_pool_vec8_kernel", mean_std_pool_vec8_kernel<E>, dim3(rows, C / 8));
+    if (narrow) return go("mean_std_pool_kernel", mean_std_pool_kernel<E, 16>, dim3(rows, ceil_div(C, 16)));
+    return go("mean_std_pool_kernel", mean_std_pool_kernel<E, 64>, dim3(rows, ceil_div(C, 64)));
+  });
 }
 
 extern "C" int kvq_conv_stem_direct(const float* x, const int32_t dims5[5], const float* w, const float* bias, int cout,
@@ -1127,26 +1089,20 @@ extern "C" int kvq_conv_stem_direct(const float* x, const int32_t dims5[5], cons
   using namespace kvq;
   KVQ_REQUIRE(x && dims5 && w && bias && kernel3 && stride3 && pad3 && out, KVQ_ERR_NULL, "kvq_conv_stem_direct: NULL pointer");
   KVQ_REQUIRE(cout == 8 || cout == 16, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_direct: Cout=%d (8 or 16: wider convs are GEMMs)", cout);
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_direct: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_conv_stem_direct", dtype);
   StemParams p{};
   p.x = x; p.w = w; p.bias = bias; p.B = dims5[0]; p.C = dims5[1]; p.D = dims5[2]; p.H = dims5[3]; p.W = dims5[4];
   p.kd = kernel3[0]; p.kh = kernel3[1]; p.kw = kernel3[2]; p.sd = stride3[0]; p.sh = stride3[1]; p.sw = stride3[2];
   p.pd = pad3[0]; p.ph = pad3[1]; p.pw = pad3[2]; p.relu = relu; p.out = out;
   KVQ_REQUIRE(p.B > 0 && p.C > 0 && p.sd > 0 && p.sh > 0 && p.sw > 0, KVQ_ERR_SHAPE, "kvq_conv_stem_direct: bad shape");
-  p.Do = (p.D + 2 * p.pd - p.kd) / p.sd + 1; p.Ho = (p.H + 2 * p.ph - p.kh) / p.sh + 1; p.Wo = (p.W + 2 * p.pw - p.kw) / p.sw + 1;
+  p.Do = conv_out(p.D, p.kd, p.sd, p.pd); p.Ho = conv_out(p.H, p.kh, p.sh, p.ph); p.Wo = conv_out(p.W, p.kw, p.sw, p.pw);
   KVQ_REQUIRE(p.Do > 0 && p.Ho > 0 && p.Wo > 0, KVQ_ERR_SHAPE, "kvq_conv_stem_direct: empty output");
   const size_t lds = (size_t)p.kd * p.kh * p.kw * p.C * cout * 4;
   KVQ_REQUIRE(lds <= 64 * 1024, KVQ_ERR_UNSUPPORTED, "kvq_conv_stem_direct: %zu B of weights exceed LDS", lds);
   const long total = (long)p.B * p.Do * p.Ho * p.Wo;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == KVQ_DT_FP16) {
-    if (cout == 8) hipLaunchKernelGGL((conv_stem_direct_kernel<Fp16, 8>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((conv_stem_direct_kernel<Fp16, 16>), grid, block, lds, st, p);
-  } else {
-    if (cout == 8) hipLaunchKernelGGL((conv_stem_direct_kernel<Bf16, 8>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((conv_stem_direct_kernel<Bf16, 16>), grid, block, lds, st, p);
-  }
-  KVQ_CHECK_LAUNCH("conv_stem_direct_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    const auto kern = cout == 8 ? conv_stem_direct_kernel<E, 8> : conv_stem_direct_kernel<E, 16>;
+    return launch("conv_stem_direct_kernel", kern, grid_1d(total), dim3(256), lds, stream, p);
+  });
 }

@@ -141,7 +141,7 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
   using namespace kvq;
   KVQ_REQUIRE(ops && tensors && out && n_ops > 0 && n_tensors > 0 && n_inputs > 0 && n_inputs <= n_tensors, KVQ_ERR_NULL,
               "kvq_convnet_create: NULL / empty argument");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_convnet_create: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_convnet_create", dtype);
   KvqConvNet* net = new KvqConvNet();
   net->n_inputs = n_inputs; net->n_outputs = n_outputs; net->dtype = dtype;
   for (int i = 0; i < n_tensors; ++i) {
@@ -174,7 +174,8 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
     } else {
       NET_REQUIRE(p.dst >= 0 && p.dst < n_outputs, "kvq_convnet_create: op %d writes output %d of %d", i, p.dst, n_outputs);
     }
-    auto odim = [&](int n, int a) { return (n + 2 * p.pad3[a] - p.kernel3[a]) / p.stride3[a] + 1; };
+    auto odim = [&](int n, int a) { return conv_out(n, p.kernel3[a], p.stride3[a], p.pad3[a]); };
+    auto stem_pool_odim = [](int n) { return conv_out(conv_out(n, 7, 2, 3), 3, 2, 1); };      // 7-wide stride-2 conv, then the 3-wide stride-2 pool
     switch (p.kind) {
       case KVQ_NET_CONV: {
         NET_REQUIRE(s.kind == KVQ_NET_T_ACT16 && (d.kind == KVQ_NET_T_ACT16 || d.kind == KVQ_NET_T_ACT32) && s.C % 8 == 0,
@@ -249,7 +250,7 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
         NET_REQUIRE(stem_pool_shape_ok(s.B, s.D, s.H, s.W, p.kernel3[0]),
                     "kvq_convnet_create: op %d (stem + pool): clip %d x %d x %d with a %d-frame kernel is outside the fused stem's limits (W %% 4 == 0, "
                     "W <= 256, temporal kernel <= 7, 96 KB of LDS)", i, s.D, s.H, s.W, p.kernel3[0]);
-        o.Do = s.D; o.Ho = ((s.H - 1) / 2 + 1 - 1) / 2 + 1; o.Wo = ((s.W - 1) / 2 + 1 - 1) / 2 + 1;
+        o.Do = s.D; o.Ho = stem_pool_odim(s.H); o.Wo = stem_pool_odim(s.W);
         NET_REQUIRE(d.B == s.B && d.D == o.Do && d.H == o.Ho && d.W == o.Wo && d.C == 8, "kvq_convnet_create: op %d (stem + pool) output shape", i);
         break;
       }
@@ -259,7 +260,7 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
         NET_REQUIRE(p.cout == 64 && p.kernel3[0] == 1 && p.kernel3[1] == 7 && p.kernel3[2] == 7 && p.stride3[0] == 1 && p.stride3[1] == 2 &&
                         p.stride3[2] == 2 && p.pad3[0] == 0 && p.pad3[1] == 3 && p.pad3[2] == 3 && s.W <= 224 && s.W % 4 == 0,
                     "kvq_convnet_create: op %d (stem64 + pool) geometry", i);
-        o.Do = p.n_index; o.Ho = ((s.H - 1) / 2 + 1 - 1) / 2 + 1; o.Wo = ((s.W - 1) / 2 + 1 - 1) / 2 + 1;
+        o.Do = p.n_index; o.Ho = stem_pool_odim(s.H); o.Wo = stem_pool_odim(s.W);
         NET_REQUIRE(d.B == s.B && d.D == o.Do && d.H == o.Ho && d.W == o.Wo && p.dst_coff % 8 == 0 && d.C % 8 == 0 && p.dst_coff + 64 <= d.C,
                     "kvq_convnet_create: op %d (stem64 + pool) output shape", i);
         for (int k = 0; k < p.n_index; ++k) NET_REQUIRE(p.t_index[k] >= 0 && p.t_index[k] < s.D, "kvq_convnet_create: op %d frame index %d", i, p.t_index[k]);
@@ -291,7 +292,7 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
         NET_REQUIRE(s.kind == KVQ_NET_T_ACT16 && d.kind == KVQ_NET_T_ACT16 && p.w, "kvq_convnet_create: op %d (bottleneck) operand kinds", i);
         const int bs = p.stride3[1];
         NET_REQUIRE(p.stride3[0] == 1 && p.stride3[2] == bs && (bs == 1 || bs == 2), "kvq_convnet_create: op %d (bottleneck) stride", i);
-        NET_REQUIRE(d.B == s.B && d.D == s.D && d.H == (s.H + bs - 1) / bs && d.W == (s.W + bs - 1) / bs && d.C == p.cout,
+        NET_REQUIRE(d.B == s.B && d.D == s.D && d.H == ceil_div(s.H, bs) && d.W == ceil_div(s.W, bs) && d.C == p.cout,
                     "kvq_convnet_create: op %d (bottleneck) output shape", i);
         NET_REQUIRE(kvq_fast_bottleneck_pack_bytes(s.C, p.kpad, p.cout, p.n_index, bs) > 0,
                     "kvq_convnet_create: op %d (bottleneck) channels %d -> %d -> %d (projection %d, stride %d) not built", i, s.C, p.kpad, p.cout,
@@ -541,9 +542,8 @@ extern "C" int kvq_convnet_forward(const KvqConvNet* net, const void* const* inp
         break;
       case KVQ_NET_SELECT_T: {
         const long hw4 = (long)s.H * s.W / 4, total4 = (long)s.B * s.C * p.n_index * hw4;
-        hipLaunchKernelGGL(select_frames_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, (const float*)ptr_of(p.src),
-                           (float*)ptr_of(p.dst), s.D, p.n_index, hw4, o.d_taps, total4);
-        KVQ_CHECK_LAUNCH("select_frames_kernel");
+        KVQ_TRY(launch("select_frames_kernel", select_frames_kernel, grid_1d(total4), dim3(256), 0, st, (const float*)ptr_of(p.src),
+                       (float*)ptr_of(p.dst), s.D, p.n_index, hw4, o.d_taps, total4));
         break;
       }
       default:

@@ -145,11 +145,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv3d_ln_kernel(DwParams p) {
 
 template <typename E, int NQ>
 static int launch_dw(const DwParams& p, hipStream_t st) {
-  constexpr int NS = DW_THREADS / NQ;
-  dim3 grid((unsigned)((p.n_strips + NS - 1) / NS)), block(DW_THREADS);
-  hipLaunchKernelGGL((dwconv3d_ln_kernel<E, NQ>), grid, block, 0, st, p);
-  KVQ_CHECK_LAUNCH("dwconv3d_ln_kernel");
-  return KVQ_OK;
+  return launch("dwconv3d_ln_kernel", dwconv3d_ln_kernel<E, NQ>, grid_1d(p.n_strips, DW_THREADS / NQ), dim3(DW_THREADS), 0, st, p);
 }
 
 template <typename E>
@@ -182,6 +178,5 @@ extern "C" int kvq_dwconv3d_ln(const KvqDwconvLnArgs* a, void* stream) {
   p.n_strips = (long)a->B * a->T * a->H * p.nsx;
   KVQ_REQUIRE(p.n_strips < (1L << 31), KVQ_ERR_SHAPE, "kvq_dwconv3d_ln: %ld strips exceed the grid", p.n_strips);
   p.eps = a->eps; p.out_h = a->out_h; p.out_f32 = a->out_f32;
-  hipStream_t st = (hipStream_t)stream;
-  return a->dtype == KVQ_DT_FP16 ? launch_dw_c<Fp16>(p, st) : launch_dw_c<Bf16>(p, st);
+  return with_operand(a->dtype, [&](auto e) { return launch_dw_c<decltype(e)>(p, (hipStream_t)stream); });
 }

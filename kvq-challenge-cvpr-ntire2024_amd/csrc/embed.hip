@@ -331,20 +331,11 @@ template <typename E_, int CM, int KS>
 static int launch_embed(const EmbedParams& p, hipStream_t st) {
   const int lds = embed_stage_off(CM, KS) + (embed_staged(CM, p.x == nullptr) ? 4 * 32 * (32 * CM * 4 + 16) : 0);
   const long total = (long)p.B * p.D0 * p.H0 * p.W0;
-  dim3 grid((unsigned)((total + 127) / 128)), block(256);      // one workgroup per tile of 128 tokens
-  auto go = [&](auto k) -> int {
-    LdsOptIn opt;                             // the opt-in is remembered per (kernel, device) in common.cpp
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(k), lds)) return rc;
-    hipLaunchKernelGGL(k, grid, block, lds, st, p);
-    return KVQ_OK;
-  };
-  int rc;
-  if (p.x == nullptr && p.frag.i420) rc = p.nr.next_ln ? go(patch_embed_i420_kernel<E_, CM, KS, true>) : go(patch_embed_i420_kernel<E_, CM, KS, false>);
-  else if (p.x == nullptr) rc = p.nr.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, true>) : go(patch_embed_kernel<E_, CM, KS, false, true>);
-  else rc = p.nr.next_ln ? go(patch_embed_kernel<E_, CM, KS, true, false>) : go(patch_embed_kernel<E_, CM, KS, false, false>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("patch_embed_kernel");
-  return KVQ_OK;
+  void (*k)(EmbedParams);
+  if (p.x == nullptr && p.frag.i420) k = p.nr.next_ln ? patch_embed_i420_kernel<E_, CM, KS, true> : patch_embed_i420_kernel<E_, CM, KS, false>;
+  else if (p.x == nullptr) k = p.nr.next_ln ? patch_embed_kernel<E_, CM, KS, true, true> : patch_embed_kernel<E_, CM, KS, false, true>;
+  else k = p.nr.next_ln ? patch_embed_kernel<E_, CM, KS, true, false> : patch_embed_kernel<E_, CM, KS, false, false>;
+  return launch("patch_embed_kernel", k, grid_1d(total, 128), dim3(256), lds, st, p);      // one workgroup per tile of 128 tokens
 }
 
 }  // namespace kvq
@@ -366,10 +357,8 @@ extern "C" int kvq_patch_embed_pack(const void* w, const float* bias, const floa
   KVQ_REQUIRE(w && bias && pack, KVQ_ERR_NULL, "kvq_patch_embed_pack: NULL pointer");
   KVQ_REQUIRE(kvq_patch_embed_pack_bytes(embed_dim, K) > 0, KVQ_ERR_UNSUPPORTED, "kvq_patch_embed_pack: E=%d K=%d", embed_dim, K);
   const long n_chunks = (long)embed_dim * K * 2 / 16, total = n_chunks + 3 * embed_dim;
-  hipLaunchKernelGGL(embed_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)w, bias, ln_w, ln_b, embed_dim, K, (unsigned char*)pack, n_chunks);
-  KVQ_CHECK_LAUNCH("embed_pack_kernel");
-  return KVQ_OK;
+  return launch("embed_pack_kernel", embed_pack_kernel, grid_1d(total), dim3(256), 0, stream, (const uint16_t*)w, bias, ln_w, ln_b, embed_dim,
+                K, (unsigned char*)pack, n_chunks);
 }
 
 extern "C" int kvq_patch_embed_fragments_supported(const KvqFragmentSource* f, int B, int in_chans, int pd, int T, int H, int W) {
@@ -399,7 +388,7 @@ int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStre
   KVQ_REQUIRE(a->B > 0, KVQ_ERR_SHAPE, "kvq_patch_embed: B=%d", a->B);
   EmbedParams p{};
   if (int rc = next_rows_fill(p.nr, a, "kvq_patch_embed")) return rc;
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_embed: dtype %d", a->dtype);
+  KVQ_REQUIRE_OPERAND("kvq_patch_embed", a->dtype);
   if (a->frag) {
     const KvqFragmentSource* f = a->frag;
     KVQ_REQUIRE(kvq_patch_embed_fragments_supported(f, a->B, a->in_chans, a->pd, a->T, a->H, a->W), KVQ_ERR_UNSUPPORTED,
@@ -420,7 +409,7 @@ int kvq::patch_embed_launch(const KvqPatchEmbedArgs* a, RangeFlag range, hipStre
   p.D0 = a->T / a->pd; p.H0 = a->H / 4; p.W0 = a->W / 4;
   p.pack = (const unsigned char*)a->pack; p.has_ln = a->has_norm; p.out = a->out; p.out16 = a->out_f16; p.eps = a->eps;
   if (a->out_f16) p.range = range;
-  if (a->embed_dim == 96)
-    return a->dtype == KVQ_DT_FP16 ? launch_embed<Fp16, 3, 6>(p, st) : launch_embed<Bf16, 3, 6>(p, st);
-  return a->dtype == KVQ_DT_FP16 ? launch_embed<Fp16, 4, 6>(p, st) : launch_embed<Bf16, 4, 6>(p, st);
+  return with_operand(a->dtype, [&](auto e) {
+    return a->embed_dim == 96 ? launch_embed<decltype(e), 3, 6>(p, st) : launch_embed<decltype(e), 4, 6>(p, st);
+  });
 }

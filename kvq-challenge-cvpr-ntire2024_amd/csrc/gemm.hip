@@ -309,14 +309,8 @@ static int launch_one(const GemmParams& p_in, hipStream_t st) {
   constexpr size_t main_bytes = NST * (BM + BN) * BK * 2;               // ring of 2*BK-byte rows
   constexpr size_t epi_bytes = 2 * WN * 32 * (32 * NI) * sizeof(float);     // one fp32 slab per wave
   constexpr size_t lds_bytes = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  auto kern = gemm_kernel<E, MI, NI, BK, EPI, NST, IMPL, WALK>;
-  static LdsOptIn opt;            // > 64 KiB of LDS needs the opt-in attribute (once per instantiation and device)
-  if (lds_bytes > 64 * 1024)
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), (int)lds_bytes)) return rc;
   dim3 grid(ceil_div(p.M, BM) * ceil_div(p.N, BN) * p.ksplit), block(128 * WN);
-  hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, p);
-  KVQ_CHECK_LAUNCH("gemm_kernel");
-  return KVQ_OK;
+  return launch("gemm_kernel", gemm_kernel<E, MI, NI, BK, EPI, NST, IMPL, WALK>, grid, block, lds_bytes, st, p);
 }
 
 // ---- split-K, second launch: out = epilogue(sum_s partial[s]) — the S partials are added in index order (bit-reproducible),
@@ -450,9 +444,7 @@ static void variant_tiles(int M, int N, int K, bool conv, long* tiles, int* nk, 
 template <typename E, int EPI>
 static int finish_splitk(const GemmParams& p, const float* partial, int S, hipStream_t st) {
   const long chunks = (long)p.M * (p.N / 8);
-  hipLaunchKernelGGL(splitk_reduce_kernel<E>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, p, partial, S, (int)EPI);
-  KVQ_CHECK_LAUNCH("splitk_reduce_kernel");
-  return KVQ_OK;
+  return launch("splitk_reduce_kernel", splitk_reduce_kernel<E>, grid_1d(chunks), dim3(256), 0, st, p, partial, S, (int)EPI);
 }
 
 template <typename E, int EPI>
@@ -527,7 +519,7 @@ static int launch_maybe_split(const GemmParams& p, hipStream_t st) {
 
 template <int EPI>
 static int launch_dt(int dtype, const GemmParams& p, hipStream_t st) {
-  return dtype == KVQ_DT_FP16 ? launch_gemm<Fp16, EPI>(p, st) : launch_gemm<Bf16, EPI>(p, st);
+  return with_operand(dtype, [&](auto e) { return launch_gemm<decltype(e), EPI>(p, st); });
 }
 
 }  // namespace kvq
@@ -666,32 +658,27 @@ extern "C" int kvq_qkv_fill_pad(void* qkv, const float* qkv_bias, const int32_t*
   using namespace kvq;
   KVQ_REQUIRE(qkv && qkv_bias && pad_rows, KVQ_ERR_NULL, "kvq_qkv_fill_pad: NULL pointer");
   KVQ_REQUIRE(n_pad > 0 && n_batch > 0 && rows_per_batch >= n_pad && num_heads > 0, KVQ_ERR_SHAPE, "kvq_qkv_fill_pad: bad shape");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_qkv_fill_pad: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_qkv_fill_pad", dtype);
   const long total = (long)3 * num_heads * n_batch * n_pad * 4;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL(qkv_fill_pad_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, (uint16_t*)qkv, qkv_bias, pad_rows, n_pad, n_batch,
-                       rows_per_batch, num_heads, q_scale);
-  else
-    hipLaunchKernelGGL(qkv_fill_pad_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, (uint16_t*)qkv, qkv_bias, pad_rows, n_pad, n_batch,
-                       rows_per_batch, num_heads, q_scale);
-  KVQ_CHECK_LAUNCH("qkv_fill_pad_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("qkv_fill_pad_kernel", qkv_fill_pad_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, (uint16_t*)qkv, qkv_bias, pad_rows,
+                  n_pad, n_batch, rows_per_batch, num_heads, q_scale);
+  });
 }
 
 extern "C" int kvq_conv_implicit(const KvqConvArgs* a, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(a && a->x && a->W && (a->epilogue == KVQ_EPI_STORE_F32 ? (const void*)a->out_f32 : (const void*)a->out_bf16),
               KVQ_ERR_NULL, "kvq_conv_implicit: NULL pointer");
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_conv_implicit: dtype %d", a->dtype);
+  KVQ_REQUIRE_OPERAND("kvq_conv_implicit", a->dtype);
   const int B = a->dims5[0], Cin = a->dims5[1], D = a->dims5[2], H = a->dims5[3], W = a->dims5[4];
   KVQ_REQUIRE(B > 0 && Cin > 0 && Cin % 8 == 0 && D > 0 && H > 0 && W > 0, KVQ_ERR_SHAPE,
               "kvq_conv_implicit: channels-last input needs C %% 8 == 0 (got B=%d C=%d D=%d H=%d W=%d)", B, Cin, D, H, W);
   for (int i = 0; i < 3; ++i)
     KVQ_REQUIRE(a->kernel3[i] > 0 && a->stride3[i] > 0 && a->pad3[i] >= 0, KVQ_ERR_SHAPE, "kvq_conv_implicit: bad kernel/stride/pad");
-  const int Do = (D + 2 * a->pad3[0] - a->kernel3[0]) / a->stride3[0] + 1;
-  const int Ho = (H + 2 * a->pad3[1] - a->kernel3[1]) / a->stride3[1] + 1;
-  const int Wo = (W + 2 * a->pad3[2] - a->kernel3[2]) / a->stride3[2] + 1;
+  const int Do = conv_out(D, a->kernel3[0], a->stride3[0], a->pad3[0]);
+  const int Ho = conv_out(H, a->kernel3[1], a->stride3[1], a->pad3[1]);
+  const int Wo = conv_out(W, a->kernel3[2], a->stride3[2], a->pad3[2]);
   // Kpad = 8 x the rows of the tap table.  Normally >= kd*kh*kw*C; a caller may leave out taps that fall into the padding for
   // EVERY output position (3x3 / pad 1 on a 1x1 map: the centre tap only) together with the matching columns of W.
   KVQ_REQUIRE(Do > 0 && Ho > 0 && Wo > 0 && a->Kpad >= 32 && a->Kpad % 32 == 0 && a->N > 0 && a->N % 8 == 0, KVQ_ERR_SHAPE,
@@ -720,9 +707,10 @@ extern "C" int kvq_conv_implicit(const KvqConvArgs* a, void* stream) {
                               a->col_off + a->N <= a->ldc),
               KVQ_ERR_SHAPE, "kvq_conv_implicit: ldc / col_off need a 16-bit epilogue, multiples of 8, col_off + N <= ldc");
   hipStream_t st = (hipStream_t)stream;
-  if (a->epilogue == KVQ_EPI_STORE_F32)      // projection shortcuts: conv + BN, no ReLU, kept in fp32
-    return a->dtype == KVQ_DT_FP16 ? launch_conv<Fp16, KVQ_EPI_STORE_F32>(p, st) : launch_conv<Bf16, KVQ_EPI_STORE_F32>(p, st);
-  if (a->epilogue == KVQ_EPI_RELU_BF16)
-    return a->dtype == KVQ_DT_FP16 ? launch_conv<Fp16, KVQ_EPI_RELU_BF16>(p, st) : launch_conv<Bf16, KVQ_EPI_RELU_BF16>(p, st);
-  return a->dtype == KVQ_DT_FP16 ? launch_conv<Fp16, KVQ_EPI_BIAS_BF16>(p, st) : launch_conv<Bf16, KVQ_EPI_BIAS_BF16>(p, st);
+  return with_operand(a->dtype, [&](auto e) {
+    using E = decltype(e);
+    if (a->epilogue == KVQ_EPI_STORE_F32) return launch_conv<E, KVQ_EPI_STORE_F32>(p, st);      // projection shortcuts: conv + BN, no ReLU, kept in fp32
+    if (a->epilogue == KVQ_EPI_RELU_BF16) return launch_conv<E, KVQ_EPI_RELU_BF16>(p, st);
+    return launch_conv<E, KVQ_EPI_BIAS_BF16>(p, st);
+  });
 }

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(GRN_THREADS) void grn_apply_kernel(const uint16_t* 
 
 static int grn_check(const KvqGrnArgs* a, const char* who) {
   KVQ_REQUIRE(a && a->x && a->gamma && a->beta && a->ws, KVQ_ERR_NULL, "%s: NULL pointer", who);
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "%s: dtype %d", who, a->dtype);
+  KVQ_REQUIRE_OPERAND(who, a->dtype);
   KVQ_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->ws | (uintptr_t)a->gamma | (uintptr_t)a->beta) & 15) == 0, KVQ_ERR_UNSUPPORTED,
               "%s: x, y, ws, gamma and beta must be 16-byte aligned", who);
   KVQ_REQUIRE(a->B >= 1 && kvq_grn_supported(a->N, a->D, a->H, a->W), KVQ_ERR_UNSUPPORTED,
@@ -299,43 +299,32 @@ extern "C" size_t kvq_grn_workspace_bytes(int B, int D, int H, int W, int N) {
 
 extern "C" int kvq_grn_stats(const KvqGrnArgs* a, void* stream) {
   using namespace kvq;
-  const int rc = grn_check(a, "kvq_grn_stats");
-  if (rc != KVQ_OK) return rc;
+  if (int rc = grn_check(a, "kvq_grn_stats")) return rc;
   const GrnPlan p = grn_plan(a->B, a->D, a->H, a->W, a->N);
   KVQ_REQUIRE(p.nchunks <= 65535, KVQ_ERR_SHAPE, "kvq_grn_stats: %d row chunks exceed the grid", p.nchunks);
-  hipStream_t st = (hipStream_t)stream;
   float* scale = a->ws;
   float* part = a->ws + (size_t)a->B * p.L;
   dim3 grid((unsigned)p.sgroups, (unsigned)p.nchunks, (unsigned)a->B), block(GRN_SUM_THREADS);
-  if (a->dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL((grn_sumsq_kernel<Fp16>), grid, block, 0, st, a->x, part, p.R, p.L, p.rpc);
-  else
-    hipLaunchKernelGGL((grn_sumsq_kernel<Bf16>), grid, block, 0, st, a->x, part, p.R, p.L, p.rpc);
-  KVQ_CHECK_LAUNCH("grn_sumsq_kernel");
+  if (int rc = with_operand(a->dtype, [&](auto e) {
+        return launch("grn_sumsq_kernel", grn_sumsq_kernel<decltype(e)>, grid, block, 0, stream, a->x, part, p.R, p.L, p.rpc);
+      }))
+    return rc;
   dim3 fgrid((unsigned)a->W, (unsigned)a->B), fblock(GRN_FIN_THREADS);
-  hipLaunchKernelGGL(grn_finalize_kernel, fgrid, fblock, 0, st, (const float*)part, a->gamma, scale, p.nchunks, a->W, a->N,
-                     a->over_w ? 1 : 0);
-  KVQ_CHECK_LAUNCH("grn_finalize_kernel");
-  if (a->over_w) {
-    hipLaunchKernelGGL(grn_finalize_w_kernel, dim3((unsigned)a->B), fblock, 0, st, a->gamma, scale, a->W, a->N);
-    KVQ_CHECK_LAUNCH("grn_finalize_w_kernel");
-  }
-  return KVQ_OK;
+  if (int rc = launch("grn_finalize_kernel", grn_finalize_kernel, fgrid, fblock, 0, stream, part, a->gamma, scale, p.nchunks, a->W, a->N,
+                      a->over_w ? 1 : 0))
+    return rc;
+  if (!a->over_w) return KVQ_OK;
+  return launch("grn_finalize_w_kernel", grn_finalize_w_kernel, dim3((unsigned)a->B), fblock, 0, stream, a->gamma, scale, a->W, a->N);
 }
 
 extern "C" int kvq_grn_apply(const KvqGrnArgs* a, void* stream) {
   using namespace kvq;
-  const int rc = grn_check(a, "kvq_grn_apply");
-  if (rc != KVQ_OK) return rc;
+  if (int rc = grn_check(a, "kvq_grn_apply")) return rc;
   const GrnPlan p = grn_plan(a->B, a->D, a->H, a->W, a->N);
   KVQ_REQUIRE(p.achunks <= 65535, KVQ_ERR_SHAPE, "kvq_grn_apply: %d row chunks exceed the grid", p.achunks);
-  hipStream_t st = (hipStream_t)stream;
   uint16_t* y = a->y ? a->y : const_cast<uint16_t*>(a->x);
   dim3 grid((unsigned)p.colgroups, (unsigned)p.achunks, (unsigned)a->B), block(GRN_THREADS);
-  if (a->dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL((grn_apply_kernel<Fp16>), grid, block, 0, st, a->x, y, (const float*)a->ws, a->beta, p.R, p.L, a->N, p.arpc);
-  else
-    hipLaunchKernelGGL((grn_apply_kernel<Bf16>), grid, block, 0, st, a->x, y, (const float*)a->ws, a->beta, p.R, p.L, a->N, p.arpc);
-  KVQ_CHECK_LAUNCH("grn_apply_kernel");
-  return KVQ_OK;
+  return with_operand(a->dtype, [&](auto e) {
+    return launch("grn_apply_kernel", grn_apply_kernel<decltype(e)>, grid, block, 0, stream, a->x, y, a->ws, a->beta, p.R, p.L, a->N, p.arpc);
+  });
 }

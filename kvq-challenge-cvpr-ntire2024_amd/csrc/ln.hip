@@ -129,20 +129,13 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnParams p) {
   }
 }
 
-template <typename E, int G, int NV>
-static int launch_ln_e(const LnParams& p, hipStream_t st) {
-  constexpr int R = NV <= 1 ? 4 : (NV <= 3 ? 2 : 1);       // 4-6 float4 loads in flight per lane; more only adds VGPRs
-  const long total = (long)p.n_batch * p.rows_out;
-  const int rows_per_block = (256 / G) * R;
-  dim3 grid((unsigned)((total + rows_per_block - 1) / rows_per_block)), block(256);
-  hipLaunchKernelGGL((layernorm_rows_kernel<E, G, NV, R>), grid, block, 0, st, p);
-  KVQ_CHECK_LAUNCH("layernorm_rows_kernel");
-  return KVQ_OK;
-}
-
 template <int G, int NV>
 static int launch_ln(const LnParams& p, int dtype, hipStream_t st) {
-  return dtype == KVQ_DT_FP16 ? launch_ln_e<Fp16, G, NV>(p, st) : launch_ln_e<Bf16, G, NV>(p, st);
+  constexpr int R = NV <= 1 ? 4 : (NV <= 3 ? 2 : 1);       // 4-6 float4 loads in flight per lane; more only adds VGPRs
+  const long total = (long)p.n_batch * p.rows_out;
+  return with_operand(dtype, [&](auto e) {
+    return launch("layernorm_rows_kernel", layernorm_rows_kernel<decltype(e), G, NV, R>, grid_1d(total, (256 / G) * R), dim3(256), 0, st, p);
+  });
 }
 
 }  // namespace kvq
@@ -161,7 +154,7 @@ int kvq::layernorm_rows_stream(const float* x, int x_f16, const int32_t* map, in
   KVQ_REQUIRE(x && gamma && beta, KVQ_ERR_NULL, "kvq_layernorm_rows: NULL input");
   KVQ_REQUIRE((out_h != nullptr) != (out_f32 != nullptr), KVQ_ERR_NULL,
               "kvq_layernorm_rows: exactly one of out_h/out_f32 must be set");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_layernorm_rows: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_layernorm_rows", dtype);
   KVQ_REQUIRE(nparts >= 1 && n_batch > 0 && rows_in > 0 && rows_out > 0 && Cin > 0 && Cin % 4 == 0,
               KVQ_ERR_SHAPE, "kvq_layernorm_rows: bad shape (nparts=%d n_batch=%d rows=%d/%d Cin=%d)", nparts,
               n_batch, rows_in, rows_out, Cin);

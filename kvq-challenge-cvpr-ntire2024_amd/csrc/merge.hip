@@ -273,19 +273,10 @@ template <typename E, int C_>
 static int launch_merge(const MergeParams& p, hipStream_t st) {
   using G = MGc<C_>;
   const long total = (long)p.B * p.Ln;
-  dim3 grid((unsigned)((total + G::TOK - 1) / G::TOK)), block(64 * G::WAVES);
-  auto go = [&](auto k) -> int {
-    LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(k), G::LDS)) return rc;
-    hipLaunchKernelGGL(k, grid, block, G::LDS, st, p);
-    return KVQ_OK;
-  };
-  int rc;
-  if (p.nr.next_ln) rc = p.x16 ? go(patch_merge_kernel<E, true, C_, true>) : go(patch_merge_kernel<E, true, C_, false>);
-  else rc = p.x16 ? go(patch_merge_kernel<E, false, C_, true>) : go(patch_merge_kernel<E, false, C_, false>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("patch_merge_kernel");
-  return KVQ_OK;
+  void (*k)(MergeParams);
+  if (p.nr.next_ln) k = p.x16 ? patch_merge_kernel<E, true, C_, true> : patch_merge_kernel<E, true, C_, false>;
+  else k = p.x16 ? patch_merge_kernel<E, false, C_, true> : patch_merge_kernel<E, false, C_, false>;
+  return launch("patch_merge_kernel", k, grid_1d(total, G::TOK), dim3(64 * G::WAVES), G::LDS, st, p);
 }
 
 template <typename E>
@@ -294,9 +285,9 @@ static int launch_merge_c(int C, const MergeParams& p, hipStream_t st) {
 }
 
 template <typename E, int C_>
-static void launch_merge_pack(const float* w, const float* g, const float* b, unsigned char* out, hipStream_t st) {
+static int launch_merge_pack(const float* w, const float* g, const float* b, unsigned char* out, void* st) {
   const int total = MGc<C_>::WBYTES / 16 + MGc<C_>::N;
-  hipLaunchKernelGGL((merge_pack_kernel<E, C_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, g, b, out);
+  return launch("merge_pack_kernel", merge_pack_kernel<E, C_>, grid_1d(total), dim3(256), 0, st, w, g, b, out);
 }
 
 }  // namespace kvq
@@ -313,20 +304,14 @@ extern "C" int kvq_patch_merge_pack(const float* red_w, const float* norm_w, con
   using namespace kvq;
   KVQ_REQUIRE(red_w && norm_w && norm_b && pack, KVQ_ERR_NULL, "kvq_patch_merge_pack: NULL pointer");
   KVQ_REQUIRE(kvq_patch_merge_supported(C), KVQ_ERR_UNSUPPORTED, "kvq_patch_merge_pack: C=%d", C);
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_merge_pack: dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
+  KVQ_REQUIRE_OPERAND("kvq_patch_merge_pack", dtype);
   unsigned char* o = (unsigned char*)pack;
-  if (dtype == KVQ_DT_FP16) {
-    if (C == 96) launch_merge_pack<Fp16, 96>(red_w, norm_w, norm_b, o, st);
-    else if (C == 128) launch_merge_pack<Fp16, 128>(red_w, norm_w, norm_b, o, st);
-    else launch_merge_pack<Fp16, 192>(red_w, norm_w, norm_b, o, st);
-  } else {
-    if (C == 96) launch_merge_pack<Bf16, 96>(red_w, norm_w, norm_b, o, st);
-    else if (C == 128) launch_merge_pack<Bf16, 128>(red_w, norm_w, norm_b, o, st);
-    else launch_merge_pack<Bf16, 192>(red_w, norm_w, norm_b, o, st);
-  }
-  KVQ_CHECK_LAUNCH("merge_pack_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    if (C == 96) return launch_merge_pack<E, 96>(red_w, norm_w, norm_b, o, stream);
+    if (C == 128) return launch_merge_pack<E, 128>(red_w, norm_w, norm_b, o, stream);
+    return launch_merge_pack<E, 192>(red_w, norm_w, norm_b, o, stream);
+  });
 }
 
 extern "C" int kvq_patch_merge(const KvqPatchMergeArgs* a, void* stream) {
@@ -340,10 +325,10 @@ int kvq::patch_merge_launch(const KvqPatchMergeArgs* a, RangeFlag range, hipStre
   KVQ_REQUIRE(a->B > 0 && a->L > 0 && a->Ln > 0, KVQ_ERR_SHAPE, "kvq_patch_merge: B=%d L=%d Ln=%d", a->B, a->L, a->Ln);
   MergeParams p{};
   if (int rc = next_rows_fill(p.nr, a, "kvq_patch_merge")) return rc;
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_merge: dtype %d", a->dtype);
+  KVQ_REQUIRE_OPERAND("kvq_patch_merge", a->dtype);
   KVQ_REQUIRE((((size_t)a->x | (size_t)a->out | (size_t)a->merge_map) & 15) == 0, KVQ_ERR_SHAPE, "kvq_patch_merge: 16-byte aligned buffers");
   p.x = a->x; p.map = a->merge_map; p.B = a->B; p.L = a->L; p.Ln = a->Ln; p.pack = (const unsigned char*)a->pack; p.out = a->out; p.x16 = a->x_f16; p.out16 = a->out_f16;
   p.eps = a->eps;
   if (a->out_f16) p.range = range;
-  return a->dtype == KVQ_DT_FP16 ? launch_merge_c<Fp16>(a->C, p, stream) : launch_merge_c<Bf16>(a->C, p, stream);
+  return with_operand(a->dtype, [&](auto e) { return launch_merge_c<decltype(e)>(a->C, p, stream); });
 }

@@ -432,10 +432,7 @@ extern "C" int kvq_resize_bilinear(const void* video, int src_is_u8, int C, int 
     p.std[c] = host_std ? host_std[c] : 1.f;
   }
   const long total = (long)C * T * oh * ow;
-  const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-  hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("resize_bilinear_kernel");
-  return KVQ_OK;
+  return launch("resize_bilinear_kernel", resize_bilinear_kernel, grid_1d(total, 256, 65536), dim3(256), 0, stream, p);
 }
 
 namespace kvq {
@@ -515,10 +512,7 @@ extern "C" int kvq_upsample_frames(const void* video, int src_is_u8, int C, int 
   p.video = video; p.out = out; p.src_is_u8 = src_is_u8; p.C = C; p.T = T; p.H = H; p.W = W; p.OH = od[0]; p.OW = od[1];
   p.scale = (float)(1.0 / scale_factor);
   const long total = (long)C * T * p.OH * p.OW;
-  const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-  hipLaunchKernelGGL(upsample_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("upsample_frames_kernel");
-  return KVQ_OK;
+  return launch("upsample_frames_kernel", upsample_frames_kernel, grid_1d(total, 256, 65536), dim3(256), 0, stream, p);
 }
 
 extern "C" int kvq_patch_im2col(const float* x, int B, int Cin, int T, int H, int W, int pd, int ph, int pw,
@@ -530,18 +524,13 @@ extern "C" int kvq_patch_im2col(const float* x, int B, int Cin, int T, int H, in
   const int D = ceil_div(T, pd), Hh = ceil_div(H, ph), Ww = ceil_div(W, pw);
   const int K = Cin * pd * ph * pw;
   const size_t lds = (size_t)Ww * K * sizeof(uint16_t);
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_patch_im2col: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_patch_im2col", dtype);
   KVQ_REQUIRE(K % 8 == 0 && lds <= 64 * 1024, KVQ_ERR_UNSUPPORTED,
               "kvq_patch_im2col: need K%%8==0 and a token row (%d x %d) of at most 64 KiB", Ww, K);
-  const int grid = B * D * Hh;
-  if (dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL(patch_im2col_kernel<Fp16>, dim3(grid), dim3(256), lds, (hipStream_t)stream, x, B, Cin, T, H, W,
-                       pd, ph, pw, D, Hh, Ww, out);
-  else
-    hipLaunchKernelGGL(patch_im2col_kernel<Bf16>, dim3(grid), dim3(256), lds, (hipStream_t)stream, x, B, Cin, T, H, W,
-                       pd, ph, pw, D, Hh, Ww, out);
-  KVQ_CHECK_LAUNCH("patch_im2col_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("patch_im2col_kernel", patch_im2col_kernel<decltype(e)>, dim3(B * D * Hh), dim3(256), lds, stream, x, B, Cin, T, H, W, pd, ph, pw,
+                  D, Hh, Ww, out);
+  });
 }
 
 namespace kvq {
@@ -551,17 +540,11 @@ static int vqa_head_tokens(const char* who, const float* feat, int B, int L, int
   const bool mfma = w1 && stride_c == 1 && hidden == 64 && C % 64 == 0 && stride_b % 4 == 0 && stride_l % 4 == 0 &&
                     (((size_t)feat | (size_t)w1) & 15) == 0;
   KVQ_REQUIRE(mfma || w1t, KVQ_ERR_NULL, "%s: this shape takes the VALU kernel, which reads w1t", who);
-  if (mfma) {
-    hipLaunchKernelGGL(vqa_head_mfma_kernel, dim3((unsigned)(((long)B * L + 15) / 16)), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
-                       (long)stride_b, (long)stride_l, w1, b1, w2, tok);
-    KVQ_CHECK_LAUNCH("vqa_head_mfma_kernel");
-  } else {
-    const int grid = (int)(((long)B * L + HEAD_TOK - 1) / HEAD_TOK);
-    hipLaunchKernelGGL(vqa_head_token_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, B, L, C,
-                       (long)stride_b, (long)stride_l, (long)stride_c, w1t, b1, hidden, w2, tok);
-    KVQ_CHECK_LAUNCH("vqa_head_token_kernel");
-  }
-  return KVQ_OK;
+  if (mfma)
+    return launch("vqa_head_mfma_kernel", vqa_head_mfma_kernel, grid_1d((long)B * L, 16), dim3(256), 0, stream, feat, B, L, C, stride_b, stride_l,
+                  w1, b1, w2, tok);
+  return launch("vqa_head_token_kernel", vqa_head_token_kernel, grid_1d((long)B * L, HEAD_TOK), dim3(256), 0, stream, feat, B, L, C, stride_b,
+                stride_l, stride_c, w1t, b1, hidden, w2, tok);
 }
 }  // namespace kvq
 
@@ -573,9 +556,7 @@ extern "C" int kvq_vqa_head(const float* feat, int B, int L, int C, int64_t stri
   KVQ_REQUIRE(B > 0 && L > 0 && C > 0 && hidden > 0, KVQ_ERR_SHAPE, "kvq_vqa_head: bad shape");
   const int rc = vqa_head_tokens("kvq_vqa_head", feat, B, L, C, stride_b, stride_l, stride_c, w1t, w1, b1, hidden, w2, scratch, stream);
   if (rc != KVQ_OK) return rc;
-  hipLaunchKernelGGL(mean_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scratch, L, b2, score);
-  KVQ_CHECK_LAUNCH("mean_rows_kernel");
-  return KVQ_OK;
+  return launch("mean_rows_kernel", mean_rows_kernel, dim3(B), dim3(256), 0, stream, scratch, L, b2, score);
 }
 
 extern "C" int kvq_vqa_head_map(const float* feat, int B, int L, int C, int64_t stride_b, int64_t stride_l, int64_t stride_c,
@@ -587,9 +568,7 @@ extern "C" int kvq_vqa_head_map(const float* feat, int B, int L, int C, int64_t 
   KVQ_REQUIRE(D > 0 && L % D == 0, KVQ_ERR_SHAPE, "kvq_vqa_head_map: %d tokens do not split into %d depth slices", L, D);
   const int rc = vqa_head_tokens("kvq_vqa_head_map", feat, B, L, C, stride_b, stride_l, stride_c, w1t, w1, b1, hidden, w2, tok_map, stream);
   if (rc != KVQ_OK) return rc;
-  hipLaunchKernelGGL(mean_rows_map_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, tok_map, L, D, b2, depth_score, score);
-  KVQ_CHECK_LAUNCH("mean_rows_map_kernel");
-  return KVQ_OK;
+  return launch("mean_rows_map_kernel", mean_rows_map_kernel, dim3(B), dim3(256), 0, stream, tok_map, L, D, b2, depth_score, score);
 }
 
 namespace kvq {
@@ -677,18 +656,16 @@ extern "C" int kvq_vqa_head_classes(const float* feat, int B, int L, int C, int6
   int Lh = L;
   float* tok = scratch;
   if (pre_pool) {                     // scratch = pooled [B][C] | token probabilities [B][num_class]
-    hipLaunchKernelGGL(feat_mean_kernel, dim3((C + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, feat, L, C, sb, sl, sc, scratch);
-    KVQ_CHECK_LAUNCH("feat_mean_kernel");
+    if (int rc = launch("feat_mean_kernel", feat_mean_kernel, dim3((C + 255) / 256, B), dim3(256), 0, stream, feat, L, C, sb, sl, sc, scratch))
+      return rc;
     feat = scratch;
     tok = scratch + (size_t)B * C;
     sb = C, sl = 0, sc = 1, Lh = 1;
   }
-  hipLaunchKernelGGL(vqa_head_classes_kernel, dim3((unsigned)((long)B * Lh)), dim3(64), num_class * sizeof(float), (hipStream_t)stream,
-                     feat, Lh, C, sb, sl, sc, w1t, b1, hidden, w2, b2, num_class, tok);
-  KVQ_CHECK_LAUNCH("vqa_head_classes_kernel");
-  hipLaunchKernelGGL(mean_classes_kernel, dim3(B, num_class), dim3(256), 0, (hipStream_t)stream, tok, Lh, num_class, score);
-  KVQ_CHECK_LAUNCH("mean_classes_kernel");
-  return KVQ_OK;
+  if (int rc = launch("vqa_head_classes_kernel", vqa_head_classes_kernel, dim3((unsigned)((long)B * Lh)), dim3(64), num_class * sizeof(float),
+                      stream, feat, Lh, C, sb, sl, sc, w1t, b1, hidden, w2, b2, num_class, tok))
+    return rc;
+  return launch("mean_classes_kernel", mean_classes_kernel, dim3(B, num_class), dim3(256), 0, stream, tok, Lh, num_class, score);
 }
 
 extern "C" int kvq_simple_vqa_head(const float* feat, int B, int T, int Cin, const float* w1, const float* b1,
@@ -697,12 +674,9 @@ extern "C" int kvq_simple_vqa_head(const float* feat, int B, int T, int Cin, con
   using namespace kvq;
   KVQ_REQUIRE(feat && w1 && b1 && w2 && scratch && score, KVQ_ERR_NULL, "kvq_simple_vqa_head: NULL pointer");
   KVQ_REQUIRE(B > 0 && T > 0 && Cin > 0 && hidden > 0, KVQ_ERR_SHAPE, "kvq_simple_vqa_head: bad shape");
-  hipLaunchKernelGGL(simple_head_frame_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, feat, Cin, w1, b1,
-                     hidden, w2, scratch);
-  KVQ_CHECK_LAUNCH("simple_head_frame_kernel");
-  hipLaunchKernelGGL(mean_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scratch, T, b2, score);
-  KVQ_CHECK_LAUNCH("mean_rows_kernel");
-  return KVQ_OK;
+  if (int rc = launch("simple_head_frame_kernel", simple_head_frame_kernel, dim3(B * T), dim3(256), 0, stream, feat, Cin, w1, b1, hidden, w2, scratch))
+    return rc;
+  return launch("mean_rows_kernel", mean_rows_kernel, dim3(B), dim3(256), 0, stream, scratch, T, b2, score);
 }
 
 extern "C" int kvq_fragment_gather(const void* video, int src_is_u8, int C, int T, int H, int W,
@@ -734,11 +708,8 @@ extern "C" int kvq_fragment_gather(const void* video, int src_is_u8, int C, int 
   KVQ_REQUIRE(plane < (1L << 30) && (long)C * T < 65536, KVQ_ERR_SHAPE, "kvq_fragment_gather: output plane / plane count too large");
   const bool vec = fs_w % 4 == 0 && ((size_t)out & 15) == 0;
   p.chan_stride = (long)T * H * W;
-  FragBatch none{};
-  if (vec) hipLaunchKernelGGL((fragment_gather_kernel<4, false>), dim3((unsigned)((plane / 4 + 255) / 256), (unsigned)(C * T)), dim3(256), 0, (hipStream_t)stream, p, none);
-  else hipLaunchKernelGGL((fragment_gather_kernel<1, false>), dim3((unsigned)((plane + 255) / 256), (unsigned)(C * T)), dim3(256), 0, (hipStream_t)stream, p, none);
-  KVQ_CHECK_LAUNCH("fragment_gather_kernel");
-  return KVQ_OK;
+  const auto kern = vec ? fragment_gather_kernel<4, false> : fragment_gather_kernel<1, false>;
+  return launch("fragment_gather_kernel", kern, dim3(grid_1d(vec ? plane / 4 : plane).x, (unsigned)(C * T)), dim3(256), 0, stream, p, FragBatch{});
 }
 
 extern "C" int kvq_fragment_gather_batch(const KvqFragmentSource* f, int C, int T, float* out, void* stream) {
@@ -770,10 +741,9 @@ extern "C" int kvq_fragment_gather_batch(const KvqFragmentSource* f, int C, int 
   const long plane = (long)f->Fh * f->fs_h * f->Fw * f->fs_w;
   KVQ_REQUIRE(plane < (1L << 30) && (long)C * T < 65536, KVQ_ERR_SHAPE, "kvq_fragment_gather_batch: output plane / plane count too large");
   const bool vec = f->fs_w % 4 == 0 && ((size_t)out & 15) == 0;
-  if (vec) hipLaunchKernelGGL((fragment_gather_kernel<4, true>), dim3((unsigned)((plane / 4 + 255) / 256), (unsigned)(C * T), (unsigned)f->n_clips), dim3(256), 0, (hipStream_t)stream, p, fb);
-  else hipLaunchKernelGGL((fragment_gather_kernel<1, true>), dim3((unsigned)((plane + 255) / 256), (unsigned)(C * T), (unsigned)f->n_clips), dim3(256), 0, (hipStream_t)stream, p, fb);
-  KVQ_CHECK_LAUNCH("fragment_gather_kernel");
-  return KVQ_OK;
+  const auto kern = vec ? fragment_gather_kernel<4, true> : fragment_gather_kernel<1, true>;
+  return launch("fragment_gather_kernel", kern, dim3(grid_1d(vec ? plane / 4 : plane).x, (unsigned)(C * T), (unsigned)f->n_clips), dim3(256), 0,
+                stream, p, fb);
 }
 
 // ---- trilinear resize, channels-last (the torch.cat of multi=True feature taps, swin_backbone.py:1070-1075) --------
@@ -823,8 +793,6 @@ extern "C" int kvq_resize_trilinear_cl(const float* src, int B, int D, int H, in
   KVQ_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && C > 0 && Do > 0 && Ho > 0 && Wo > 0 && c_off >= 0 && c_off + C <= c_total,
               KVQ_ERR_SHAPE, "kvq_resize_trilinear_cl: bad geometry");
   const long total = (long)B * Do * Ho * Wo * C;
-  hipLaunchKernelGGL(resize_trilinear_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
-                     D, H, W, C, dst, Do, Ho, Wo, c_total, c_off, total);
-  KVQ_CHECK_LAUNCH("resize_trilinear_cl_kernel");
-  return KVQ_OK;
+  return launch("resize_trilinear_cl_kernel", resize_trilinear_cl_kernel, grid_1d(total), dim3(256), 0, stream, src, D, H, W, C, dst,
+                Do, Ho, Wo, c_total, c_off, total);
 }

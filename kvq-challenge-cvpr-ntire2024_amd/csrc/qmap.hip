@@ -290,19 +290,15 @@ static int paint_run(const char* who, const KvqQualityPaintArgs* a, const KvqQua
       KVQ_REQUIRE(f->video[b], KVQ_ERR_NULL, "%s: clip %d has no frames", who, b);
   }
   const dim3 grid((unsigned)ceil_div(p.Ho, p.band), (unsigned)a->D, (unsigned)f->n_clips);
-  if (rg) hipLaunchKernelGGL(quality_paint_kernel<true>, grid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(quality_paint_kernel<false>, grid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("quality_paint_kernel");
+  if (int rc = launch("quality_paint_kernel", rg ? quality_paint_kernel<true> : quality_paint_kernel<false>, grid, dim3(QM_THREADS), 0, stream, p))
+    return rc;
   if (!a->overlay) return KVQ_OK;
   p.overlay = a->overlay; p.range = a->range; p.n_ov = a->n_ov; p.alpha = a->alpha; p.dim = a->dim;
   p.groups = ceil_div(p.Ws, 4);
   p.band = QM_THREADS / p.groups > 0 ? QM_THREADS / p.groups : 1;
   if (p.band > p.Hs) p.band = p.Hs;
   const dim3 ogrid((unsigned)ceil_div(p.Hs, p.band), (unsigned)a->n_ov, (unsigned)f->n_clips);
-  if (rg) hipLaunchKernelGGL(quality_overlay_kernel<true>, ogrid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(quality_overlay_kernel<false>, ogrid, dim3(QM_THREADS), 0, (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("quality_overlay_kernel");
-  return KVQ_OK;
+  return launch("quality_overlay_kernel", rg ? quality_overlay_kernel<true> : quality_overlay_kernel<false>, ogrid, dim3(QM_THREADS), 0, stream, p);
 }
 
 }  // namespace kvq

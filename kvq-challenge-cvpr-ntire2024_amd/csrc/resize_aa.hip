@@ -241,13 +241,6 @@ extern "C" int kvq_resize_bilinear_aa(const void* video, int src_is_u8, int C, i
               rh, rw, ow);
   const long blocks = (long)planes * p.nbands;
   KVQ_REQUIRE(blocks < (1L << 31), KVQ_ERR_SHAPE, "kvq_resize_bilinear_aa: grid too large");
-  auto go = [&](auto k) -> int {
-    LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(k), (int)lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(AA_THREADS), (size_t)lds, (hipStream_t)stream, p);
-    return KVQ_OK;
-  };
-  if (int rc = src_is_u8 ? go(resize_aa_kernel<uint8_t>) : go(resize_aa_kernel<float>)) return rc;
-  KVQ_CHECK_LAUNCH("resize_aa_kernel");
-  return KVQ_OK;
+  return launch("resize_aa_kernel", src_is_u8 ? resize_aa_kernel<uint8_t> : resize_aa_kernel<float>, dim3((unsigned)blocks), dim3(AA_THREADS),
+                (size_t)lds, stream, p);
 }

@@ -236,7 +236,7 @@ extern "C" int kvq_slow_bottleneck(const uint16_t* x, const int32_t dims4[4], in
                                    uint16_t* out, int out_C, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && dims4 && pack && out, KVQ_ERR_NULL, "kvq_slow_bottleneck: NULL pointer");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_slow_bottleneck: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_slow_bottleneck", dtype);
   KVQ_REQUIRE(kvq_slow_bottleneck_pack_bytes(cin, ci, cout), KVQ_ERR_UNSUPPORTED, "kvq_slow_bottleneck: block (%d, %d, %d) is not built (256, 64, 256 only)",
               cin, ci, cout);
   SlowneckParams p{};
@@ -248,14 +248,7 @@ extern "C" int kvq_slow_bottleneck(const uint16_t* x, const int32_t dims4[4], in
   p.tiles_y = ceil_div(p.H, SN_T); p.tiles_x = ceil_div(p.W, SN_T);
   const long blocks = (long)p.B * p.T * p.tiles_y * p.tiles_x;
   KVQ_REQUIRE(blocks < (1L << 31), KVQ_ERR_UNSUPPORTED, "kvq_slow_bottleneck: %ld tiles", blocks);
-  auto launch = [&](auto kern) -> int {
-    static LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), SN_LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SN_WAVES * 64), SN_LDS_BYTES, (hipStream_t)stream, p);
-    return KVQ_OK;
-  };
-  const int rc = dtype == KVQ_DT_FP16 ? launch(slow_bottleneck_kernel<Fp16>) : launch(slow_bottleneck_kernel<Bf16>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("slow_bottleneck_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("slow_bottleneck_kernel", slow_bottleneck_kernel<decltype(e)>, dim3((unsigned)blocks), dim3(SN_WAVES * 64), SN_LDS_BYTES, stream, p);
+  });
 }

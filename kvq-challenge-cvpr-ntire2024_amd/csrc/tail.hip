@@ -499,21 +499,9 @@ static int launch_tail(const TailParams& p, hipStream_t st) {
   // (the rows are read and written lane per row: an LDS-transposed form of round 5 bought nothing, profiles/r05_tail_staged_ab.txt)
   const size_t lds = (size_t)NST * SLOT + ((((size_t)(4 * C + p.hidden) * 4) + 1023) & ~(size_t)1023) + (size_t)2 * C * 4;
   KVQ_REQUIRE(lds <= (size_t)163840 / tail_bpc(C, NW), KVQ_ERR_UNSUPPORTED, "kvq_block_tail: %zu B of LDS", lds);
-  dim3 grid((unsigned)ceil_div(p.gather ? p.n_tok : p.M, 32 * NW)), block(64 * NW);
-  auto go = [&](auto k) -> int {
-    KVQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, grid, block, lds, st, p);
-    return KVQ_OK;
-  };
-  int rc;
-  if (p.qkv_out) {
-    KVQ_REQUIRE((3 * C / 32) % 2 == 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: q | k | v emission with an odd panel count");
-    rc = go(block_tail_kernel<E, CM, NW, 2>);
-  } else if (p.nr.next_ln) rc = go(block_tail_kernel<E, CM, NW, 1>);
-  else rc = go(block_tail_kernel<E, CM, NW, 0>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("block_tail_kernel");
-  return KVQ_OK;
+  KVQ_REQUIRE(!p.qkv_out || (3 * C / 32) % 2 == 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: q | k | v emission with an odd panel count");
+  const auto k = p.qkv_out ? block_tail_kernel<E, CM, NW, 2> : p.nr.next_ln ? block_tail_kernel<E, CM, NW, 1> : block_tail_kernel<E, CM, NW, 0>;
+  return launch("block_tail_kernel", k, dim3((unsigned)ceil_div(p.gather ? p.n_tok : p.M, 32 * NW)), dim3(64 * NW), lds, st, p);
 }
 
 template <typename E>
@@ -558,11 +546,8 @@ extern "C" int kvq_block_tail_pack(const void* proj_w, const float* proj_b, cons
   const long n_chunks = (long)tail_items(C, hidden) * tail_slot_bytes(C) / 16;
   const long n_par = (long)tail_param_bytes(C, hidden) / 4;
   const long total = n_chunks + n_par;
-  hipLaunchKernelGGL(tail_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)proj_w, (const uint16_t*)fc1_w, (const uint16_t*)fc2_w, proj_b, norm2_w, norm2_b,
-                     fc1_b, fc2_b, C, hidden, (unsigned char*)pack, n_chunks, n_par);
-  KVQ_CHECK_LAUNCH("tail_pack_kernel");
-  return KVQ_OK;
+  return launch("tail_pack_kernel", tail_pack_kernel, grid_1d(total), dim3(256), 0, stream, (const uint16_t*)proj_w, (const uint16_t*)fc1_w,
+                (const uint16_t*)fc2_w, proj_b, norm2_w, norm2_b, fc1_b, fc2_b, C, hidden, (unsigned char*)pack, n_chunks, n_par);
 }
 
 namespace kvq {
@@ -594,10 +579,8 @@ extern "C" int kvq_block_tail_qkv_pack(const void* qkv_w, int C, int hidden, voi
   KVQ_REQUIRE(kvq_block_tail_qkv_pack_bytes(C, hidden) > 0, KVQ_ERR_UNSUPPORTED, "kvq_block_tail_qkv_pack: C=%d hidden=%d", C, hidden);
   if (use_tailmm(C, hidden)) return tailmm_qkv_pack((const uint16_t*)qkv_w, C, hidden, (unsigned char*)pack, (hipStream_t)stream);
   const long n_chunks = (long)kvq_block_tail_qkv_pack_bytes(C, hidden) / 16;
-  hipLaunchKernelGGL(tail_qkv_pack_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)qkv_w, C,
-                     (unsigned char*)pack, n_chunks);
-  KVQ_CHECK_LAUNCH("tail_qkv_pack_kernel");
-  return KVQ_OK;
+  return launch("tail_qkv_pack_kernel", tail_qkv_pack_kernel, grid_1d(n_chunks), dim3(256), 0, stream, (const uint16_t*)qkv_w, C,
+                (unsigned char*)pack, n_chunks);
 }
 
 extern "C" int kvq_block_tail(const KvqBlockTailArgs* a, void* stream) {
@@ -612,7 +595,7 @@ int kvq::block_tail_launch(const KvqBlockTailArgs* a, RangeFlag range, hipStream
   KVQ_REQUIRE(a->M > 0 && a->out_rows > 0 && (!a->scatter_map || a->map_rows > 0), KVQ_ERR_SHAPE, "kvq_block_tail: bad rows");
   TailParams p{};
   if (int rc = next_rows_fill(p.nr, a, "kvq_block_tail")) return rc;
-  KVQ_REQUIRE(a->dtype == KVQ_DT_BF16 || a->dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_block_tail: dtype %d", a->dtype);
+  KVQ_REQUIRE_OPERAND("kvq_block_tail", a->dtype);
   p.attn = (const uint16_t*)a->attn; p.x = a->x; p.x16 = a->x_f16; p.map = a->scatter_map; p.map_rows = a->map_rows; p.out_rows = a->out_rows;
   p.M = a->M; p.hidden = a->hidden; p.pack = (const unsigned char*)a->pack;
   p.eps = a->eps; p.trace = g_trace; p.trace_blocks = g_trace_blocks;
@@ -630,5 +613,5 @@ int kvq::block_tail_launch(const KvqBlockTailArgs* a, RangeFlag range, hipStream
     p.gather = a->attn_gather; p.n_tok = a->M / a->map_rows * a->out_rows; p.map = nullptr;
   }
   if (use_tailmm(a->C, a->hidden)) return tailmm_launch(p, a->C, a->dtype, stream);
-  return a->dtype == KVQ_DT_FP16 ? launch_tail_e<Fp16>(p, a->C, stream) : launch_tail_e<Bf16>(p, a->C, stream);
+  return with_operand(a->dtype, [&](auto e) { return launch_tail_e<decltype(e)>(p, a->C, stream); });
 }

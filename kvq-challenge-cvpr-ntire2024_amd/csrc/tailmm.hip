@@ -173,22 +173,20 @@ __global__ void tailmm_pack_kernel(const uint16_t* wp, const uint16_t* w1, const
 }
 
 template <int CF, int HC>
-static void launch_pack(const uint16_t* wp, const uint16_t* w1, const uint16_t* w2, const float* proj_b, const float* n2w, const float* n2b,
-                        const float* b1, const float* b2, unsigned char* out, hipStream_t st) {
+static int launch_pack(const uint16_t* wp, const uint16_t* w1, const uint16_t* w2, const float* proj_b, const float* n2w, const float* n2b,
+                       const float* b1, const float* b2, unsigned char* out, hipStream_t st) {
   const long total = (long)4 * MMc<CF, HC>::NF * 64 + MMc<CF, HC>::PRM_FLOATS;
-  hipLaunchKernelGGL((tailmm_pack_kernel<CF, HC>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, wp, w1, w2, proj_b, n2w, n2b, b1, b2, out);
+  return launch("tailmm_pack_kernel", tailmm_pack_kernel<CF, HC>, grid_1d(total), dim3(256), 0, st, wp, w1, w2, proj_b, n2w, n2b, b1, b2, out);
 }
 
 int tailmm_pack(const uint16_t* wp, const uint16_t* w1, const uint16_t* w2, const float* proj_b, const float* n2w, const float* n2b,
                 const float* b1, const float* b2, int C, int hidden, unsigned char* out, hipStream_t st) {
-  if (C == 512 && tailmm_hc(C) == 128) launch_pack<4, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  else if (C == 512) launch_pack<4, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  else if (C == 768) launch_pack<6, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  else if (C == 256) launch_pack<2, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  else if (tailmm_hc(C) == 128) launch_pack<3, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  else launch_pack<3, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
-  KVQ_CHECK_LAUNCH("tailmm_pack_kernel");
-  return KVQ_OK;
+  if (C == 512 && tailmm_hc(C) == 128) return launch_pack<4, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
+  if (C == 512) return launch_pack<4, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
+  if (C == 768) return launch_pack<6, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
+  if (C == 256) return launch_pack<2, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
+  if (tailmm_hc(C) == 128) return launch_pack<3, 128>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
+  return launch_pack<3, 256>(wp, w1, w2, proj_b, n2w, n2b, b1, b2, out, st);
 }
 
 // q | k | v of the NEXT block from this launch (round 5): its qkv weight as a fourth fragment list per wave — [which = q, k, v][k-step]
@@ -217,13 +215,8 @@ size_t tailmm_qkv_pack_bytes(int C, int hidden) {
 int tailmm_qkv_pack(const uint16_t* qkv_w, int C, int hidden, unsigned char* out, hipStream_t st) {
   KVQ_REQUIRE(tailmm_supported(C, hidden), KVQ_ERR_UNSUPPORTED, "kvq_block_tail_qkv_pack: C=%d hidden=%d", C, hidden);
   const long total = (long)tailmm_qkv_pack_bytes(C, hidden) / 16;
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (C == 512) hipLaunchKernelGGL(tailmm_qkv_pack_kernel<4>, grid, block, 0, st, qkv_w, out);
-  else if (C == 768) hipLaunchKernelGGL(tailmm_qkv_pack_kernel<6>, grid, block, 0, st, qkv_w, out);
-  else if (C == 256) hipLaunchKernelGGL(tailmm_qkv_pack_kernel<2>, grid, block, 0, st, qkv_w, out);
-  else hipLaunchKernelGGL(tailmm_qkv_pack_kernel<3>, grid, block, 0, st, qkv_w, out);
-  KVQ_CHECK_LAUNCH("tailmm_qkv_pack_kernel");
-  return KVQ_OK;
+  const auto k = C == 512 ? tailmm_qkv_pack_kernel<4> : C == 768 ? tailmm_qkv_pack_kernel<6> : C == 256 ? tailmm_qkv_pack_kernel<2> : tailmm_qkv_pack_kernel<3>;
+  return launch("tailmm_qkv_pack_kernel", k, grid_1d(total), dim3(256), 0, st, qkv_w, out);
 }
 
 #endif  // MM_PART_HERE(0)
@@ -688,21 +681,9 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
 
 template <typename E, int CF, int HC = 256>
 static int launch_mm_cf(const TailParams& p, hipStream_t st) {
-  constexpr int LDS = MMc<CF, HC>::LDS;
-  dim3 grid((unsigned)ceil_div(p.gather ? p.n_tok : p.M, MMc<CF, HC>::TOK)), block(256);
-  auto go = [&](auto k) -> int {
-    LdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(k), LDS)) return rc;
-    hipLaunchKernelGGL(k, grid, block, LDS, st, p);
-    return KVQ_OK;
-  };
-  int rc;
-  if (p.qkv_out) rc = go(block_tailmm_kernel<E, 2, CF, HC>);
-  else if (p.nr.next_ln) rc = go(block_tailmm_kernel<E, 1, CF, HC>);
-  else rc = go(block_tailmm_kernel<E, 0, CF, HC>);
-  if (rc) return rc;
-  KVQ_CHECK_LAUNCH("block_tailmm_kernel");
-  return KVQ_OK;
+  using K = MMc<CF, HC>;
+  const auto k = p.qkv_out ? block_tailmm_kernel<E, 2, CF, HC> : p.nr.next_ln ? block_tailmm_kernel<E, 1, CF, HC> : block_tailmm_kernel<E, 0, CF, HC>;
+  return launch("block_tailmm_kernel", k, dim3((unsigned)ceil_div(p.gather ? p.n_tok : p.M, K::TOK)), dim3(256), K::LDS, st, p);
 }
 
 // the forms, grouped by translation unit (see the top of the file)
@@ -711,7 +692,7 @@ int tailmm_launch_part1(int form, const TailParams& p, int dtype, hipStream_t st
 int tailmm_launch_part2(int form, const TailParams& p, int dtype, hipStream_t st);
 int tailmm_launch_part3(int form, const TailParams& p, int dtype, hipStream_t st);
 enum { MM_F_C512_H128, MM_F_C512_H256, MM_F_C768, MM_F_C256, MM_F_C384_H128, MM_F_C384_H256 };
-#define MM_GO(CF, HC) (dtype == KVQ_DT_FP16 ? launch_mm_cf<Fp16, CF, HC>(p, st) : launch_mm_cf<Bf16, CF, HC>(p, st))
+#define MM_GO(CF, HC) with_operand(dtype, [&](auto e) { return launch_mm_cf<decltype(e), CF, HC>(p, st); })
 #ifndef KVQ_TAILMM_FOCUS
 #if MM_PART_HERE(0)
 int tailmm_launch_part0(int form, const TailParams& p, int dtype, hipStream_t st) { return MM_GO(3, 128); }                                 // C = 384: the C2 line's form

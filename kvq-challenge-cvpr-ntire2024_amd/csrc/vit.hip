@@ -230,10 +230,8 @@ extern "C" int kvq_vit_embed_ln(const float* tok, const float* cls, const float*
   using namespace kvq;
   KVQ_REQUIRE(tok && cls && pos && ln_w && ln_b && out, KVQ_ERR_NULL, "kvq_vit_embed_ln: NULL pointer");
   KVQ_REQUIRE(B > 0 && G > 0 && D > 0, KVQ_ERR_SHAPE, "kvq_vit_embed_ln: bad shape B=%d G=%d D=%d", B, G, D);
-  hipLaunchKernelGGL(vit_embed_ln_kernel, dim3((unsigned)(B * (G + 1))), dim3(256), 0, (hipStream_t)stream, tok, cls, pos, ln_w,
-                     ln_b, G, D, eps, out);
-  KVQ_CHECK_LAUNCH("vit_embed_ln_kernel");
-  return KVQ_OK;
+  return launch("vit_embed_ln_kernel", vit_embed_ln_kernel, dim3((unsigned)(B * (G + 1))), dim3(256), 0, stream, tok, cls, pos, ln_w, ln_b,
+                G, D, eps, out);
 }
 
 extern "C" int kvq_mha_cross(const uint16_t* q, long ldq, const uint16_t* k, long ldk, const uint16_t* v, long ldv, int B, int Lq,
@@ -244,23 +242,14 @@ extern "C" int kvq_mha_cross(const uint16_t* q, long ldq, const uint16_t* k, lon
                   ldv >= (long)heads * head_dim && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0,
               KVQ_ERR_SHAPE, "kvq_mha_cross: bad shape B=%d Lq=%d Lk=%d heads=%d (Lk <= 320, strides multiples of 8)", B, Lq, Lk, heads);
   KVQ_REQUIRE(head_dim == 64, KVQ_ERR_UNSUPPORTED, "kvq_mha_cross: head_dim %d (64 only)", head_dim);
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_mha_cross: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_mha_cross", dtype);
   KVQ_REQUIRE((((size_t)k | (size_t)v) & 15) == 0, KVQ_ERR_SHAPE, "kvq_mha_cross: k / v must be 16-byte aligned");
   MhaParams p{q, k, v, ldq, ldk, ldv, Lq, Lk, heads, scale, out};
   // K + V of the head (16-bit) + the key-split partials of Lq <= 128 (three parts x 64 queries, or one x 128)
   const size_t lds = (size_t)2 * Lk * 64 * sizeof(uint16_t) + (Lq <= 64 ? 3 * 64 : (Lq <= 128 ? 128 : 0)) * (size_t)(64 + 2) * sizeof(float);
-  dim3 grid((unsigned)(B * heads)), block(256);
-  if (dtype == KVQ_DT_FP16) {
-    auto kern = mha_small_kernel<Fp16, 64>;
-    if (lds > 64 * 1024) KVQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, p);
-  } else {
-    auto kern = mha_small_kernel<Bf16, 64>;
-    if (lds > 64 * 1024) KVQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, p);
-  }
-  KVQ_CHECK_LAUNCH("mha_small_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("mha_small_kernel", mha_small_kernel<decltype(e), 64>, dim3((unsigned)(B * heads)), dim3(256), lds, stream, p);
+  });
 }
 
 extern "C" int kvq_mha_small(const uint16_t* qkv, int B, int L, int heads, int head_dim, int dtype, uint16_t* out, void* stream) {
@@ -275,35 +264,29 @@ extern "C" int kvq_cls_gather(const float* x, int B, int L, int D, int dtype, ui
   using namespace kvq;
   KVQ_REQUIRE(x && out, KVQ_ERR_NULL, "kvq_cls_gather: NULL pointer");
   KVQ_REQUIRE(B > 0 && L > 0 && D > 0, KVQ_ERR_SHAPE, "kvq_cls_gather: bad shape");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_cls_gather: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_cls_gather", dtype);
   const long total = (long)B * D;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(cls_gather_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, x, L, D, out, total);
-  else hipLaunchKernelGGL(cls_gather_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, x, L, D, out, total);
-  KVQ_CHECK_LAUNCH("cls_gather_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("cls_gather_kernel", cls_gather_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, x, L, D, out, total);
+  });
 }
 
 extern "C" int kvq_cls_mix(float* x, const uint16_t* a, int B, int L, int D, float ratio, int dtype, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && a, KVQ_ERR_NULL, "kvq_cls_mix: NULL pointer");
   KVQ_REQUIRE(B > 0 && L > 0 && D > 0, KVQ_ERR_SHAPE, "kvq_cls_mix: bad shape");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_cls_mix: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_cls_mix", dtype);
   const long total = (long)B * D;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(cls_mix_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, x, a, L, D, ratio, total);
-  else hipLaunchKernelGGL(cls_mix_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, x, a, L, D, ratio, total);
-  KVQ_CHECK_LAUNCH("cls_mix_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("cls_mix_kernel", cls_mix_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, x, a, L, D, ratio, total);
+  });
 }
 
 extern "C" int kvq_cosine_cls(const float* x, int B, int L, int D, float* out, void* stream) {
   using namespace kvq;
   KVQ_REQUIRE(x && out, KVQ_ERR_NULL, "kvq_cosine_cls: NULL pointer");
   KVQ_REQUIRE(B > 0 && L > 1 && D > 0, KVQ_ERR_SHAPE, "kvq_cosine_cls: bad shape B=%d L=%d D=%d", B, L, D);
-  hipLaunchKernelGGL(cosine_cls_kernel, dim3((unsigned)(B * (L - 1))), dim3(64), 0, (hipStream_t)stream, x, L, D, out);
-  KVQ_CHECK_LAUNCH("cosine_cls_kernel");
-  return KVQ_OK;
+  return launch("cosine_cls_kernel", cosine_cls_kernel, dim3((unsigned)(B * (L - 1))), dim3(64), 0, stream, x, L, D, out);
 }
 
 // ---- KSVQE content-distortion modulation (CDM) pieces, KSVQE_model.py:817-835, :934-960 -----------------------------
@@ -365,20 +348,14 @@ extern "C" int kvq_convert(const void* src, void* dst, long n, int to_half, int 
   using namespace kvq;
   KVQ_REQUIRE(src && dst, KVQ_ERR_NULL, "kvq_convert: NULL pointer");
   KVQ_REQUIRE(n > 0, KVQ_ERR_SHAPE, "kvq_convert: n=%ld", n);
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_convert: dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  if (to_half) {
-    KVQ_REQUIRE((((size_t)src & 15) | ((size_t)dst & 7)) == 0, KVQ_ERR_SHAPE, "kvq_convert: unaligned");
-    dim3 grid((unsigned)((n / 4 + 256) / 256)), block(256);
-    if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(to_half_kernel<Fp16>, grid, block, 0, st, (const float*)src, (uint16_t*)dst, n);
-    else hipLaunchKernelGGL(to_half_kernel<Bf16>, grid, block, 0, st, (const float*)src, (uint16_t*)dst, n);
-  } else {
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(to_float_kernel<Fp16>, grid, block, 0, st, (const uint16_t*)src, (float*)dst, n);
-    else hipLaunchKernelGGL(to_float_kernel<Bf16>, grid, block, 0, st, (const uint16_t*)src, (float*)dst, n);
-  }
-  KVQ_CHECK_LAUNCH("convert kernel");
-  return KVQ_OK;
+  KVQ_REQUIRE_OPERAND("kvq_convert", dtype);
+  if (to_half) KVQ_REQUIRE((((size_t)src & 15) | ((size_t)dst & 7)) == 0, KVQ_ERR_SHAPE, "kvq_convert: unaligned");
+  return with_operand(dtype, [&](auto e) {
+    using E = decltype(e);
+    if (to_half)      // four values per thread, and one thread more for the n % 4 left over
+      return launch("convert kernel", to_half_kernel<E>, grid_1d(n / 4 + 1), dim3(256), 0, stream, (const float*)src, (uint16_t*)dst, n);
+    return launch("convert kernel", to_float_kernel<E>, grid_1d(n), dim3(256), 0, stream, (const uint16_t*)src, (float*)dst, n);
+  });
 }
 
 extern "C" int kvq_sem_modulate(const float* x, const float* input, const float* w_gama, float b_gama, const float* w_beta,
@@ -386,10 +363,8 @@ extern "C" int kvq_sem_modulate(const float* x, const float* input, const float*
   using namespace kvq;
   KVQ_REQUIRE(x && input && w_gama && w_beta && out, KVQ_ERR_NULL, "kvq_sem_modulate: NULL pointer");
   KVQ_REQUIRE(M > 0 && C > 0, KVQ_ERR_SHAPE, "kvq_sem_modulate: bad shape M=%d C=%d", M, C);
-  hipLaunchKernelGGL(sem_modulate_kernel, dim3((unsigned)M), dim3(64), 0, (hipStream_t)stream, x, input, w_gama, b_gama, w_beta,
-                     b_beta, C, out);
-  KVQ_CHECK_LAUNCH("sem_modulate_kernel");
-  return KVQ_OK;
+  return launch("sem_modulate_kernel", sem_modulate_kernel, dim3((unsigned)M), dim3(64), 0, stream, x, input, w_gama, b_gama, w_beta, b_beta,
+                C, out);
 }
 
 extern "C" int kvq_dist_modulate(const float* input, const uint16_t* gamma_logit, const uint16_t* beta, int B, int rows, int C,
@@ -397,15 +372,12 @@ extern "C" int kvq_dist_modulate(const float* input, const uint16_t* gamma_logit
   using namespace kvq;
   KVQ_REQUIRE(input && gamma_logit && beta && out, KVQ_ERR_NULL, "kvq_dist_modulate: NULL pointer");
   KVQ_REQUIRE(B > 0 && rows > 0 && C > 0, KVQ_ERR_SHAPE, "kvq_dist_modulate: bad shape");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_dist_modulate: dtype %d", dtype);
+  KVQ_REQUIRE_OPERAND("kvq_dist_modulate", dtype);
   const long total = (long)B * rows * C;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == KVQ_DT_FP16)
-    hipLaunchKernelGGL(dist_modulate_kernel<Fp16>, grid, block, 0, (hipStream_t)stream, input, gamma_logit, beta, rows, C, out, total);
-  else
-    hipLaunchKernelGGL(dist_modulate_kernel<Bf16>, grid, block, 0, (hipStream_t)stream, input, gamma_logit, beta, rows, C, out, total);
-  KVQ_CHECK_LAUNCH("dist_modulate_kernel");
-  return KVQ_OK;
+  return with_operand(dtype, [&](auto e) {
+    return launch("dist_modulate_kernel", dist_modulate_kernel<decltype(e)>, grid_1d(total), dim3(256), 0, stream, input, gamma_logit, beta,
+                  rows, C, out, total);
+  });
 }
 
 // ---- KSVQE quality-aware region selection (QRS), eval path of RegionNet_CLIP.forward (patchnet.py:461-550) ---------
@@ -479,9 +451,7 @@ extern "C" int kvq_qrs_top_region(const float* score, int BK, int gs, int gh, in
   KVQ_REQUIRE(score && idx, KVQ_ERR_NULL, "kvq_qrs_top_region: NULL pointer");
   KVQ_REQUIRE(BK > 0 && gs > 0 && gh >= kh && gw >= kw && kh > 0 && kw > 0, KVQ_ERR_SHAPE,
               "kvq_qrs_top_region: bad shape gs=%d grid %dx%d window %dx%d", gs, gh, gw, kh, kw);
-  hipLaunchKernelGGL(qrs_top_region_kernel, dim3((unsigned)BK), dim3(64), 0, (hipStream_t)stream, score, gs, gh, gw, kh, kw, idx);
-  KVQ_CHECK_LAUNCH("qrs_top_region_kernel");
-  return KVQ_OK;
+  return launch("qrs_top_region_kernel", qrs_top_region_kernel, dim3((unsigned)BK), dim3(64), 0, stream, score, gs, gh, gw, kh, kw, idx);
 }
 
 extern "C" int kvq_crop_regions(const float* x, const int32_t* region, int B, int C, int T, int H, int W, int anchor, int kh, int kw,
@@ -492,16 +462,11 @@ extern "C" int kvq_crop_regions(const float* x, const int32_t* region, int B, in
               "kvq_crop_regions: bad shape %dx%d anchor %d window %dx%d", H, W, anchor, kh, kw);
   const int oh = kh * anchor, ow = kw * anchor, nx = W / anchor - kw + 1;
   const long total = (long)B * C * T * oh * ow;
-  if (anchor % 4 == 0 && W % 4 == 0 && (((size_t)x | (size_t)out) & 15) == 0) {
-    hipLaunchKernelGGL(crop_regions_vec4_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, region,
-                       C, T, H, W, anchor, nx, oh, ow, out, total / 4);
-    KVQ_CHECK_LAUNCH("crop_regions_vec4_kernel");
-    return KVQ_OK;
-  }
-  hipLaunchKernelGGL(crop_regions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, region, C, T,
-                     H, W, anchor, nx, oh, ow, out, total);
-  KVQ_CHECK_LAUNCH("crop_regions_kernel");
-  return KVQ_OK;
+  if (anchor % 4 == 0 && W % 4 == 0 && (((size_t)x | (size_t)out) & 15) == 0)
+    return launch("crop_regions_vec4_kernel", crop_regions_vec4_kernel, grid_1d(total / 4), dim3(256), 0, stream, x, region, C, T, H, W,
+                  anchor, nx, oh, ow, out, total / 4);
+  return launch("crop_regions_kernel", crop_regions_kernel, grid_1d(total), dim3(256), 0, stream, x, region, C, T, H, W, anchor, nx, oh, ow,
+                out, total);
 }
 
 // F.normalize(x, dim=1) (x / max(||x||_2, 1e-12)) on fp32 rows -> 16-bit (the projector's GEMM operand; CONTRIQUE_model.forward,
@@ -525,11 +490,10 @@ extern "C" int kvq_l2_normalize_rows(const float* x, int M, int D, int dtype, ui
   using namespace kvq;
   KVQ_REQUIRE(x && out, KVQ_ERR_NULL, "kvq_l2_normalize_rows: NULL pointer");
   KVQ_REQUIRE(M > 0 && D > 0, KVQ_ERR_SHAPE, "kvq_l2_normalize_rows: bad shape");
-  KVQ_REQUIRE(dtype == KVQ_DT_BF16 || dtype == KVQ_DT_FP16, KVQ_ERR_UNSUPPORTED, "kvq_l2_normalize_rows: dtype %d", dtype);
-  if (dtype == KVQ_DT_FP16) hipLaunchKernelGGL(l2_normalize_rows_kernel<Fp16>, dim3((unsigned)M), dim3(64), 0, (hipStream_t)stream, x, D, out);
-  else hipLaunchKernelGGL(l2_normalize_rows_kernel<Bf16>, dim3((unsigned)M), dim3(64), 0, (hipStream_t)stream, x, D, out);
-  KVQ_CHECK_LAUNCH("l2_normalize_rows_kernel");
-  return KVQ_OK;
+  KVQ_REQUIRE_OPERAND("kvq_l2_normalize_rows", dtype);
+  return with_operand(dtype, [&](auto e) {
+    return launch("l2_normalize_rows_kernel", l2_normalize_rows_kernel<decltype(e)>, dim3((unsigned)M), dim3(64), 0, stream, x, D, out);
+  });
 }
 
 // out = a * x + b * y (fp32, n elements): the fixed mixes of KSVQE.forward (0.2 / 0.8 adapter blend :1426, (a1 x_d + a2 x_s) / 2 :1482)
@@ -544,7 +508,5 @@ extern "C" int kvq_axpby(const float* x, const float* y, float a, float b, float
   using namespace kvq;
   KVQ_REQUIRE(x && y && out, KVQ_ERR_NULL, "kvq_axpby: NULL pointer");
   KVQ_REQUIRE(n > 0, KVQ_ERR_SHAPE, "kvq_axpby: n=%ld", n);
-  hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, a, b, out, n);
-  KVQ_CHECK_LAUNCH("axpby_kernel");
-  return KVQ_OK;
+  return launch("axpby_kernel", axpby_kernel, grid_1d(n), dim3(256), 0, stream, x, y, a, b, out, n);
 }

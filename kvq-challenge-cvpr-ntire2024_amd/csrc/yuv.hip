@@ -103,8 +103,6 @@ extern "C" int kvq_yuv420_to_rgb(const void* frames, int T, int H, int W, int fo
   YuvParams p{};
   p.frames = (const uint8_t*)frames; p.out = rgb_out; p.T = T; p.H = H; p.W = W;
   p.groups = ceil_div(W, 16); p.pairs = (H + 1) / 2; p.k = yuv420_coeffs(format);
-  hipLaunchKernelGGL(yuv420_to_rgb_kernel, dim3((unsigned)ceil_div(p.groups * p.pairs, 256), (unsigned)T), dim3(256), 0,
-                     (hipStream_t)stream, p);
-  KVQ_CHECK_LAUNCH("yuv420_to_rgb_kernel");
-  return KVQ_OK;
+  return launch("yuv420_to_rgb_kernel", yuv420_to_rgb_kernel, dim3((unsigned)ceil_div(p.groups * p.pairs, 256), (unsigned)T), dim3(256), 0,
+                stream, p);
 }

@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/kvq_hip.h declares (no compute
 calls without a GPU); host-side module logic (state_dict surface, config dispatch, error paths)."""
+import ctypes
 import os
 import re
 
@@ -93,6 +94,90 @@ def test_error_paths_without_gpu():
     assert rc == -3          # num_stages == 0 -> unsupported, reported not crashed
     with pytest.raises(_abi.KvqError):
         _abi.check(rc, "plan")
+
+
+_HOST_BUFFER = (ctypes.c_char * 4112)()
+
+
+def _operand_guard_cases():
+    """(entry, arguments, text of kvq_last_error()) for the exported entries that take an operand dtype and check it before their
+    first HIP call: a valid small shape, real int32 / int64 arrays where the entry reads them on the host, one 16-byte-aligned host
+    buffer for every pointer, and dtype 7.  The texts are pinned as they are: an entry that delegates answers in its delegate's name."""
+    import ctypes as C
+    i32 = C.c_int32
+    P = C.c_void_p((C.addressof(_HOST_BUFFER) + 15) & ~15)
+    BAD = 7
+    dims5, dims4 = (i32 * 5)(1, 3, 2, 8, 8), (i32 * 4)(1, 2, 8, 8)
+    k3, s3, p3 = (i32 * 3)(1, 7, 7), (i32 * 3)(1, 2, 2), (i32 * 3)(0, 3, 3)
+    strides5 = (C.c_int64 * 5)(384, 128, 64, 8, 1)
+
+    def struct(cls, **kw):
+        a = cls()
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    attn32 = struct(_abi.KvqAttnDenseArgs, qkv=P, bias_dense=P, n_types=1, BW=1, nW=1, N=8, num_heads=1, dtype=BAD, out=P, dsplit_from=-1)
+    gemm = struct(_abi.KvqGemmArgs, A=P, W=P, M=8, N=8, K=32, epilogue=_abi.EPI_RESID_F32, out_f32=P, resid_f32=P, dtype=BAD)
+    conv = struct(_abi.KvqConvArgs, x=P, W=P, dims5=dims5, kernel3=k3, stride3=s3, pad3=p3, Kpad=32, N=8, epilogue=_abi.EPI_BIAS_BF16,
+                  dtype=BAD, out_bf16=P)
+    dw = struct(_abi.KvqDwconvLnArgs, x=P, w=P, bias=P, ln_w=P, ln_b=P, B=1, T=1, H=2, W=2, C=96, kt=1, eps=1e-6, dtype=BAD, out_h=P)
+    grn = struct(_abi.KvqGrnArgs, x=P, y=P, gamma=P, beta=P, ws=P, B=1, D=1, H=2, W=2, N=384, dtype=BAD)
+    tail = struct(_abi.KvqBlockTailArgs, attn=P, x=P, out_rows=32, M=32, C=96, hidden=384, pack=P, eps=1e-5, dtype=BAD)
+    embed = struct(_abi.KvqPatchEmbedArgs, x=P, B=1, in_chans=3, T=2, H=32, W=32, pd=2, ph=4, pw=4, embed_dim=96, pack=P, out=P, eps=1e-5,
+                   dtype=BAD)
+    merge = struct(_abi.KvqPatchMergeArgs, x=P, merge_map=P, B=1, L=128, Ln=32, C=96, pack=P, out=P, eps=1e-5, dtype=BAD)
+    ops, tensors, net = (_abi.KvqNetOp * 1)(), (_abi.KvqNetTensor * 2)(), C.c_void_p()
+    cfg, plan = struct(_abi.KvqSwinCfg, num_stages=1), C.c_void_p()
+    return [
+        ("kvq_mha_cross", (P, 64, P, 64, P, 64, 1, 4, 4, 1, 64, 0.125, BAD, P, None), "kvq_mha_cross: dtype 7"),
+        ("kvq_mha_small", (P, 1, 4, 1, 64, BAD, P, None), "kvq_mha_cross: dtype 7"),
+        ("kvq_cls_gather", (P, 1, 2, 8, BAD, P, None), "kvq_cls_gather: dtype 7"),
+        ("kvq_cls_mix", (P, P, 1, 2, 8, 0.5, BAD, None), "kvq_cls_mix: dtype 7"),
+        ("kvq_convert", (P, P, 8, 1, BAD, None), "kvq_convert: dtype 7"),
+        ("kvq_dist_modulate", (P, P, P, 1, 2, 8, BAD, P, None), "kvq_dist_modulate: dtype 7"),
+        ("kvq_l2_normalize_rows", (P, 2, 8, BAD, P, None), "kvq_l2_normalize_rows: dtype 7"),
+        ("kvq_patch_im2col", (P, 1, 3, 2, 8, 8, 2, 4, 4, BAD, P, None), "kvq_patch_im2col: dtype 7"),
+        ("kvq_pack_clip_cl4", (P, dims5, 4, BAD, P, None), "kvq_pack_clip_cl4: dtype 7"),
+        ("kvq_conv_stem_mfma", (P, dims4, P, P, k3, s3, p3, 1, BAD, P, None), "kvq_conv_stem_mfma: dtype 7"),
+        ("kvq_conv_stem_pool", (P, dims5, P, P, 1, 1, BAD, P, None), "kvq_conv_stem_pool: dtype 7"),
+        ("kvq_conv_stem64_pool", (P, dims5, None, 2, P, P, 1, BAD, P, 64, 0, None), "kvq_conv_stem64_pool: dtype 7"),
+        ("kvq_im2col_nd", (P, 1, BAD, strides5, dims5, k3, s3, p3, 160, P, None), "kvq_im2col_nd: dtype 7"),
+        ("kvq_pool_nd", (P, BAD, dims5, k3, s3, p3, 1, P, None), "kvq_pool_nd: dtype 7"),
+        ("kvq_pool_nd_strided", (P, BAD, dims5, k3, s3, p3, 1, P, 8, 0, None), "kvq_pool_nd: dtype 7"),
+        ("kvq_pack_channels_last8", (P, dims5, strides5, BAD, P, None), "kvq_pack_channels_last8: dtype 7"),
+        ("kvq_mean_std_pool", (P, BAD, 2, 4, 8, P, 16, 0, 8, None), "kvq_mean_std_pool: dtype 7"),
+        ("kvq_conv_stem_direct", (P, dims5, P, P, 8, k3, s3, p3, 1, BAD, P, None), "kvq_conv_stem_direct: dtype 7"),
+        ("kvq_window_attention", (P, P, P, None, None, 8, 0, 1, 1, 8, 1, 0, BAD, P, None), "kvq_window_attention: dtype 7"),
+        ("kvq_window_attention32", (attn32, None), "kvq_window_attention32: dtype 7"),
+        ("kvq_window_attention32_ranges", (attn32, P, None), "kvq_window_attention32_ranges: dtype 7"),
+        ("kvq_fast_bottleneck", (P, dims4, 8, 8, 32, 1, 1, P, BAD, P, None), "kvq_fast_bottleneck: dtype 7"),
+        ("kvq_slow_bottleneck", (P, dims4, 256, 64, 256, P, BAD, P, 256, None), "kvq_slow_bottleneck: dtype 7"),
+        ("kvq_layernorm_rows", (P, None, 1, 1, 2, 2, 8, P, P, 1e-5, P, BAD, None, None), "kvq_layernorm_rows: dtype 7"),
+        ("kvq_dwconv3d_ln", (dw, None), "kvq_dwconv3d_ln: dtype 7"),
+        ("kvq_patch_embed", (embed, None), "kvq_patch_embed: dtype 7"),
+        ("kvq_patch_merge_pack", (P, P, P, 96, BAD, P, None), "kvq_patch_merge_pack: dtype 7"),
+        ("kvq_patch_merge", (merge, None), "kvq_patch_merge: dtype 7"),
+        ("kvq_gemm_bf16", (gemm, None), "kvq_gemm_bf16: unknown dtype 7"),
+        ("kvq_gemm_resid_scaled", (gemm, P, None), "kvq_gemm_bf16: unknown dtype 7"),
+        ("kvq_qkv_fill_pad", (P, P, P, 1, 1, 8, 1, 1.0, BAD, None), "kvq_qkv_fill_pad: dtype 7"),
+        ("kvq_conv_implicit", (conv, None), "kvq_conv_implicit: dtype 7"),
+        ("kvq_grn_stats", (grn, None), "kvq_grn_stats: dtype 7"),
+        ("kvq_grn_apply", (grn, None), "kvq_grn_apply: dtype 7"),
+        ("kvq_block_tail", (tail, None), "kvq_block_tail: dtype 7"),
+        ("kvq_convnet_create", (ops, 1, tensors, 2, 1, 1, BAD, C.byref(net)), "kvq_convnet_create: dtype 7"),
+        ("kvq_swin3d_plan_create", (C.byref(cfg), 1, 2, 32, 32, BAD, C.byref(plan)), "unknown dtype 7"),
+    ]
+
+
+def test_unknown_operand_dtype_is_refused_before_any_launch():
+    handle = _abi.lib()
+    cases = _operand_guard_cases()
+    assert len({name for name, _, _ in cases}) == len(cases)
+    for name, args, text in cases:
+        rc = getattr(handle, name)(*args)
+        assert rc == -3, (name, rc, handle.kvq_last_error())          # KVQ_ERR_UNSUPPORTED
+        assert handle.kvq_last_error().decode() == text, (name, handle.kvq_last_error())
 
 
 def test_state_dict_surface_matches_reference_keys():
