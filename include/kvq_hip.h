@@ -699,6 +699,50 @@ int kvq_fragment_gather_batch(const KvqFragmentSource* src, int C, int T, float*
 int kvq_yuv420_coeffs(int format /* KVQ_SRC_I420_* */, int32_t host_out6[6]);
 int kvq_yuv420_to_rgb(const void* frames, int T, int H, int W, int format, uint8_t* rgb_out, void* stream);
 
+/* Baseline JPEG (Motion-JPEG frames) -> I420 frames of format KVQ_SRC_I420_BT601_FULL, no codec library: the entropy decode on the
+ * host (csrc/jpeg.cpp, plain C++, no HIP call), dequantisation + inverse DCT on the device (csrc/jpeg.hip) or by its scalar twin.
+ * The hand-over between the two is dense: per frame QUANTISED coefficients as int16, every 8 x 8 block 64 values in natural
+ * (de-zigzagged) order, index 8 v + u for vertical frequency v and horizontal frequency u, the blocks de-interleaved from MCU order
+ * into per-plane block raster over the MCU-padded planes: with mx = ceil(W / 16), my = ceil(H / 16) the Y blocks (2 my rows of 2 mx),
+ * then Cb (my rows of mx), then Cr — 768 bytes per 16 x 16 MCU (kvq_jpeg_coef_bytes) — and the three components' quantiser tables
+ * as uint16 [3][64], natural order too (they may differ from frame to frame).
+ *
+ * kvq_jpeg_probe (host only) walks the segments of the image at data[0 .. n) up to its SOS and fills `info`.  KVQ_OK with
+ * info->supported = 1 for what the library decodes: SOF0 (baseline, 8-bit, Huffman), three components sampled Y 2x2, Cb 1x1, Cr 1x1
+ * (4:2:0), 8-bit quantiser tables.  Several tables in one DQT / DHT segment, APPn and COM segments, fill 0xFF bytes before a marker,
+ * DRI / RSTn are accepted; a stream without DHT uses the tables of ITU-T T.81 Annex K (AVI "MJPG" frames).  KVQ_ERR_UNSUPPORTED with
+ * info->supported = 0 and the cause in kvq_last_error: progressive and every other SOFn, 12-bit precision, 16-bit quantiser tables,
+ * any other sampling (the factors are named), one or four components, an Adobe APP14 segment with transform 0.  KVQ_ERR_SHAPE: not
+ * a JPEG image, or its segments are cut short.  info->frame_bytes: the image's length up to and including its EOI (the next image
+ * of a concatenated stream starts there), 0 when no EOI follows the scan inside n.  No read leaves data[0 .. n).
+ *
+ * kvq_jpeg_coeffs (host only) entropy-decodes one such image: coef_out receives kvq_jpeg_coef_bytes(H, W) bytes of coefficients
+ * (coef_cap = the capacity of coef_out in bytes; a smaller one is KVQ_ERR_WORKSPACE, nothing written), qt_out the tables.  Byte
+ * stuffing, DC prediction and its reset at every RSTn, EOB, ZRL and code lengths up to 16 bits are handled; a truncated stream, a
+ * code that is in no table, a run past coefficient 63, a wrong or missing RSTn and a missing EOI are KVQ_ERR_SHAPE with a message —
+ * never a read past n or a write past coef_cap (the contents of coef_out are then unspecified).
+ *
+ * kvq_jpeg_idct_i420: coef = T frames of coefficients (device, back to back), qt = uint16 [T][3][64] (device) ->
+ * frames_out uint8 (T, H W + 2 ceil(H/2) ceil(W/2)): T I420 frames, Y | U | V, the MCU padding cropped.  One launch; sample =
+ * clamp(idct(coef * q) + 128) with the integer inverse DCT csrc/jpeg_idct.hpp defines to the bit (two passes, 13-bit constants,
+ * the rounding of the IJG library's default decoder), exact for sum |coef * q| <= 8192 per block and an unspecified byte beyond.
+ * kvq_jpeg_idct_i420_host: the same on host memory, bit-equal.  T in 1..65535, H, W in 1..65535 with H W < 2^28; coef and qt of
+ * the launch 16-byte aligned (frames of coefficients are multiples of 768 bytes, tables of 384); anything else is KVQ_ERR_SHAPE. */
+typedef struct KvqJpegInfo {
+  int32_t width, height;
+  int32_t ncomp;             /* components of the frame header */
+  int32_t hsamp[4], vsamp[4];/* their sampling factors */
+  int32_t restart_interval;  /* MCUs between RSTn markers, 0 = none */
+  int32_t supported;         /* 1: kvq_jpeg_coeffs decodes it */
+  int32_t has_dht;           /* 0: no DHT segment, the Annex K tables apply */
+  int64_t frame_bytes;       /* length up to and including EOI, 0 = no EOI inside n */
+} KvqJpegInfo;
+size_t kvq_jpeg_coef_bytes(int H, int W);
+int kvq_jpeg_probe(const uint8_t* data, size_t n, KvqJpegInfo* info);
+int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out, size_t coef_cap, uint16_t* qt_out);
+int kvq_jpeg_idct_i420_host(const int16_t* coef, const uint16_t* qt, int T, int H, int W, uint8_t* frames_out);
+int kvq_jpeg_idct_i420(const void* coef, const void* qt, int T, int H, int W, uint8_t* frames_out, void* stream);
+
 /* torchvision Resize on a tensor (= bilinear, align_corners=False, no antialias; get_resize_function,
  * fusion_datasets.py:229-241) + crop + (v-mean)/std: get_resized_video (:244-252), get_resizecrop_video
  * (:299-316).  video u8|fp32 (C,T,H,W) -> resized to (rh,rw) -> crop [cy:cy+oh, cx:cx+ow] -> out fp32

@@ -167,6 +167,11 @@ class KvqPatchMergeArgs(C.Structure):
                 ("next_ln", p_void), ("next_rows", C.c_int32), ("eps", C.c_float), ("dtype", C.c_int32), ("x_f16", C.c_int32), ("out_f16", C.c_int32)]
 
 
+class KvqJpegInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hsamp", C.c_int32 * 4), ("vsamp", C.c_int32 * 4),
+                ("restart_interval", C.c_int32), ("supported", C.c_int32), ("has_dht", C.c_int32), ("frame_bytes", C.c_int64)]
+
+
 class KvqProfRecord(C.Structure):
     _fields_ = [("kind", C.c_int32), ("variant", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -296,6 +301,11 @@ SYMBOLS = {
     "kvq_mean_std_pool": (i32, [p_void, i32, i32, i32, i32, p_void, i64, i32, i32, p_void]),
     "kvq_yuv420_coeffs": (i32, [i32, C.POINTER(i32 * 6)]),
     "kvq_yuv420_to_rgb": (i32, [p_void, i32, i32, i32, i32, p_void, p_void]),
+    "kvq_jpeg_coef_bytes": (sz, [i32, i32]),
+    "kvq_jpeg_probe": (i32, [p_void, sz, C.POINTER(KvqJpegInfo)]),
+    "kvq_jpeg_coeffs": (i32, [p_void, sz, p_void, sz, p_void]),
+    "kvq_jpeg_idct_i420_host": (i32, [p_void, p_void, i32, i32, i32, p_void]),
+    "kvq_jpeg_idct_i420": (i32, [p_void, p_void, i32, i32, i32, p_void, p_void]),
     "kvq_fragment_gather_batch": (i32, [C.POINTER(KvqFragmentSource), i32, i32, p_void, p_void]),
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),

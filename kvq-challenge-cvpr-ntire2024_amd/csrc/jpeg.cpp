@@ -1,0 +1,448 @@
+// Host half of the Motion-JPEG reader (include/kvq_hip.h, "Baseline JPEG"): segment walk (kvq_jpeg_probe), baseline Huffman entropy
+// decode into the dense int16 coefficient hand-over (kvq_jpeg_coeffs) and the scalar twin of the IDCT launch
+// (kvq_jpeg_idct_i420_host).  Plain C++17: no HIP call and no HIP header, so the file also compiles with the host compiler alone
+// (tools/jpeg_hostcheck.cpp builds it under the address and undefined-behaviour sanitizers).  Every read of the stream goes through
+// a bounds check against n; every coefficient is written at an index computed from the frame's own geometry, inside the
+// kvq_jpeg_coef_bytes(H, W) that coef_cap was checked against.
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../include/kvq_hip.h"
+#include "jpeg_idct.hpp"
+
+namespace kvq {
+void set_error(const char* fmt, ...);      // common.cpp (the stand-alone check program brings its own)
+}
+
+namespace {
+
+#define JPEG_REQUIRE(cond, code, ...)  \
+  do {                                 \
+    if (!(cond)) {                     \
+      kvq::set_error(__VA_ARGS__);     \
+      return code;                     \
+    }                                  \
+  } while (0)
+
+const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ITU-T T.81 Annex K.3: the tables of a stream that carries no DHT segment
+const uint8_t STD_DC_LUM_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+const uint8_t STD_DC_CHR_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+const uint8_t STD_DC_VALS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t STD_AC_LUM_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125};
+const uint8_t STD_AC_LUM_VALS[162] = {
+    1,   2,   3,   0,   4,   17,  5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161, 8,   35,  66,  177,
+    193, 21,  82,  209, 240, 36,  51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,  39,  40,  41,  42,  52,  53,  54,  55,
+    56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106,
+    115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163,
+    164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211,
+    212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+const uint8_t STD_AC_CHR_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119};
+const uint8_t STD_AC_CHR_VALS[162] = {
+    0,   1,   2,   3,   17,  4,   5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,  145, 161, 177, 193,
+    9,   35,  51,  82,  240, 21,  98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,  26,  38,  39,  40,  41,  42,  53,  54,
+    55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105,
+    106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154,
+    162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202,
+    210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+
+// canonical Huffman code of one table: codes of length l run from mincode[l] to maxcode[l]; the first 9 bits resolve short codes at once
+struct Huff {
+  bool present;
+  int32_t mincode[17], maxcode[17], valptr[17];
+  uint8_t vals[256];
+  uint16_t look[512];      // (length << 8) | symbol for codes of 1..9 bits, 0 = longer
+};
+
+bool huff_build(Huff& h, const uint8_t bits[16], const uint8_t* vals, int nvals) {
+  memset(&h, 0, sizeof(h));
+  memcpy(h.vals, vals, (size_t)nvals);
+  int32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    h.valptr[l] = k;
+    h.mincode[l] = code;
+    const int cnt = bits[l - 1];
+    if (code + cnt > (1 << l)) return false;          // more codes of this length than the prefix code has room for
+    if (l <= 9)
+      for (int i = 0; i < cnt; ++i)
+        for (int f = 0; f < (1 << (9 - l)); ++f) h.look[((code + i) << (9 - l)) | f] = (uint16_t)((l << 8) | vals[k + i]);
+    code += cnt;
+    k += cnt;
+    h.maxcode[l] = cnt ? code - 1 : -1;
+    code <<= 1;
+  }
+  h.present = true;
+  return true;
+}
+
+struct Comp {
+  int id, h, v, tq, td, ta;
+};
+
+struct Parsed {
+  KvqJpegInfo info;
+  Comp comp[4];
+  uint16_t qt[4][64];      // natural order
+  bool qt_present[4];
+  Huff dc[4], ac[4];
+  size_t scan;             // offset of the first entropy-coded byte
+  int why_rank;            // the strongest reason the image is outside what the library decodes
+  char why[200];
+};
+
+void refuse(Parsed& p, int rank, const char* fmt, ...) {
+  if (rank <= p.why_rank) return;
+  p.why_rank = rank;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(p.why, sizeof(p.why), fmt, ap);
+  va_end(ap);
+}
+
+// the marker at data[pos]: 0xFF, any number of fill 0xFF, the code; pos moves past it.  false: no marker there / cut short
+bool read_marker(const uint8_t* d, size_t n, size_t& pos, int& marker) {
+  if (pos >= n || d[pos] != 0xFF) return false;
+  while (pos < n && d[pos] == 0xFF) ++pos;
+  if (pos >= n) return false;
+  marker = d[pos++];
+  return marker != 0;
+}
+
+// entropy-coded bytes from pos: the offset of the next marker's 0xFF (stuffed FF 00 and RSTn are data), n if there is none
+size_t skip_scan(const uint8_t* d, size_t n, size_t pos) {
+  while (pos + 1 < n) {
+    if (d[pos] != 0xFF) { ++pos; continue; }
+    const int b = d[pos + 1];
+    if (b == 0x00 || (b >= 0xD0 && b <= 0xD7)) { pos += 2; continue; }
+    if (b == 0xFF) { ++pos; continue; }
+    return pos;
+  }
+  return n;
+}
+
+int parse(const uint8_t* d, size_t n, Parsed& p, const char* who) {
+  memset(&p.info, 0, sizeof(p.info));
+  memset(p.qt_present, 0, sizeof(p.qt_present));
+  memset(p.comp, 0, sizeof(p.comp));
+  for (int i = 0; i < 4; ++i) p.dc[i].present = p.ac[i].present = false;
+  p.scan = 0; p.why_rank = 0; p.why[0] = 0;
+  JPEG_REQUIRE(n >= 4 && d[0] == 0xFF && d[1] == 0xD8, KVQ_ERR_SHAPE, "%s: not a JPEG image (no SOI marker at its start)", who);
+  size_t pos = 2;
+  bool have_sof = false;
+  for (;;) {
+    int m = 0;
+    const size_t at = pos;
+    JPEG_REQUIRE(read_marker(d, n, pos, m), KVQ_ERR_SHAPE, "%s: no marker at byte %zu (the stream is cut short or not a JPEG image)", who, at);
+    JPEG_REQUIRE(m != 0xD9 && m != 0xD8 && !(m >= 0xD0 && m <= 0xD7) && m != 0x01, KVQ_ERR_SHAPE,
+                 "%s: marker FF%02X at byte %zu before any scan", who, m, at);
+    JPEG_REQUIRE(pos + 2 <= n, KVQ_ERR_SHAPE, "%s: segment FF%02X at byte %zu is cut short", who, m, at);
+    const size_t L = ((size_t)d[pos] << 8) | d[pos + 1];
+    JPEG_REQUIRE(L >= 2 && pos + L <= n, KVQ_ERR_SHAPE, "%s: segment FF%02X at byte %zu is cut short (length %zu)", who, m, at, L);
+    const uint8_t* s = d + pos + 2;
+    const size_t sl = L - 2;
+    pos += L;
+    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {           // SOFn
+      JPEG_REQUIRE(!have_sof, KVQ_ERR_SHAPE, "%s: a second frame header at byte %zu", who, at);
+      JPEG_REQUIRE(sl >= 6 && sl >= 6 + 3 * (size_t)s[5], KVQ_ERR_SHAPE, "%s: frame header at byte %zu is cut short", who, at);
+      have_sof = true;
+      if (m == 0xC2) refuse(p, 9, "%s: progressive JPEG (SOF2) is not decoded, baseline only", who);
+      else if (m != 0xC0) refuse(p, 9, "%s: SOF%d (%s) is not decoded, baseline SOF0 only", who, m - 0xC0,
+                                 m == 0xC1 ? "extended sequential" : m == 0xC3 ? "lossless" : m >= 0xC9 ? "arithmetic coding" : "hierarchical");
+      if (s[0] != 8) refuse(p, 8, "%s: %d-bit sample precision is not decoded, 8-bit only", who, (int)s[0]);
+      p.info.height = (s[1] << 8) | s[2];
+      p.info.width = (s[3] << 8) | s[4];
+      p.info.ncomp = s[5];
+      JPEG_REQUIRE(p.info.width > 0 && p.info.height > 0, KVQ_ERR_SHAPE, "%s: frame header with size %d x %d", who, p.info.width, p.info.height);
+      JPEG_REQUIRE(p.info.ncomp >= 1 && p.info.ncomp <= 4, KVQ_ERR_SHAPE, "%s: frame header with %d components", who, p.info.ncomp);
+      for (int c = 0; c < p.info.ncomp; ++c) {
+        Comp& k = p.comp[c];
+        k.id = s[6 + 3 * c]; k.h = s[7 + 3 * c] >> 4; k.v = s[7 + 3 * c] & 15; k.tq = s[8 + 3 * c];
+        p.info.hsamp[c] = k.h; p.info.vsamp[c] = k.v;
+        JPEG_REQUIRE(k.tq <= 3 && k.h >= 1 && k.h <= 4 && k.v >= 1 && k.v <= 4, KVQ_ERR_SHAPE, "%s: frame header component %d is malformed", who, c);
+      }
+      if (p.info.ncomp != 3)
+        refuse(p, 7, "%s: %d component%s (%s) — three components Y Cb Cr only", who, p.info.ncomp, p.info.ncomp == 1 ? "" : "s",
+               p.info.ncomp == 1 ? "grayscale" : p.info.ncomp == 4 ? "CMYK / YCCK" : "two planes");
+      else if (!(p.comp[0].h == 2 && p.comp[0].v == 2 && p.comp[1].h == 1 && p.comp[1].v == 1 && p.comp[2].h == 1 && p.comp[2].v == 1))
+        refuse(p, 6, "%s: sampling factors Y %dx%d Cb %dx%d Cr %dx%d — 4:2:0 (Y 2x2 Cb 1x1 Cr 1x1) only", who, p.comp[0].h, p.comp[0].v,
+               p.comp[1].h, p.comp[1].v, p.comp[2].h, p.comp[2].v);
+    } else if (m == 0xDB) {                                                           // DQT, any number of tables
+      size_t q = 0;
+      while (q < sl) {
+        const int pq = s[q] >> 4, tq = s[q] & 15;
+        const size_t need = 1 + (pq ? 128 : 64);
+        JPEG_REQUIRE(pq <= 1 && tq <= 3 && q + need <= sl, KVQ_ERR_SHAPE, "%s: quantiser table segment at byte %zu is malformed", who, at);
+        if (pq) refuse(p, 5, "%s: 16-bit quantiser table %d is not decoded, 8-bit tables only", who, tq);
+        for (int i = 0; i < 64; ++i) p.qt[tq][ZIGZAG[i]] = pq ? (uint16_t)((s[q + 1 + 2 * i] << 8) | s[q + 2 + 2 * i]) : s[q + 1 + i];
+        p.qt_present[tq] = true;
+        q += need;
+      }
+    } else if (m == 0xC4) {                                                           // DHT, any number of tables
+      size_t q = 0;
+      while (q < sl) {
+        JPEG_REQUIRE(q + 17 <= sl, KVQ_ERR_SHAPE, "%s: Huffman table segment at byte %zu is cut short", who, at);
+        const int tc = s[q] >> 4, th = s[q] & 15;
+        int cnt = 0;
+        for (int i = 0; i < 16; ++i) cnt += s[q + 1 + i];
+        JPEG_REQUIRE(tc <= 1 && th <= 3 && cnt <= 256 && q + 17 + (size_t)cnt <= sl, KVQ_ERR_SHAPE,
+                     "%s: Huffman table segment at byte %zu is malformed", who, at);
+        JPEG_REQUIRE(huff_build(tc ? p.ac[th] : p.dc[th], s + q + 1, s + q + 17, cnt), KVQ_ERR_SHAPE,
+                     "%s: Huffman table %d/%d at byte %zu is not a prefix code", who, tc, th, at);
+        p.info.has_dht = 1;
+        q += 17 + (size_t)cnt;
+      }
+    } else if (m == 0xDD) {                                                           // DRI
+      JPEG_REQUIRE(sl >= 2, KVQ_ERR_SHAPE, "%s: restart interval segment at byte %zu is cut short", who, at);
+      p.info.restart_interval = (s[0] << 8) | s[1];
+    } else if (m == 0xEE) {                                                           // APP14
+      if (sl >= 12 && memcmp(s, "Adobe", 5) == 0 && s[11] == 0)
+        refuse(p, 4, "%s: Adobe APP14 segment with transform 0 (RGB or CMYK samples, no Y Cb Cr)", who);
+    } else if (m == 0xDA) {                                                           // SOS
+      JPEG_REQUIRE(have_sof, KVQ_ERR_SHAPE, "%s: scan at byte %zu before any frame header", who, at);
+      JPEG_REQUIRE(sl >= 1 && sl >= 4 + 2 * (size_t)s[0], KVQ_ERR_SHAPE, "%s: scan header at byte %zu is cut short", who, at);
+      const int ns = s[0];
+      if (ns != p.info.ncomp) refuse(p, 3, "%s: a scan of %d of the %d components (non-interleaved) is not decoded", who, ns, p.info.ncomp);
+      for (int c = 0; c < ns && c < p.info.ncomp; ++c) {
+        if (s[1 + 2 * c] != p.comp[c].id) refuse(p, 3, "%s: scan components are not in frame-header order", who);
+        p.comp[c].td = s[2 + 2 * c] >> 4; p.comp[c].ta = s[2 + 2 * c] & 15;
+        JPEG_REQUIRE(p.comp[c].td <= 3 && p.comp[c].ta <= 3, KVQ_ERR_SHAPE, "%s: scan header at byte %zu names Huffman table %d/%d", who, at,
+                     p.comp[c].td, p.comp[c].ta);
+      }
+      p.scan = pos;
+      break;
+    }                                                                                 // APPn, COM and everything else: skipped
+  }
+  // the image's length: entropy-coded data, then whatever segments and further scans follow, up to EOI
+  size_t e = skip_scan(d, n, pos);
+  while (e < n) {
+    int m = 0;
+    if (!read_marker(d, n, e, m)) break;
+    if (m == 0xD9) { p.info.frame_bytes = (int64_t)e; break; }
+    if (e + 2 > n) break;
+    const size_t L = ((size_t)d[e] << 8) | d[e + 1];
+    if (L < 2 || e + L > n) break;
+    e += L;
+    if (m == 0xDA) e = skip_scan(d, n, e);
+  }
+  if (p.why_rank) {
+    kvq::set_error("%s", p.why);
+    return KVQ_ERR_UNSUPPORTED;
+  }
+  p.info.supported = 1;
+  return KVQ_OK;
+}
+
+// the scan's bits, most significant first; a marker or the end of the buffer ends the supply, and asking for more is an error
+struct Bits {
+  const uint8_t* d;
+  size_t pos, n;
+  uint64_t acc;
+  int nbits;
+  void fill() {
+    while (nbits <= 56 && pos < n) {
+      const uint8_t b = d[pos];
+      if (b == 0xFF) {
+        if (pos + 1 >= n || d[pos + 1] != 0x00) return;      // a marker (or the cut): stay in front of it
+        pos += 2;
+      } else {
+        ++pos;
+      }
+      acc = (acc << 8) | b;
+      nbits += 8;
+    }
+  }
+  // the next 16 bits, zero-padded where the supply has ended
+  uint32_t peek16() {
+    if (nbits < 16) fill();
+    return nbits >= 16 ? (uint32_t)(acc >> (nbits - 16)) & 0xFFFFu : (uint32_t)(acc << (16 - nbits)) & 0xFFFFu;
+  }
+  bool take(int k, uint32_t& out) {                           // k in 0..16
+    if (nbits < k) fill();
+    if (nbits < k) return false;
+    out = k ? (uint32_t)(acc >> (nbits - k)) & ((1u << k) - 1u) : 0u;
+    nbits -= k;
+    return true;
+  }
+};
+
+enum { SYM_TRUNCATED = -1, SYM_BAD_CODE = -2 };
+
+int decode_symbol(Bits& b, const Huff& h) {
+  const uint32_t w = b.peek16();
+  const uint16_t e = h.look[w >> 7];
+  int len = e >> 8, sym = e & 255;
+  if (!len) {
+    for (len = 10; len <= 16; ++len) {
+      const int32_t code = (int32_t)(w >> (16 - len));
+      if (code <= h.maxcode[len] && code >= h.mincode[len]) { sym = h.vals[h.valptr[len] + code - h.mincode[len]]; break; }
+    }
+    if (len > 16) return b.nbits < 16 ? SYM_TRUNCATED : SYM_BAD_CODE;
+  }
+  if (len > b.nbits) return SYM_TRUNCATED;
+  b.nbits -= len;
+  return sym;
+}
+
+inline int32_t extend(uint32_t v, int s) { return v < (1u << (s - 1)) ? (int32_t)v - (1 << s) + 1 : (int32_t)v; }
+
+// one block into blk[64] (zeroed by the caller), natural order.  0, or the error text's cause
+const char* decode_block(Bits& b, const Huff& dc, const Huff& ac, int32_t& pred, int16_t* blk) {
+  int t = decode_symbol(b, dc);
+  if (t == SYM_TRUNCATED) return "the entropy-coded data is truncated";
+  if (t == SYM_BAD_CODE) return "a code that is in no Huffman table";
+  if (t > 15) return "a DC difference of more than 15 bits";
+  uint32_t v = 0;
+  if (!b.take(t, v)) return "the entropy-coded data is truncated";
+  pred = (int16_t)(pred + (t ? extend(v, t) : 0));           // kept to 16 bits, as it is stored
+  blk[0] = (int16_t)pred;
+  int k = 1;
+  while (k < 64) {
+    const int rs = decode_symbol(b, ac);
+    if (rs == SYM_TRUNCATED) return "the entropy-coded data is truncated";
+    if (rs == SYM_BAD_CODE) return "a code that is in no Huffman table";
+    const int r = rs >> 4, s = rs & 15;
+    if (s == 0) {
+      if (r != 15) break;                                     // EOB
+      k += 16;                                                // ZRL
+      if (k > 64) return "a zero run past coefficient 63";
+      continue;
+    }
+    k += r;
+    if (k > 63) return "a zero run past coefficient 63";
+    if (!b.take(s, v)) return "the entropy-coded data is truncated";
+    blk[ZIGZAG[k]] = (int16_t)extend(v, s);
+    ++k;
+  }
+  return nullptr;
+}
+
+// between restart intervals and at the end: drop the padding bits, then the marker `want` must stand at the read position
+bool expect_marker(Bits& b, int want, int& got) {
+  b.acc = 0; b.nbits = 0;
+  got = -1;
+  size_t pos = b.pos;
+  if (!read_marker(b.d, b.n, pos, got)) { got = -1; return false; }
+  if (got != want) return false;
+  b.pos = pos;
+  return true;
+}
+
+}  // namespace
+
+extern "C" size_t kvq_jpeg_coef_bytes(int H, int W) {
+  if (!kvq::jpeg_size_ok(H, W)) return 0;
+  return (size_t)kvq::jpeg_geom(H, W).blocks * 64 * sizeof(int16_t);
+}
+
+extern "C" int kvq_jpeg_probe(const uint8_t* data, size_t n, KvqJpegInfo* info) {
+  JPEG_REQUIRE(data && info, KVQ_ERR_NULL, "kvq_jpeg_probe: NULL pointer");
+  static thread_local Parsed p;
+  const int rc = parse(data, n, p, "kvq_jpeg_probe");
+  *info = p.info;
+  return rc;
+}
+
+extern "C" int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out, size_t coef_cap, uint16_t* qt_out) {
+  using namespace kvq;
+  JPEG_REQUIRE(data && coef_out && qt_out, KVQ_ERR_NULL, "kvq_jpeg_coeffs: NULL pointer");
+  static thread_local Parsed p;
+  static thread_local Huff std_tab[4];                       // Annex K: DC lum, DC chroma, AC lum, AC chroma
+  if (const int rc = parse(data, n, p, "kvq_jpeg_coeffs")) return rc;
+  const int H = p.info.height, W = p.info.width;
+  JPEG_REQUIRE(jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: frame of %d x %d", W, H);
+  const JpegGeom g = jpeg_geom(H, W);
+  const size_t bytes = (size_t)g.blocks * 64 * sizeof(int16_t);
+  JPEG_REQUIRE(coef_cap >= bytes, KVQ_ERR_WORKSPACE, "kvq_jpeg_coeffs: coef_out holds %zu bytes, a %d x %d frame needs %zu", coef_cap, W, H, bytes);
+  const Huff* dc[3];
+  const Huff* ac[3];
+  if (!p.info.has_dht) {
+    if (!std_tab[0].present) {
+      huff_build(std_tab[0], STD_DC_LUM_BITS, STD_DC_VALS, 12);
+      huff_build(std_tab[1], STD_DC_CHR_BITS, STD_DC_VALS, 12);
+      huff_build(std_tab[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS, 162);
+      huff_build(std_tab[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS, 162);
+    }
+  }
+  for (int c = 0; c < 3; ++c) {
+    JPEG_REQUIRE(p.qt_present[p.comp[c].tq], KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: quantiser table %d of component %d is not defined", p.comp[c].tq, c);
+    if (p.info.has_dht) {
+      dc[c] = &p.dc[p.comp[c].td]; ac[c] = &p.ac[p.comp[c].ta];
+      JPEG_REQUIRE(dc[c]->present && ac[c]->present, KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: Huffman table %d/%d of component %d is not defined",
+                   p.comp[c].td, p.comp[c].ta, c);
+    } else {                                                  // no DHT at all: table 0 = luminance, any other = chrominance
+      dc[c] = &std_tab[p.comp[c].td ? 1 : 0]; ac[c] = &std_tab[p.comp[c].ta ? 3 : 2];
+    }
+    for (int i = 0; i < 64; ++i) qt_out[64 * c + i] = p.qt[p.comp[c].tq][i];
+  }
+  memset(coef_out, 0, bytes);
+  int16_t* plane[3] = {coef_out, coef_out + (size_t)g.ny * 64, coef_out + (size_t)(g.ny + g.nc) * 64};
+  Bits b{data, p.scan, n, 0, 0};
+  int32_t pred[3] = {0, 0, 0};
+  const int ri = p.info.restart_interval;
+  int mcu = 0, got = 0;
+  for (int y = 0; y < g.my; ++y)
+    for (int x = 0; x < g.mx; ++x, ++mcu) {
+      if (ri && mcu && mcu % ri == 0) {
+        const int want = 0xD0 + ((mcu / ri - 1) & 7);
+        if (!expect_marker(b, want, got)) {
+          if (got < 0) set_error("kvq_jpeg_coeffs: missing RST%d before MCU %d (the stream is truncated or has no marker there)", want - 0xD0, mcu);
+          else set_error("kvq_jpeg_coeffs: wrong restart marker FF%02X before MCU %d, expected RST%d", got, mcu, want - 0xD0);
+          return KVQ_ERR_SHAPE;
+        }
+        pred[0] = pred[1] = pred[2] = 0;
+      }
+      for (int k = 0; k < 6; ++k) {
+        const int c = k < 4 ? 0 : k - 3;
+        const size_t blk = c == 0 ? (size_t)(2 * y + (k >> 1)) * (2 * g.mx) + 2 * x + (k & 1) : (size_t)y * g.mx + x;
+        if (const char* why = decode_block(b, *dc[c], *ac[c], pred[c], plane[c] + blk * 64)) {
+          set_error("kvq_jpeg_coeffs: %s (MCU %d of %d, block %d)", why, mcu, g.nc, k);
+          return KVQ_ERR_SHAPE;
+        }
+      }
+    }
+  if (!expect_marker(b, 0xD9, got)) {
+    if (got < 0) set_error("kvq_jpeg_coeffs: missing EOI after the last MCU (the stream is truncated)");
+    else set_error("kvq_jpeg_coeffs: marker FF%02X after the last MCU where EOI belongs", got);
+    return KVQ_ERR_SHAPE;
+  }
+  return KVQ_OK;
+}
+
+extern "C" int kvq_jpeg_idct_i420_host(const int16_t* coef, const uint16_t* qt, int T, int H, int W, uint8_t* frames_out) {
+  using namespace kvq;
+  JPEG_REQUIRE(coef && qt && frames_out, KVQ_ERR_NULL, "kvq_jpeg_idct_i420_host: NULL pointer");
+  JPEG_REQUIRE(T > 0 && T < 65536 && jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_idct_i420_host: %d frames of %dx%d", T, H, W);
+  const JpegGeom g = jpeg_geom(H, W);
+  const int ch = (H + 1) >> 1, cw = (W + 1) >> 1;
+  const size_t frame = (size_t)H * W + 2 * (size_t)ch * cw;
+  for (int t = 0; t < T; ++t) {
+    const int16_t* cf = coef + (size_t)t * g.blocks * 64;
+    for (int b = 0; b < g.blocks; ++b) {
+      const int c = b < g.ny ? 0 : (b < g.ny + g.nc ? 1 : 2);
+      const int id = c == 0 ? b : b - g.ny - (c - 1) * g.nc;
+      const int bpr = c == 0 ? 2 * g.mx : g.mx, ph = c == 0 ? H : ch, pw = c == 0 ? W : cw;
+      const int by = id / bpr, bx = id - by * bpr;
+      if (8 * by >= ph || 8 * bx >= pw) continue;            // a block that lies wholly in the MCU padding
+      const uint16_t* q = qt + ((size_t)t * 3 + c) * 64;
+      int32_t ws[8][8], v[8];
+      for (int u = 0; u < 8; ++u) {
+        for (int r = 0; r < 8; ++r) v[r] = jw_mul(cf[(size_t)b * 64 + 8 * r + u], q[8 * r + u]);
+        jpeg_idct_pass1(v);
+        for (int r = 0; r < 8; ++r) ws[r][u] = v[r];
+      }
+      uint8_t* out = frames_out + (size_t)t * frame + (c == 0 ? 0 : (size_t)H * W + (size_t)(c - 1) * ch * cw);
+      for (int r = 0; r < 8 && 8 * by + r < ph; ++r) {
+        for (int u = 0; u < 8; ++u) v[u] = ws[r][u];
+        jpeg_idct_pass2(v);
+        for (int u = 0; u < 8 && 8 * bx + u < pw; ++u) out[(size_t)(8 * by + r) * pw + 8 * bx + u] = (uint8_t)v[u];
+      }
+    }
+  }
+  return KVQ_OK;
+}

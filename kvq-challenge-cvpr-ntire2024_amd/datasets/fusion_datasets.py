@@ -417,14 +417,205 @@ class Y4mFrameReader:
             out[j] = self.payload[int(i)]
 
 
+class MjpegFrameReader:
+    """Motion-JPEG video as a frame reader — no codec library.  Every frame is one baseline 4:2:0 JPEG image (what
+    ``kvq_jpeg_probe`` accepts: include/kvq_hip.h); MJPEG is intra-only, so only the frames a sampler picks are ever decoded.
+    Three containers, indexed once as (offset, length) over a memory map:
+      ``*.mjpeg`` / ``*.mjpg``  concatenated images, found by walking each image's segments to its EOI (an ``FF D8`` inside an APPn
+                                payload is not a frame start)
+      ``*.avi``                 RIFF AVI whose video stream's handler or compression is ``MJPG``: W, H and the rate from ``hdrl``,
+                                the ``##dc`` / ``##db`` chunks of ``movi`` through ``idx1`` when present; a zero-length chunk repeats
+                                the previous frame; OpenDML files that continue past the first RIFF chunk are refused
+      a directory               its ``*.jpg`` / ``*.jpeg`` files in natural sort order (``2.jpg`` before ``10.jpg``); ``fps`` is None
+    Every frame must be decodable and of the first frame's size: one that is not is a ValueError naming the file, the frame and the
+    library's message.  JFIF fixes BT.601 full range, so ``format`` is ``SRC_I420_BT601_FULL`` and no ``yuv_matrix`` applies.
+
+    ``len(reader)`` frames; ``reader[i]`` -> uint8 RGB (H, W, 3) on the host (entropy decode, the scalar twin of the IDCT launch,
+    ``yuv420_to_rgb_host``); ``read_jpeg_into(indices, coef_out, qt_out)`` -> the quantised coefficients and quantiser tables
+    ``kernels.jpeg_idct_i420`` takes.  ``H``, ``W``, ``fps``, ``format``, ``frame_bytes`` as ``Y4mFrameReader``."""
+
+    def __init__(self, path):
+        from .._abi import SRC_I420_BT601_FULL
+        self.path, self.fps, self.format = path, None, SRC_I420_BT601_FULL
+        if os.path.isdir(path):
+            import re
+            names = [f for f in os.listdir(path) if f.lower().endswith((".jpg", ".jpeg"))]
+            names.sort(key=lambda f: [int(t) if t.isdigit() else t.lower() for t in re.split(r"(\d+)", f)])
+            if not names:
+                raise ValueError(f"{path}: frame 0: the directory holds no *.jpg / *.jpeg file")
+            self._index = [(os.path.join(path, f), 0, os.path.getsize(os.path.join(path, f))) for f in names]
+        elif path.lower().endswith(".avi"):
+            hdr = _avi_index(path)
+            if not hdr["mjpeg"]:
+                raise ValueError(f"{path}: the video stream is {hdr['handler']!r} / {hdr['compression']!r}, not MJPG")
+            self._index = [(path, o, n) for o, n in hdr["frames"]]
+            self.fps = hdr["fps"]
+            if not self._index:
+                raise ValueError(f"{path}: frame 0: the AVI file holds no video chunk")
+        else:
+            self._index, size, pos = [], os.path.getsize(path), 0
+            if size == 0:
+                raise ValueError(f"{path}: frame 0: the file is empty")
+            while pos < size:
+                rc, info, msg = kernels.jpeg_probe(self._bytes(path, pos, size - pos))
+                if rc == -2 or info.frame_bytes == 0:
+                    raise ValueError(f"{path}: frame {len(self._index)} (at byte {pos}): " + (msg or "the image has no EOI marker: the stream is truncated"))
+                self._index.append((path, pos, int(info.frame_bytes)))
+                pos += int(info.frame_bytes)
+        self.H = self.W = None
+        for i in range(len(self._index)):
+            if self._index[i][2] == 0:
+                raise ValueError(f"{self._index[i][0]}: frame {i}: the file is empty")
+            rc, info, msg = kernels.jpeg_probe(self._frame(i))
+            if rc == 0 and info.frame_bytes == 0:
+                rc, msg = -2, "the image has no EOI marker: the frame is truncated"
+            if rc == 0 and self.H is not None and (info.height, info.width) != (self.H, self.W):
+                rc, msg = -2, f"a frame of {info.width} x {info.height} in a video of {self.W} x {self.H}"
+            if rc:
+                raise ValueError(f"{self._index[i][0]}: frame {i}: {msg}")
+            if self.H is None:
+                self.H, self.W = int(info.height), int(info.width)
+        self.frame_bytes = kernels.i420_frame_bytes(self.H, self.W)
+        self.coef_bytes = kernels.jpeg_coef_bytes(self.H, self.W)
+        self._coeffs = None
+
+    @staticmethod
+    def _bytes(file, off, n):
+        """n bytes of ``file`` from ``off`` as a read-only mapped uint8 array (a mapping of its own: safe from any thread)"""
+        return np.memmap(file, dtype=np.uint8, mode="r", offset=off, shape=(n,))
+
+    def _frame(self, i):
+        return self._bytes(*self._index[int(i)])
+
+    def __len__(self):
+        return len(self._index)
+
+    def read_jpeg_into(self, indices, coef_out, qt_out):
+        """entropy-decode frames[indices] -> coef_out int16 (n, coef_bytes / 2), qt_out uint16 (n, 3, 64): host numpy views (pinned
+        staging); the library call releases the GIL"""
+        for j, i in enumerate(indices):
+            file, off, n = self._index[int(i)]
+            rc, msg = kernels.jpeg_coeffs(self._bytes(file, off, n), coef_out[j], qt_out[j])
+            if rc:
+                raise ValueError(f"{file}: frame {int(i)}: {msg}")
+
+    def i420(self, i):
+        """frame i as its I420 bytes (frame_bytes,), decoded on the host"""
+        coef, qt = np.empty((1, self.coef_bytes // 2), np.int16), np.empty((1, 3, 64), np.uint16)
+        self.read_jpeg_into([i], coef, qt)
+        return kernels.jpeg_idct_i420_host(coef, qt, self.H, self.W)[0]
+
+    def __getitem__(self, i):
+        if self._coeffs is None:
+            self._coeffs = kernels.yuv420_coeffs(self.format)
+        H, W = self.H, self.W
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        p = self.i420(i)
+        return yuv420_to_rgb_host(p[:H * W].reshape(H, W), p[H * W:H * W + ch * cw].reshape(ch, cw), p[H * W + ch * cw:].reshape(ch, cw),
+                                  self._coeffs)
+
+
+def _avi_index(path, frames=True):
+    """The first RIFF chunk of an AVI file -> dict(mjpeg, handler, compression, W, H, fps, frames [(offset, length)]) for its first
+    video stream.  ``frames`` is filled for an MJPG stream only (from ``idx1`` when present, else by walking ``movi``)."""
+    import struct
+    mm = np.memmap(path, dtype=np.uint8, mode="r")
+    size = mm.shape[0]
+    u32 = lambda o: int.from_bytes(bytes(mm[o:o + 4]), "little")     # noqa: E731
+    tag = lambda o: bytes(mm[o:o + 4])                               # noqa: E731
+    if size < 12 or tag(0) != b"RIFF" or tag(8) != b"AVI ":
+        raise ValueError(f"{path}: not a RIFF AVI file")
+    end = min(size, 8 + u32(4))
+    out = dict(mjpeg=False, handler=b"", compression=b"", W=0, H=0, fps=None, frames=[])
+    stream, n_strl, movi, idx1 = None, 0, None, None
+
+    def walk(lo, hi, depth):
+        nonlocal stream, n_strl, movi, idx1
+        o = lo
+        while o + 8 <= hi:
+            cid, n = tag(o), u32(o + 4)
+            body = o + 8
+            if cid == b"LIST" and body + 4 <= hi:
+                kind = tag(body)
+                if kind == b"movi":
+                    movi = (body, min(hi, body + n))
+                elif kind in (b"hdrl", b"strl"):
+                    walk(body + 4, min(hi, body + n), depth + 1)
+                    n_strl += kind == b"strl"
+            elif cid == b"strh" and stream is None and tag(body) == b"vids" and n >= 32:
+                stream = n_strl
+                out["handler"] = tag(body + 4)
+                scale, rate = u32(body + 20), u32(body + 24)
+                out["fps"] = rate / scale if rate and scale else None
+            elif cid == b"strf" and stream == n_strl and not out["W"] and n >= 20:
+                out["W"], out["H"] = u32(body + 4), abs(struct.unpack("<i", bytes(mm[body + 8:body + 12]))[0])
+                out["compression"] = tag(body + 16)
+            elif cid == b"idx1":
+                idx1 = (body, min(hi, body + n))
+            o = body + n + (n & 1)
+
+    walk(12, end, 0)
+    out["mjpeg"] = stream is not None and b"MJPG" in (out["handler"].upper(), out["compression"].upper())
+    if not out["mjpeg"] or not frames:
+        return out
+    if end + 12 <= size and tag(end) == b"RIFF" and tag(end + 8) == b"AVIX":
+        raise ValueError(f"{path}: an OpenDML AVI that continues past its first RIFF chunk (AVIX) is not read")
+    if movi is None:
+        raise ValueError(f"{path}: frame 0: the AVI file has no movi list")
+    ids = (b"%02ddc" % stream, b"%02ddb" % stream)
+    chunks = []                                                       # (offset of the data, length)
+    if idx1 is not None:
+        ent = np.frombuffer(bytes(mm[idx1[0]:idx1[0] + (idx1[1] - idx1[0]) // 16 * 16]), dtype="<u4").reshape(-1, 4)
+        base = None
+        for cid_u, _, off, n in ent.tolist():
+            cid = cid_u.to_bytes(4, "little")
+            if cid not in ids:
+                continue
+            if base is None:                                          # offsets count from the 'movi' tag, or in some files from byte 0
+                base = movi[0] if movi[0] + off + 8 <= size and tag(movi[0] + off) == cid else 0
+            o = base + off
+            if o + 8 + n > size or tag(o) != cid:
+                raise ValueError(f"{path}: frame {len(chunks)}: the idx1 entry points outside the file or at no {cid.decode()} chunk")
+            chunks.append((o + 8, n))
+    else:
+        def movi_walk(lo, hi):
+            o = lo
+            while o + 8 <= hi:
+                cid, n = tag(o), u32(o + 4)
+                if cid == b"LIST":
+                    movi_walk(o + 12, min(hi, o + 8 + n))
+                elif cid in ids:
+                    if o + 8 + n > size:
+                        raise ValueError(f"{path}: frame {len(chunks)}: the chunk is cut short by the end of the file")
+                    chunks.append((o + 8, n))
+                o += 8 + n + (n & 1)
+        movi_walk(movi[0] + 4, movi[1])
+    for k, (o, n) in enumerate(chunks):
+        if n == 0:                                                    # a dropped frame: show the previous one again
+            if not out["frames"]:
+                raise ValueError(f"{path}: frame 0: a zero-length chunk with no frame before it")
+            out["frames"].append(out["frames"][-1])
+        else:
+            out["frames"].append((o, n))
+    return out
+
+
 def open_video(path, yuv_matrix="bt601"):
-    """Frame reader for ``path``: a ``*.y4m`` file by ``Y4mFrameReader`` (``yuv_matrix``: its conversion matrix); ``<path>`` itself or
+    """Frame reader for ``path``: a ``*.y4m`` file by ``Y4mFrameReader`` (``yuv_matrix``: its conversion matrix); Motion-JPEG — a
+    ``*.mjpeg`` / ``*.mjpg`` stream, an ``*.avi`` file whose video stream is ``MJPG``, a directory of ``*.jpg`` frames — by
+    ``MjpegFrameReader`` (``yuv_matrix`` does not apply: JFIF fixes BT.601 full range); ``<path>`` itself or
     ``<path>.npy`` as a frame stack (this build's decode-free entries), else
     decord.VideoReader (fusion_datasets.py:381-383), else — decord missing, or failing on this file: the reference wraps the decord
     branch in a bare ``try`` — the OpenCV fallback (:398-431, ``Cv2FrameReader``)."""
     import os
+    if os.path.isdir(path):                                                                        # a directory of frames, whatever its name
+        return MjpegFrameReader(path)
     if path.endswith(".y4m") and (os.path.exists(path) or not os.path.exists(path + ".npy")):      # a missing file with a decoded
         return Y4mFrameReader(path, yuv_matrix)                                                    # .npy beside its name: the stack
+    if path.lower().endswith((".mjpeg", ".mjpg")) and os.path.exists(path):
+        return MjpegFrameReader(path)
+    if path.lower().endswith(".avi") and os.path.isfile(path) and _avi_is_mjpeg(path):
+        return MjpegFrameReader(path)
     if path.endswith(".npy"):
         return NpyFrameReader(path)
     if os.path.exists(path + ".npy"):
@@ -440,7 +631,16 @@ def open_video(path, yuv_matrix="bt601"):
     except ImportError as e:
         raise ImportError(f"cannot read {path}: video decode needs decord or OpenCV (neither is part of this image: SURVEY.md §8 f2; "
                           f"decord: {type(decord_error).__name__}: {decord_error}) — or provide the decoded frames as a uint8 "
-                          f"[T,H,W,3] array in {path}.npy, or the video as an uncompressed .y4m file") from e
+                          f"[T,H,W,3] array in {path}.npy, or the video as an uncompressed .y4m file or as Motion-JPEG (.mjpeg, MJPG .avi, "
+                          f"a directory of .jpg frames)") from e
+
+
+def _avi_is_mjpeg(path):
+    """True: ``path`` is a RIFF AVI whose first video stream is MJPG; any other file goes the way it always went"""
+    try:
+        return bool(_avi_index(path, frames=False)["mjpeg"])
+    except (OSError, ValueError):
+        return False
 
 
 class _Staging:
@@ -468,8 +668,11 @@ def _frames_to_device(vr, uniq, device):
     """The sampled frames ``uniq`` of a reader -> ONE uint8 (n, H, W, 3) device tensor: gathered into pinned staging memory
     by a few host threads (numpy copies release the GIL), then a single asynchronous H2D copy on the current stream.
     A reader of I420 frames (``read_i420_into``: ``Y4mFrameReader``) stages its payload as it is — 1.5 B/pixel through the gather
-    and the copy instead of 3 — and the result is a ``kernels.I420Frames`` (n, frame_bytes)."""
+    and the copy instead of 3 — and the result is a ``kernels.I420Frames`` (n, frame_bytes).
+    A Motion-JPEG reader (``read_jpeg_into``: ``MjpegFrameReader``) goes through ``_jpeg_frames_to_device``."""
     global _COPY_POOL
+    if hasattr(vr, "read_jpeg_into"):
+        return _jpeg_frames_to_device(vr, uniq, device)
     i420 = hasattr(vr, "read_i420_into")
     if i420:
         first, read = None, vr.read_i420_into
@@ -504,6 +707,39 @@ def _frames_to_device(vr, uniq, device):
         ev.record(torch.cuda.current_stream(dev.device))
         st["ev"][k] = ev
     return kernels.I420Frames(dev, vr.H, vr.W, vr.format) if i420 else dev
+
+
+def _copy_pool():
+    global _COPY_POOL
+    if _COPY_POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+        _COPY_POOL = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix="kvq-copy")
+    return _COPY_POOL
+
+
+def _jpeg_frames_to_device(vr, uniq, device):
+    """The sampled frames of a Motion-JPEG reader -> ``kernels.I420Frames``: the host threads of the copy pool entropy-decode them
+    into pinned staging (quantised int16 coefficients, 3 B/pixel, then the quantiser tables; the library calls release the GIL), ONE
+    asynchronous H2D copy carries both, ONE ``jpeg_idct_i420`` launch on the current stream reconstructs the frames.  Without a
+    device the scalar twin of the launch runs instead (bit-equal)."""
+    n, cb = len(uniq), vr.coef_bytes
+    nbytes = n * (cb + 384)                              # cb is a multiple of 768: the tables start 16-byte aligned
+    st, k = _Staging.get(nbytes)
+    stage = st["buf"][k][:nbytes]
+    host = stage.numpy()
+    coef, qt = host[:n * cb].view(np.int16).reshape(n, cb // 2), host[n * cb:].view(np.uint16).reshape(n, 3, 64)
+    nt = max(1, min(_COPY_THREADS, n))
+    bounds = np.linspace(0, n, nt + 1).astype(int)
+    jobs = [_copy_pool().submit(vr.read_jpeg_into, uniq[a:b], coef[a:b], qt[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+    for j in jobs:
+        j.result()
+    if torch.device(device).type != "cuda":
+        return kernels.I420Frames(torch.from_numpy(kernels.jpeg_idct_i420_host(coef, qt, vr.H, vr.W)), vr.H, vr.W, vr.format)
+    dev = stage.to(device, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev.device))
+    st["ev"][k] = ev
+    return kernels.jpeg_idct_i420(dev[:n * cb].view(torch.int16).view(n, cb // 2), dev[n * cb:].view(torch.uint16).view(n, 3, 64), vr.H, vr.W)
 
 
 def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601"):

@@ -423,6 +423,55 @@ class I420Frames:
         return self._rgb
 
 
+def jpeg_coef_bytes(H: int, W: int) -> int:
+    """bytes of one frame's coefficient hand-over (``kvq_jpeg_coef_bytes``): 768 per 16 x 16 MCU"""
+    n = lib().kvq_jpeg_coef_bytes(int(H), int(W))
+    if n == 0:
+        raise ValueError(f"jpeg_coef_bytes: a frame of {W} x {H} is outside what the library decodes")
+    return n
+
+
+def jpeg_probe(buf):
+    """``kvq_jpeg_probe`` on a uint8 numpy array (host only) -> (status, ``_abi.KvqJpegInfo``, message)"""
+    info = _abi.KvqJpegInfo()
+    rc = lib().kvq_jpeg_probe(buf.ctypes.data, buf.size, C.byref(info))
+    return rc, info, (lib().kvq_last_error().decode("utf-8", "replace") if rc else "")
+
+
+def jpeg_coeffs(buf, coef_out, qt_out):
+    """``kvq_jpeg_coeffs`` (host only): the image in the uint8 numpy array ``buf`` -> ``coef_out`` int16 (jpeg_coef_bytes / 2,),
+    ``qt_out`` uint16 (3, 64), both numpy views of host memory.  Returns (status, message); the ctypes call releases the GIL."""
+    rc = lib().kvq_jpeg_coeffs(buf.ctypes.data, buf.size, coef_out.ctypes.data, coef_out.nbytes, qt_out.ctypes.data)
+    return rc, (lib().kvq_last_error().decode("utf-8", "replace") if rc else "")
+
+
+def jpeg_idct_i420_host(coef, qt, H: int, W: int):
+    """the scalar twin of ``jpeg_idct_i420`` on numpy arrays: coef int16 (T, jpeg_coef_bytes / 2), qt uint16 (T, 3, 64) -> uint8
+    (T, i420_frame_bytes)"""
+    import numpy as np
+    coef, qt = np.ascontiguousarray(coef, np.int16), np.ascontiguousarray(qt, np.uint16)
+    T = qt.reshape(-1, 3, 64).shape[0]
+    assert coef.size * 2 == T * jpeg_coef_bytes(H, W), (coef.shape, T, H, W)
+    out = np.empty((T, i420_frame_bytes(H, W)), np.uint8)
+    check(lib().kvq_jpeg_idct_i420_host(coef.ctypes.data, qt.ctypes.data, T, int(H), int(W), out.ctypes.data), "kvq_jpeg_idct_i420_host")
+    return out
+
+
+def jpeg_idct_i420(coef: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None) -> "I420Frames":
+    """Quantised JPEG coefficients -> ``I420Frames`` (BT.601 full range, what JFIF fixes), one launch (``kvq_jpeg_idct_i420``).
+    coef int16 (T, jpeg_coef_bytes / 2) in the hand-over layout of ``kvq_jpeg_coeffs``, qt uint16 (T, 3, 64), both on the device."""
+    _need_gpu(coef, qt)
+    T = qt.shape[0]
+    assert coef.dtype == torch.int16 and qt.dtype == torch.uint16 and coef.is_contiguous() and qt.is_contiguous()
+    assert tuple(qt.shape) == (T, 3, 64) and coef.numel() * 2 == T * jpeg_coef_bytes(H, W), (tuple(coef.shape), tuple(qt.shape), H, W)
+    if out is None:
+        out = torch.empty(T, i420_frame_bytes(H, W), dtype=torch.uint8, device=coef.device)
+    else:
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (T, i420_frame_bytes(H, W)) and out.is_contiguous() and out.device == coef.device
+    check(lib().kvq_jpeg_idct_i420(ptr(coef), ptr(qt), T, int(H), int(W), ptr(out), stream_of(coef)), "kvq_jpeg_idct_i420")
+    return I420Frames(out, H, W, _abi.SRC_I420_BT601_FULL)
+
+
 def _frame_format(v) -> int:
     """KvqSrcFormat of a frame tensor / ``I420Frames``"""
     return v.format if isinstance(v, I420Frames) else int(v.dtype == torch.uint8)
