@@ -188,6 +188,9 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
       s1 += d[e];
       sq = fmaf(d[e], d[e], sq);
     }
+    // the running sums are final for this k-step HERE: s1 is read only after the last k-step, and without the opaque copy the IR-level
+    // sinking defers its first 32 adds past the chunk refills, keeping those d values alive in scratch at C = 192
+    asm volatile("" : "+v"(s1), "+v"(sq));
     const u32x4 w = {E::pack2(d[0], d[1]), E::pack2(d[2], d[3]), E::pack2(d[4], d[5]), E::pack2(d[6], d[7])};
     const V8 bx = __builtin_bit_cast(V8, w);
     const unsigned char* wb = lds + ((s / KC) & 1) * CHUNK + (s % KC) * 1024 + lane * 16;

@@ -262,6 +262,34 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     return st;
   };
 
+  // A LayerNorm of the row in acc (scale rs_, shift nm_ = -mean rs_, affine gam / bet in LDS) as the B operands of the next GEMM,
+  // one whole fragment (8 values = accumulator registers 8t .. 8t+7 of tile i) at a time into bx.  The packed fragment goes through
+  // an opaque copy: without it the IR-level sinking moves the two fma and the pack of every value down to the first MFMA that
+  // reads it, while the 2 x C/4 gamma / beta LDS reads stay here — at C = 192 that is 192 registers of loaded vectors live at
+  // once, which the allocator spilled to scratch (44 dwords per lane written and read back once per token).
+  auto norm_to_bx = [&](float rs_, float nm_, const float* gam, const float* bet) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < CM; ++i)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        u32x4 w;
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) {
+          const int q = 2 * t + qq;
+          const f32x4 g = *reinterpret_cast<const f32x4*>(gam + 32 * i + 8 * q + 4 * h);
+          const f32x4 be = *reinterpret_cast<const f32x4*>(bet + 32 * i + 8 * q + 4 * h);
+          float y[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs_, nm_), g[e], be[e]);      // two fma per value: (x rstd - mean rstd) g + b
+          w[2 * qq] = E::pack2(y[0], y[1]);
+          w[2 * qq + 1] = E::pack2(y[2], y[3]);
+        }
+        asm volatile("" : "+v"(w));
+        bx[2 * i + t] = __builtin_bit_cast(V8, w);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  };
+
   // ---- proj: acc (= x) += Wp . attn^T ------------------------------------------------------------------------
   const unsigned char* st = nullptr;
 #pragma unroll
@@ -299,21 +327,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     asm volatile("" : "+v"(mean_n));   // an opaque copy: CSE with the variance pass would keep C/2 differences live (spills)
     const float nmr = -mean_n * rstd;
     // normalised row -> B operands of fc1 (k order = accumulator order, see tail_pack_kernel); x1 stays in acc
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(s_g2 + 32 * i + 8 * q + 4 * h);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(s_b2n + 32 * i + 8 * q + 4 * h);
-        float y[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rstd, nmr), g[e], be[e]);      // two fma per value: (x rstd - mean rstd) g + b
-        u32x4 w = __builtin_bit_cast(u32x4, bx[2 * i + (q >> 1)]);
-        w[2 * (q & 1)] = E::pack2(y[0], y[1]);
-        w[2 * (q & 1) + 1] = E::pack2(y[2], y[3]);
-        bx[2 * i + (q >> 1)] = __builtin_bit_cast(V8, w);
-        if (q & 1) __builtin_amdgcn_sched_barrier(0);
-      }
+    norm_to_bx(rstd, nmr, s_g2, s_b2n);
   }
   __builtin_amdgcn_sched_barrier(0);     // nothing of the MLP prologue (bias / fragment loads) is hoisted into norm2
   KVQ_STAMP(2);
@@ -428,21 +442,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     if (QKV) {
       // ---- the next block's q | k | v (swin_backbone.py:252-260 of block b + 1): its norm1 row becomes the B operand in registers (k order
       // = accumulator order, as norm2's), then one 32-channel panel = one head of q, k or v at a time from 3C / 32 more ring panels ----
-#pragma unroll
-      for (int i = 0; i < CM; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + C + 32 * i + 8 * q + 4 * h);
-          float y[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs, nmr2), g[e], be[e]);
-          u32x4 w = __builtin_bit_cast(u32x4, bx[2 * i + (q >> 1)]);
-          w[2 * (q & 1)] = E::pack2(y[0], y[1]);
-          w[2 * (q & 1) + 1] = E::pack2(y[2], y[3]);
-          bx[2 * i + (q >> 1)] = __builtin_bit_cast(V8, w);
-          if (q & 1) __builtin_amdgcn_sched_barrier(0);
-        }
+      norm_to_bx(rs, nmr2, s_nn, s_nn + C);
       __builtin_amdgcn_sched_barrier(0);
       const int nH = C / 32;
 #pragma unroll 1
