@@ -1015,6 +1015,48 @@ int kvq_pool_nd_strided(const uint16_t* x, int dtype, const int32_t dims5[5], co
 int kvq_mean_std_pool(const uint16_t* x, int dtype, int rows, int HW, int C, float* out, int64_t out_stride,
                       int mean_off, int std_off, void* stream);
 
+/* ---- VQAHead training step on features of a frozen trunk (csrc/headtrain.hip): the reference's train-mode head
+ * (head.py:60-68), plcc_loss / rank_loss (trainer.py:337-354), the gradients of the four head parameters, torch's AdamW and the EMA copy
+ * (trainer.py:163-172).  All fp32 (fp32 MFMA, fp32 sums), no atomics: two runs are bit-equal.
+ *
+ *   feat     channels-last fp32 [B][L][C], dense, 16-byte aligned
+ *   params   one flat fp32 vector, 16-byte aligned: W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]  (hidden * C + 2 hidden + 1
+ *            floats); grads, exp_avg, exp_avg_sq and ema have the same layout
+ *   p_drop   probability of both dropouts (head.py:63, :65), 0 <= p < 1.  The mask of element idx of dropout `which` (0: the features, idx
+ *            in [b][l][c] order; 1: the GELU output, idx in [b][l][hidden] order) at (seed, step) is the counter-based hash of
+ *            csrc/headtrain.hpp; kept values are multiplied by 1 / (1 - p); p == 0 is the identity.  No mask tensor is stored.
+ *   score    forward: out [B], the train-mode scores;  dscore: backward: in [B], d loss / d score;  grads: backward: out
+ *
+ * Shapes: hidden == 64, C a multiple of 64, p_drop in [0, 1), 16-byte alignment: otherwise KVQ_ERR_UNSUPPORTED.  B >= 2, L >= 1,
+ * B * L * C < 2^32: otherwise KVQ_ERR_SHAPE.  A workspace below kvq_headtrain_workspace_bytes(B, L, C, hidden) (0 for a shape that is
+ * not built): KVQ_ERR_WORKSPACE.  NULL: KVQ_ERR_NULL.  All of it is checked on the host before the first launch.  The forward leaves the
+ * pre-activations in the workspace; the backward of the same (seed, step, p_drop) reads them, so the two calls share one workspace. */
+typedef struct KvqHeadTrainArgs {
+  const float* feat;
+  int32_t B, L, C, hidden;
+  const float* params;
+  float p_drop;
+  uint32_t seed, step;
+  void* workspace;
+  size_t workspace_bytes;
+  float* score;
+  const float* dscore;
+  float* grads;
+} KvqHeadTrainArgs;
+size_t kvq_headtrain_workspace_bytes(int B, int L, int C, int hidden);
+int kvq_headtrain_forward(const KvqHeadTrainArgs* host_args, void* stream);
+int kvq_headtrain_backward(const KvqHeadTrainArgs* host_args, void* stream);
+/* out[i] = 1 if element i of dropout `which` (0 | 1) is kept at (seed, step) under probability p, else 0; 1 <= n <= 2^32 */
+int kvq_headtrain_mask(uint32_t seed, uint32_t step, int which, float p, int64_t n, uint8_t* out, void* stream);
+/* One launch: out3 = {plcc + rank_weight * rank, plcc, rank} and dscore [B] = d out3[0] / d score, the gradient through the rank loss's
+ * 1 + max included.  2 <= B <= 1024 or KVQ_ERR_SHAPE.  Ties of the maximum and scores on the relu kink: deterministic, the first in
+ * row-major order carries the maximum and a zero difference has zero gradient. */
+int kvq_headtrain_loss(const float* score, const float* label, int B, float rank_weight, float* out3, float* dscore, void* stream);
+/* torch.optim.AdamW (betas 0.9 / 0.999, eps 1e-8, decoupled decay p *= 1 - lr * wd on every element) on n elements, optimiser step
+ * `step` >= 1 (bias corrections computed on the host in double), then ema = 0.999 ema + 0.001 params unless ema is NULL. */
+int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float wd,
+                        int step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,12 @@ class KvqJpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("supported", C.c_int32), ("has_dht", C.c_int32), ("frame_bytes", C.c_int64)]
 
 
+class KvqHeadTrainArgs(C.Structure):
+    _fields_ = [("feat", p_void), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32), ("params", p_void),
+                ("p_drop", C.c_float), ("seed", C.c_uint32), ("step", C.c_uint32), ("workspace", p_void), ("workspace_bytes", C.c_size_t),
+                ("score", p_void), ("dscore", p_void), ("grads", p_void)]
+
+
 class KvqProfRecord(C.Structure):
     _fields_ = [("kind", C.c_int32), ("variant", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -309,6 +315,12 @@ SYMBOLS = {
     "kvq_fragment_gather_batch": (i32, [C.POINTER(KvqFragmentSource), i32, i32, p_void, p_void]),
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),
+    "kvq_headtrain_workspace_bytes": (sz, [i32] * 4),
+    "kvq_headtrain_forward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
+    "kvq_headtrain_backward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
+    "kvq_headtrain_mask": (i32, [C.c_uint32, C.c_uint32, i32, f32, i64, p_void, p_void]),
+    "kvq_headtrain_loss": (i32, [p_void, p_void, i32, f32, p_void, p_void, p_void]),
+    "kvq_headtrain_adamw": (i32, [p_void, p_void, p_void, p_void, p_void, i64, f32, f32, i32, p_void]),
 }
 
 _lib: Optional[C.CDLL] = None

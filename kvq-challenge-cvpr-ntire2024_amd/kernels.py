@@ -1384,3 +1384,81 @@ def conv_stem_direct(x: torch.Tensor, w_kc: torch.Tensor, bias: torch.Tensor, ke
                                      C.byref(_i32x(kernel)), C.byref(_i32x(stride)), C.byref(_i32x(pad)), int(relu),
                                      dtype_code(out_dtype), ptr(out), current_stream()), "kvq_conv_stem_direct")
     return out
+
+
+# ---- VQAHead training step (csrc/headtrain.hip): thin wrappers; kvq_amd/finetune.py drives them ---------------------------------
+def headtrain_param_count(C_in: int, hidden: int = 64) -> int:
+    """length of the flat parameter vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]"""
+    return hidden * C_in + 2 * hidden + 1
+
+
+def headtrain_workspace(B: int, L: int, C_in: int, hidden: int = 64, device=None) -> torch.Tensor:
+    """the workspace the forward and the backward of one (B, L, C) share; raises for a shape that is not built"""
+    n = int(lib().kvq_headtrain_workspace_bytes(B, L, C_in, hidden))
+    if n == 0:
+        raise _abi.KvqError(f"kvq_headtrain: shape B={B} L={L} C={C_in} hidden={hidden} is not built "
+                            "(B >= 2, C a multiple of 64, hidden 64)")
+    return torch.empty(n // 4, dtype=torch.float32, device=device if device is not None else "cuda")
+
+
+def headtrain_mask(seed: int, step: int, which: int, p: float, n: int, device=None) -> torch.Tensor:
+    """uint8 [n]: 1 where element i of dropout ``which`` (0: features, 1: GELU output) is kept at (seed, step)"""
+    out = torch.empty(n, dtype=torch.uint8, device=device if device is not None else "cuda")
+    _need_gpu(out)
+    check(lib().kvq_headtrain_mask(seed & 0xFFFFFFFF, step & 0xFFFFFFFF, which, p, n, ptr(out), stream_of(out)), "kvq_headtrain_mask")
+    return out
+
+
+def _headtrain_args(feat, params, p, seed, step, ws, score=None, dscore=None, grads=None, hidden=64):
+    _need_gpu(feat, params, ws, score, dscore, grads)
+    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous(), "features: dense fp32 [B][L][C]"
+    B, L, Cc = feat.shape
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == headtrain_param_count(Cc, hidden)
+    a = _abi.KvqHeadTrainArgs()
+    a.feat, a.B, a.L, a.C, a.hidden, a.params = ptr(feat), B, L, Cc, hidden, ptr(params)
+    a.p_drop, a.seed, a.step = float(p), seed & 0xFFFFFFFF, step & 0xFFFFFFFF
+    a.workspace, a.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
+    a.score, a.dscore, a.grads = ptr(score), ptr(dscore), ptr(grads)
+    return a
+
+
+def headtrain_forward(feat, params, p, seed, step, ws, score=None):
+    """train-mode scores fp32 [B] of channels-last features [B][L][C] under the flat parameters; the pre-activations stay in ``ws``"""
+    if score is None:
+        score = torch.empty(feat.shape[0], dtype=torch.float32, device=feat.device)
+    a = _headtrain_args(feat, params, p, seed, step, ws, score=score)
+    check(lib().kvq_headtrain_forward(C.byref(a), stream_of(feat)), "kvq_headtrain_forward")
+    return score
+
+
+def headtrain_loss(score, label, rank_weight=0.0, out3=None, dscore=None):
+    """-> (out3 = [loss, plcc_loss, rank_loss], dscore [B]) of trainer.py:337-354, one launch"""
+    _need_gpu(score, label)
+    assert score.dtype == label.dtype == torch.float32 and score.is_contiguous() and label.is_contiguous()
+    B = score.numel()
+    assert label.numel() == B
+    out3 = torch.empty(3, dtype=torch.float32, device=score.device) if out3 is None else out3
+    dscore = torch.empty(B, dtype=torch.float32, device=score.device) if dscore is None else dscore
+    check(lib().kvq_headtrain_loss(ptr(score), ptr(label), B, float(rank_weight), ptr(out3), ptr(dscore), stream_of(score)),
+          "kvq_headtrain_loss")
+    return out3, dscore
+
+
+def headtrain_backward(feat, params, p, seed, step, ws, dscore, grads=None):
+    """the flat gradient (layout of ``params``) from ``dscore`` [B]; reads the pre-activations the forward of the same
+    (seed, step, p) left in ``ws``"""
+    if grads is None:
+        grads = torch.empty_like(params)
+    a = _headtrain_args(feat, params, p, seed, step, ws, dscore=dscore, grads=grads)
+    check(lib().kvq_headtrain_backward(C.byref(a), stream_of(feat)), "kvq_headtrain_backward")
+    return grads
+
+
+def headtrain_adamw(params, grads, exp_avg, exp_avg_sq, ema, lr, wd, step):
+    """torch.optim.AdamW's update of the flat vector in place (optimiser step ``step`` >= 1), then the EMA copy (``ema`` None: skipped)"""
+    _need_gpu(params, grads, exp_avg, exp_avg_sq, ema)
+    n = params.numel()
+    for t in (grads, exp_avg, exp_avg_sq) + (() if ema is None else (ema,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    check(lib().kvq_headtrain_adamw(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), ptr(ema), n, float(lr), float(wd), int(step),
+                                    stream_of(params)), "kvq_headtrain_adamw")

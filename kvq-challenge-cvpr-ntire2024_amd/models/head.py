@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's ``models/head.py`` (``VQAHead`` :33-68, ``simpleVQAHead``
 :10-31).  Parameter names/shapes are the reference's; forward calls libkvq_hip.so.
-Inference only: dropout is the identity (``model.eval()`` in ``trainer.py:257,303``)."""
+``forward`` is the eval-mode head: dropout is the identity (``model.eval()`` in ``trainer.py:257,303``).  The train-mode head
+(dropout on the features and behind the GELU), its losses and its optimiser step live in ``kvq_amd/finetune.py``
+(``HeadFinetuner``, csrc/headtrain.hip), which works on a ``VQAHead``'s parameters and writes the trained ones back into them."""
 from __future__ import annotations
 
 import torch

@@ -7,7 +7,8 @@ Differences that are deliberate:
   * one process per GPU (``torch.distributed.run``) instead of ``nn.DataParallel``: videos are sharded
     ``videos[rank::world]`` and ONE all-gather of the score vector runs at the end;
   * scores stay on the device until the end (no per-video ``.item()`` sync, ``trainer.py:329``).
-Training (optimizer, losses, EMA, checkpoints) is out of scope: this is an inference engine.
+Training: ``finetune_head()`` fits the ``VQAHead`` on features of the frozen trunk (kvq_amd/finetune.py: the reference's losses, AdamW,
+schedule, EMA and best-checkpoint rule); gradients into a backbone are out of scope.
 """
 from __future__ import annotations
 
@@ -465,6 +466,57 @@ class Trainer:
         if getattr(self.val_dataset, "labels", None) is not None and len(scores) > 2:
             self.inferece_val(scores)
         return scores
+
+    # ---- head fine-tuning on the frozen trunk (the reference's train.py / train_eval_all_epoches for the head's parameters) ----------
+    def finetune_head(self):
+        """The reference's yml schema: ``num_epochs``, ``l_num_epochs``, ``warmup_epochs``, ``batch_size`` (clips per batch), ``ema``,
+        ``save_model``, ``optimizer.{lr, wd, backbone_lr_mult}``, ``data.train`` (sampled deterministically, ``phase: test``) and
+        ``data.val``.  After every epoch the trained head and the EMA head are scored on ``data.val`` with the ``inferece_val``
+        metrics and kept by the rule of trainer.py:223-230 in ``{resume}/{name}_head_{test_set}_{n|s}_finetuned.pth``.
+        -> (best of the trained head, best of the EMA head), each (SRCC, PLCC, KRCC, RMSE)."""
+        from .finetune import HeadFinetuner
+        cfg, opt = self.config, self.config["optimizer"]
+        if opt.get("backbone_lr_mult", 0) != 0:
+            raise NotImplementedError(f"optimizer.backbone_lr_mult = {opt['backbone_lr_mult']}: this engine trains the head on a frozen "
+                                      "trunk; set it to 0")
+        if self.world > 1:
+            raise NotImplementedError("finetune_head() runs on one rank")
+        key = self.key_list[0]
+        tcfg = cfg["data"]["train"]
+        train_ds = getattr(_datasets, tcfg["type"])(dict(tcfg["args"], phase="test"), None, device=self.device)
+        use_ema = bool(cfg.get("ema", True))
+        ft = HeadFinetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=use_ema, seed=int(cfg.get("seed", 0)),
+                           rank_weight=float(cfg.get("rank_weight", 0.0)))
+        ft.cache_features(train_ds, self)
+        n = sum(f.shape[0] for f in ft.feats)
+        bs = int(cfg["batch_size"])
+        per_epoch = n // bs + (1 if n % bs >= 3 else 0)
+        ft.set_schedule(int(cfg["warmup_epochs"] * per_epoch), int((cfg["num_epochs"] + cfg["l_num_epochs"]) * per_epoch))
+        val = HeadFinetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=False)       # the cache of data.val's features
+        val.cache_features(self.val_dataset, self)
+        resume, test_set = getattr(self.args, "resume", "./checkpoint/"), getattr(self.args, "test_set", "val")
+        save = bool(cfg.get("save_model", True))
+        best = {"n": (-1, -1, -1, 1999), "s": (-1, -1, -1, 1999)}
+        for epoch in range(int(cfg["num_epochs"])):
+            log = ft.fit(1, bs)
+            if log:
+                print("train/total_loss", log[-1]["loss"], "train/plcc_loss", log[-1]["plcc_loss"], "lr", log[-1]["lr"])
+            for suffix in ("n", "s") if use_ema else ("n",):
+                scores = np.asarray([float(ft.predict(f, ema=suffix == "s").mean()) for f in val.feats])
+                s, p, k, r = self.inferece_val(scores)
+                bs_, bp, bk, br = best[suffix]
+                if s + p > bs_ + bp and save:
+                    ft.write_back(ema=suffix == "s")
+                    os.makedirs(resume, exist_ok=True)
+                    torch.save({"state_dict": {"module." + n_: v.detach().cpu() for n_, v in self.model.state_dict().items()},
+                                "validation_results": tuple(float(v) for v in best[suffix])},       # plain floats: a weights-only load reads it
+                               f"{resume}/{cfg['name']}_head_{test_set}_{suffix}_finetuned.pth")
+                best[suffix] = (max(bs_, s), max(bp, p), max(bk, k), min(br, r))
+                print({f"val_{suffix}/best_SRCC-{suffix}": best[suffix][0], f"val_{suffix}/best_PLCC-{suffix}": best[suffix][1],
+                       f"val_{suffix}/best_KRCC-{suffix}": best[suffix][2], f"val_{suffix}/best_RMSE-{suffix}": best[suffix][3]})
+        ft.write_back(ema=False)                 # the model ends with the trained head, as the reference's self.model does
+        self.finetuner = ft
+        return best["n"], best["s"]
 
     def rescale(self, pr, gt=None):
         pr = np.asarray(pr, np.float64)
