@@ -130,19 +130,159 @@ def test_cdm_modules_vs_reference_golden(golden, dtype):
         mods["sem"](torch.zeros(1, 768, 7, 7), torch.zeros(1, 768, 7, 7))
 
 
-@pytest.mark.parametrize("B,Lq,Lk,heads", [(4, 49, 49, 12), (3, 16, 16, 12), (2, 100, 7, 3), (1, 64, 2, 2), (2, 128, 130, 1), (1, 129, 320, 1)])
-def test_mha_cross_strided(B, Lq, Lk, heads):
+MHA_CROSS_SHAPES = [(4, 49, 49, 12), (3, 16, 16, 12), (2, 100, 7, 3), (1, 64, 2, 2), (2, 128, 130, 1), (1, 129, 320, 1),
+                    (1, 64, 320, 1),       # four key splits + the largest LDS request (K | V of 320 keys + three partial sets: 132 608 B)
+                    (2, 50, 3, 2),         # four key splits over three keys: one part is empty
+                    (1, 130, 9, 1)]        # just past the two-split form: a third query pass of two live rows
+
+
+def _mha_cross_strided(B, Lq, Lk, heads, dtype):
     g = torch.Generator().manual_seed(Lq * 100 + Lk)
     D = heads * 64
-    q = torch.randn(B * Lq, D, generator=g).to(torch.float16)
-    kv = torch.randn(B * Lk, 2 * D + 8, generator=g).to(torch.float16)       # k and v interleaved in one buffer: strided rows
+    q = torch.randn(B * Lq, D, generator=g).to(HALF[dtype])
+    kv = torch.randn(B * Lk, 2 * D + 8, generator=g).to(HALF[dtype])       # k and v interleaved in one buffer: strided rows
     kvd = kv.to(DEV)
     out = kernels.mha_cross(q.to(DEV), kvd[:, :D], kvd[:, D:2 * D], B, heads, 0.05).float().cpu()
     qh = q.float().reshape(B, Lq, heads, 64).transpose(1, 2)
     kh = kv[:, :D].float().reshape(B, Lk, heads, 64).transpose(1, 2)
     vh = kv[:, D:2 * D].float().reshape(B, Lk, heads, 64).transpose(1, 2)
     ref = (torch.softmax(qh @ kh.transpose(-1, -2) * 0.05, -1) @ vh).transpose(1, 2).reshape(B * Lq, D)
-    assert (out - ref).abs().max().item() <= 2.1 * 2.0 ** -11 * max(1.0, ref.abs().max().item())
+    assert (out - ref).abs().max().item() <= 2.1 * EPS[dtype] * max(1.0, ref.abs().max().item())
+
+
+@pytest.mark.parametrize("B,Lq,Lk,heads", MHA_CROSS_SHAPES)
+def test_mha_cross_strided(B, Lq, Lk, heads):
+    _mha_cross_strided(B, Lq, Lk, heads, "fp16")
+
+
+@pytest.mark.parametrize("B,Lq,Lk,heads", MHA_CROSS_SHAPES)
+def test_mha_cross_strided_bf16(B, Lq, Lk, heads):
+    _mha_cross_strided(B, Lq, Lk, heads, "bf16")
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("Lq", [64, 100])
+def test_mha_cross_softmax_extremes(Lq, dtype):
+    """A key that wins by about 90 in the logits and sits in the LAST 8-key chunk of the LAST wave's key split (Lq = 64: four
+    splits of 80 keys; Lq = 100: two of 160), every other logit about -60: the wave that merges the parts holds a running
+    maximum 90 below the winner's, so its own sum is scaled by exp(-90) and the part that holds the winner by 1.  Finite, and
+    the float64 softmax to the output's rounding."""
+    g = torch.Generator().manual_seed(900 + Lq)
+    Lk, win = 320, 317
+    q = (torch.randn(Lq, 64, generator=g) * 0.5).to(HALF[dtype])
+    k = (torch.randn(Lk, 64, generator=g) * 0.5).to(HALF[dtype])
+    v = torch.randn(Lk, 64, generator=g).to(HALF[dtype])
+    q[:, 0], k[:, 0] = 8.0, -7.5                                            # every logit 8 * -7.5 = -60 (+ ~N(0, 2))
+    k[win, 0] = 3.75                                                        # ... but this one: +30
+    logits = q.double() @ k.double().t()
+    top2 = logits.topk(2, dim=1).values
+    assert (logits.argmax(1) == win).all() and float((top2[:, 0] - top2[:, 1]).min()) > 75.0
+    ref = torch.softmax(logits, -1) @ v.double()
+    out = kernels.mha_cross(q.to(DEV), k.to(DEV), v.to(DEV), 1, 1, 1.0).float().cpu()
+    assert torch.isfinite(out).all()
+    err = (out.double() - ref).abs().max().item()
+    print(f"mha_cross extremes Lq={Lq} {dtype}: err {err:.3e} bound {2.1 * EPS[dtype] * max(1.0, ref.abs().max().item()):.3e}")
+    assert err <= 2.1 * EPS[dtype] * max(1.0, ref.abs().max().item())
+
+
+# ------------------------------------------------------------------ entry points that had no direct test
+def _err_and_bound(got, ref64, ref32):
+    """(max |got - ref|, bound): 8 x the error of the same expression evaluated by torch in fp32 on the CPU, floor 2^-22 max|ref| —
+    the rule of test_gpu_headtrain.py (the kernel sums in another order and uses __expf; 8 x keeps any 16-bit rounding out)"""
+    err = (got.double() - ref64).abs().max().item()
+    bound = max(8.0 * (ref32.double() - ref64).abs().max().item(), 2.0 ** -22 * ref64.abs().max().item())
+    return err, bound
+
+
+@pytest.mark.parametrize("C", [64, 768, 100])
+@pytest.mark.parametrize("M", [1, 98])
+def test_sem_modulate_vs_float64(M, C):
+    g = torch.Generator().manual_seed(M * 1000 + C)
+    x, inp = torch.randn(M, C, generator=g), torch.randn(M, C, generator=g) * 2.0
+    wg, wb = torch.randn(C, generator=g) / C ** 0.5, torch.randn(C, generator=g) / C ** 0.5
+    bg, bb = 0.3, -0.2
+    # gate logits of +30 and -30 (the sigmoid saturates) in the first and the last row, ordinary ones between
+    x[0] = x[0] + (30.0 - bg - float(wg @ x[0])) * wg / float(wg @ wg)
+    if M > 1:
+        x[-1] = x[-1] + (-30.0 - bg - float(wg @ x[-1])) * wg / float(wg @ wg)
+    out = kernels.sem_modulate(x.to(DEV), inp.to(DEV), wg.to(DEV), bg, wb.to(DEV), bb).cpu()
+    f = lambda x, inp, wg, wb: torch.sigmoid(x @ wg + bg)[:, None] * inp + (x @ wb + bb)[:, None]      # noqa: E731
+    ref64 = f(x.double(), inp.double(), wg.double(), wb.double())
+    assert abs(float(x[0].double() @ wg.double()) + bg - 30.0) < 1e-3
+    err, bound = _err_and_bound(out, ref64, f(x, inp, wg, wb))
+    print(f"sem_modulate M={M} C={C}: err {err:.3e} bound {bound:.3e}")
+    assert out.shape == (M, C) and err <= bound
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("C", [64, 768, 100])
+def test_dist_modulate_vs_float64(C, dtype):
+    g = torch.Generator().manual_seed(C)
+    B, rows = 2, 3
+    inp = torch.randn(B, rows, C, generator=g) * 2.0
+    gl, beta = (torch.randn(B, C, generator=g) * 2.0).to(HALF[dtype]), torch.randn(B, C, generator=g).to(HALF[dtype])
+    gl[0, 0], gl[0, 1], gl[1, C - 1], gl[1, C - 2] = 30.0, -30.0, 30.0, -30.0
+    out = kernels.dist_modulate(inp.to(DEV), gl.to(DEV), beta.to(DEV)).cpu()
+    f = lambda inp, gl, beta: torch.sigmoid(gl)[:, None] * inp + beta[:, None]      # noqa: E731
+    ref64 = f(inp.double(), gl.double(), beta.double())
+    err, bound = _err_and_bound(out, ref64, f(inp, gl.float(), beta.float()))
+    print(f"dist_modulate C={C} {dtype}: err {err:.3e} bound {bound:.3e}")
+    assert out.shape == (B, rows, C) and err <= bound
+
+
+@pytest.mark.parametrize("C", [64, 768, 100])
+@pytest.mark.parametrize("M", [1, 98])
+def test_axpby_vs_float64(M, C):
+    g = torch.Generator().manual_seed(M + C)
+    x, y = torch.randn(M, C, generator=g), torch.randn(M, C, generator=g) * 3.0
+    for a, b in ((0.2, 0.8), (0.5, -0.5)):
+        out = kernels.axpby(x.to(DEV), y.to(DEV), a, b).cpu()
+        a32, b32 = torch.tensor(a, dtype=torch.float32), torch.tensor(b, dtype=torch.float32)     # the kernel takes float arguments
+        ref64 = a32.double() * x.double() + b32.double() * y.double()
+        err, bound = _err_and_bound(out, ref64, a32 * x + b32 * y)
+        print(f"axpby M={M} C={C} a={a} b={b}: err {err:.3e} bound {bound:.3e}")
+        assert out.shape == (M, C) and err <= bound
+
+
+CONVERT_LENGTHS = list(range(1, 10)) + [1027]
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_to_half_and_to_float_bit_exact(dtype):
+    """``kvq_convert``: fp32 -> 16 bits is torch's round-to-nearest-even for finite values inside the type's range, at every tail
+    length of the four-per-thread kernel (n % 4 = 0..3, n < 4, several blocks); 16 bits -> fp32 is exact."""
+    g = torch.Generator().manual_seed(12)
+    for n in CONVERT_LENGTHS:
+        x = torch.randn(n, generator=g) * 10.0 ** torch.randint(-3, 4, (n,), generator=g).float()
+        x[0] = 1.0 + 2.0 ** -11 if dtype == "fp16" else 1.0 + 2.0 ** -8            # a tie: rounds to even
+        h = kernels.to_half(x.to(DEV), HALF[dtype])
+        assert h.dtype == HALF[dtype] and h.shape == x.shape
+        assert torch.equal(h.cpu().view(torch.int16), x.to(HALF[dtype]).view(torch.int16)), n
+        f = kernels.to_float(h)
+        assert f.dtype == torch.float32 and torch.equal(f.cpu(), x.to(HALF[dtype]).float()), n
+    x = torch.randn(3, 343, generator=g)                                          # shape is kept
+    assert kernels.to_half(x.to(DEV), HALF[dtype]).shape == (3, 343)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("D", [64, 2048, 100])
+def test_l2_normalize_rows_vs_float64(D, dtype):
+    """F.normalize(x, dim=1) in float64, every element within one 16-bit ulp (2 EPS |ref|); an all-zero row comes out as zeros
+    (the 1e-12 floor of the norm), not NaN.  |x| >= 0.25 keeps every quotient inside fp16's normal range (smallest: 0.25 / ~60)."""
+    g = torch.Generator().manual_seed(D)
+    M = 5
+    x = torch.randn(M, D, generator=g)
+    x = torch.sign(x) * (0.25 + x.abs())
+    x[1] *= 300.0
+    x[2] *= 1e-3
+    x[3] = 0.0
+    out = kernels.l2_normalize_rows(x.to(DEV), HALF[dtype]).float().cpu()
+    ref = x.double() / x.double().norm(dim=1, keepdim=True).clamp_min(1e-12)
+    assert out.shape == (M, D) and torch.isfinite(out).all() and bool((out[3] == 0).all())
+    excess = ((out.double() - ref).abs() - 2.0 * EPS[dtype] * ref.abs()).max().item()
+    print(f"l2_normalize_rows D={D} {dtype}: max rel err {((out.double() - ref).abs() / ref.abs().clamp_min(1e-30)).max().item():.3e} "
+          f"(bound {2.0 * EPS[dtype]:.3e})")
+    assert excess <= 0.0
 
 
 def test_keyframes_and_qrs_vs_reference_golden(golden):
