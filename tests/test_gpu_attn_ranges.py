@@ -61,6 +61,19 @@ def to_order(t, order, BW, N):
     return torch.stack([t[b].index_select(-2, idx[b]) for b in range(BW)])
 
 
+def ranges_operands(dims, window, lay, nH, half):
+    """(q2, k, v [BW, nH, N, 32] rounded to ``half``, in raster order; rpb, fpb) of one clip (BW = nW), q scaled by 0.6 log2(e)"""
+    g = np.random.Generator(np.random.PCG64(sum(dims) + sum(window) + 300))
+    N, BW = lay["N"], lay["nW"]
+    tl = (2 * window[0] - 1) * (2 * window[1] - 1) * (2 * window[2] - 1)
+    q2 = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)) * (0.6 * kernels.LOG2E), half)
+    k = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)), half)
+    v = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)), half)
+    rpb = torch.from_numpy((0.5 * g.standard_normal((tl, nH))).astype(np.float32))
+    fpb = torch.from_numpy((0.5 * g.standard_normal((tl, nH))).astype(np.float32))
+    return q2, k, v, rpb, fpb
+
+
 # (dims, window, shift): eight (8,7,7) windows, one of each last / not-last combination along D, H and W (N = 392: the SHORT body); N < 385
 # (the generic body): the smallest window with two regions on an axis, and a seven-block window whose ranges start past block 0
 GEOMETRIES = [((16, 14, 14), (8, 7, 7), (4, 3, 3)), ((4, 4, 4), (2, 2, 2), (1, 1, 1)), ((8, 14, 14), (4, 7, 7), (2, 3, 3))]
@@ -72,17 +85,11 @@ def test_ranges_launch_vs_oracle_and_full_launch(dims, window, shift, half):
     test_window_attention32_vs_oracle_and_gather_path; against kvq_window_attention32 (every key block, dsplit_from = -1) on the same
     inputs: rows whose range starts at block 0 bit for bit (the blocks passed over come last and add exact zeros), the others within
     the bound test_window_attention32_depth_split allows its second-half rows."""
-    g = np.random.Generator(np.random.PCG64(sum(dims) + sum(window) + 300))
     lay, tok_o, order, ranges, center = region_ordered(dims, window, shift)
     N, nW, nH = lay["N"], lay["nW"], 2
     BW = nW
     assert BW == 8
-    tl = (2 * window[0] - 1) * (2 * window[1] - 1) * (2 * window[2] - 1)
-    q2 = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)) * (0.6 * kernels.LOG2E), half)
-    k = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)), half)
-    v = rnd(torch.from_numpy(g.standard_normal((BW, nH, N, 32)).astype(np.float32)), half)
-    rpb = torch.from_numpy((0.5 * g.standard_normal((tl, nH))).astype(np.float32))
-    fpb = torch.from_numpy((0.5 * g.standard_normal((tl, nH))).astype(np.float32))
+    q2, k, v, rpb, fpb = ranges_operands(dims, window, lay, nH, half)
     # the oracle works in raster order; its output rows move into the region order with the inputs
     ref = to_order(O.attention_core(q2 / kernels.LOG2E, k, v, rpb, fpb, window, lay), order, BW, N).reshape(BW * N, nH * 32)
     ref_img = to_order(O.attention_core(q2 / kernels.LOG2E, k, v, rpb, fpb, window, lay, image=True), order, BW, N).reshape(BW * N, nH * 32)

@@ -322,8 +322,7 @@ def test_window_attention(dims, window, shift, nH, half):
     check(inputs, lambda t: kernels.window_attention(t["qkv"], t["tok"], t["rpb"], t["fpb"], center, lay["nW"], lay["N"], True))
 
 
-@pytest.mark.parametrize("dims,window,shift,nH", ATTN_GEOMS, ids=["N196-padded", "N64"])
-def test_attn_bias32_and_window_attention32(dims, window, shift, nH, half):
+def guarded_attn_bias32_and_window_attention32(dims, window, shift, nH, half):
     inputs, lay, center = _attn_inputs(sum(dims) + nH + 200, dims, window, shift, nH, 3, half, q_scale=0.6 * kernels.LOG2E)
     N, nW = lay["N"], lay["nW"]
 
@@ -336,7 +335,12 @@ def test_attn_bias32_and_window_attention32(dims, window, shift, nH, half):
     check(inputs, call, [Keep(0, torch.arange(nb) >= nb - 2048)])
 
 
-def test_window_attention32_tile_skip_leaves_skipped_rows_alone(half):
+@pytest.mark.parametrize("dims,window,shift,nH", ATTN_GEOMS, ids=["N196-padded", "N64"])
+def test_attn_bias32_and_window_attention32(dims, window, shift, nH, half):
+    guarded_attn_bias32_and_window_attention32(dims, window, shift, nH, half)
+
+
+def guarded_window_attention32_tile_skip(half):
     dims, nH, B = (4, 10, 9), 1, 3
     inputs, lay, center = _attn_inputs(77, dims, WIN, (4, 3, 3), nH, B, half, q_scale=0.6 * kernels.LOG2E)
     N, nW = lay["N"], lay["nW"]
@@ -356,7 +360,11 @@ def test_window_attention32_tile_skip_leaves_skipped_rows_alone(half):
     check(inputs, call, [Keep(0, row_mask((B * nW * N, nH * 32), 0, both))])
 
 
-def test_window_attention32_depth_split(half):
+def test_window_attention32_tile_skip_leaves_skipped_rows_alone(half):
+    guarded_window_attention32_tile_skip(half)
+
+
+def guarded_window_attention32_depth_split(half):
     dims, nH, B = (16, 14, 14), 3, 2
     inputs, lay, center = _attn_inputs(51, dims, WIN, (4, 3, 3), nH, B, half, q_scale=0.7)
     N, nW = lay["N"], lay["nW"]
@@ -366,6 +374,10 @@ def test_window_attention32_depth_split(half):
         image = kernels.attn_bias32(t["tok"], t["rpb"], t["fpb"], center, nW, N, True)
         return kernels.window_attention32(t["qkv"], image, nW, N, dsplit_from=first)
     check(inputs, call)
+
+
+def test_window_attention32_depth_split(half):
+    guarded_window_attention32_depth_split(half)
 
 
 def test_window_attention32_fused_projection_fills_the_q_scratch(half):
@@ -386,7 +398,7 @@ def test_window_attention32_fused_projection_fills_the_q_scratch(half):
     check(inputs, call)
 
 
-def test_window_attention32_pad_mask_does_not_read_padding_rows(half):
+def guarded_window_attention32_pad_mask(half):
     dims, nH, B = (8, 10, 9), 2, 2
     inputs, lay, center = _attn_inputs(177, dims, WIN, (4, 3, 3), nH, B, half, gated=False, q_scale=0.7)
     N, nW = lay["N"], lay["nW"]
@@ -405,13 +417,16 @@ def test_window_attention32_pad_mask_does_not_read_padding_rows(half):
     check(inputs, call)
 
 
-def test_window_attention32_ranges(half):
+def test_window_attention32_pad_mask_does_not_read_padding_rows(half):
+    guarded_window_attention32_pad_mask(half)
+
+
+def guarded_window_attention32_ranges(dims, window, shift, half):
     from test_gpu_attn_ranges import region_ordered
-    dims, window, shift = (4, 4, 4), (2, 2, 2), (1, 1, 1)
     g = gen(300)
     lay, tok_o, order, ranges, center = region_ordered(dims, window, shift)
     N, nW, nH = lay["N"], lay["nW"], 2
-    tl = 27
+    tl = (2 * window[0] - 1) * (2 * window[1] - 1) * (2 * window[2] - 1)
     qkv = f32(g, 3, nH, nW * N, 32)
     qkv[0] *= 0.6 * kernels.LOG2E
     inputs = dict(qkv=qkv.to(half), tok=i32(tok_o), rpb=f32(g, tl, nH, sc=0.5), fpb=f32(g, tl, nH, sc=0.5),
@@ -421,6 +436,10 @@ def test_window_attention32_ranges(half):
         image = kernels.attn_bias32(t["tok"], t["rpb"], t["fpb"], center, nW, N, True)
         return kernels.window_attention32(t["qkv"], image, nW, N, ranges=t["ranges"])
     check(inputs, call)
+
+
+def test_window_attention32_ranges(half):
+    guarded_window_attention32_ranges((4, 4, 4), (2, 2, 2), (1, 1, 1), half)
 
 
 # --------------------------------------------------------------------------------------------------- fused token launches
@@ -448,6 +467,10 @@ TAILS = [  # C, dims (None: identity over 333 rows), shift, mode, next shift, em
                          ids=["C96-333rows", "C192-357", "C384-4109-scatter", "C384-4109-gather", "C768-1677", "C96-next-norm", "C192-next-qkv",
                               "C96-fp16-stream"])
 def test_block_tail(C, dims, shift, mode, nxt, emit, x16, half):
+    guarded_block_tail(C, dims, shift, mode, nxt, emit, x16, half)
+
+
+def guarded_block_tail(C, dims, shift, mode, nxt, emit, x16, half):
     g = gen(C + (sum(dims) if dims else 0) + len(mode))
     hidden, B = 4 * C, 2
     inputs = dict(pack=_tail_weights(g, C, half))

@@ -23,6 +23,19 @@ def rng(seed):
 
 HALVES = [torch.float16, torch.bfloat16]
 EPS = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}     # half-ulp relative rounding error
+# window_attention32 against the oracle, in units of EPS: the maximum against the oracle fed the bias as the image holds it, the mean
+# against the exact-bias oracle; and the image's own fp16 rounding of the bias (tests/test_gpu_latency_mode.py asserts the same three)
+ATTN32_MAX, ATTN32_MEAN, IMAGE_ROUNDING = 6.4, 0.5, 2.0 ** -7
+
+
+def tail_bound(half, scale):
+    """the fused tail's x (and its emitted q | k | v) against the fp32 composition with the launch's 16-bit rounding points"""
+    return 6 * EPS[half] * scale + 1e-4
+
+
+def emitted_bound(half, scale):
+    """rows a tail emits (norm1 of the next block, or its q | k | v against the GEMM launch): one 16-bit rounding"""
+    return 2 * EPS[half] * scale + 1e-5
 
 
 @pytest.fixture(params=HALVES, ids=["fp16", "bf16"])
@@ -473,6 +486,34 @@ def test_window_attention_softmax_extremes(half):
     assert (out - ref).abs().max().item() <= 6.4 * EPS[half]
 
 
+def _tile_skip_mask(g, nW, N):
+    """int32 [nW]: a random tile_skip word per window (bit t = rows 16t..16t+15 are padding only); q-block 0 always runs"""
+    skip = np.zeros(nW, np.int32)
+    nqt = -(-N // 16)
+    for wv in range(nW):
+        skip[wv] = int(g.integers(0, 1 << nqt)) & ~3                       # q-block 0 always runs
+    return skip
+
+
+def _tile_skipped_rows(skip, BW, nW, N):
+    """bool [BW * N]: the rows of q-blocks whose two 16-row tiles are both marked (the launch passes those q-blocks over)"""
+    rows = np.arange(BW * N)
+    t0 = 2 * ((rows % N) // 32)
+    sk = skip[(rows // N) % nW]
+    both = ((sk >> t0) & 1) & (((sk >> (t0 + 1)) & 1) | (16 * (t0 + 1) >= N))
+    return torch.from_numpy(both.astype(bool))
+
+
+def _pad_mask_words(pad):
+    """pad bool [nW, N] -> uint32 [nW, 13]: bit r & 31 of word r >> 5 = row r of the window is a padding row (``pad_mask``)"""
+    pad = np.asarray(pad)
+    mask = np.zeros((pad.shape[0], 13), np.uint32)
+    for wv in range(pad.shape[0]):
+        for r in np.nonzero(pad[wv])[0]:
+            mask[wv, r >> 5] |= np.uint32(1) << np.uint32(r & 31)
+    return mask
+
+
 @pytest.mark.parametrize("dims,window,shifted,gated,nH", [
     ((8, 14, 14), (8, 7, 7), False, True, 3),
     ((8, 14, 14), (8, 7, 7), True, True, 3),
@@ -510,9 +551,9 @@ def test_window_attention32_vs_oracle_and_gather_path(dims, window, shifted, gat
     # against the oracle fed the bias as the image holds it (fp16 of bias - row maximum): the 16-bit rounding of the probabilities and of
     # the output only; the image's own rounding against the exact fp32 bias is bounded separately
     ref_img = O.attention_core(q2 / kernels.LOG2E, k, v, rpb, fpb, window, lay, image=True).reshape(BW * N, nH * 32)
-    assert (out - ref_img).abs().max().item() <= 6.4 * EPS[half]
-    assert (ref_img - ref).abs().max().item() <= 2.0 ** -7
-    assert (out - ref).abs().mean().item() <= 0.5 * EPS[half]
+    assert (out - ref_img).abs().max().item() <= ATTN32_MAX * EPS[half]
+    assert (ref_img - ref).abs().max().item() <= IMAGE_ROUNDING
+    assert (out - ref).abs().mean().item() <= ATTN32_MEAN * EPS[half]
     # the exact per-score path on the same inputs: the two kernels' roundings + the image's + ONE MORE 16-bit rounding of q (the gather
     # kernel takes q un-scaled; re-rounding q moves every logit by up to 2^-9 (bf16) / 2^-12 (fp16) of its size)
     qg = rnd(q2 / kernels.LOG2E, half)
@@ -520,24 +561,15 @@ def test_window_attention32_vs_oracle_and_gather_path(dims, window, shifted, gat
     gather = kernels.window_attention(qkv_g, tokd, rpbd, fpbd, center, nW, N, use_mask).float().cpu()
     assert (out - gather).abs().max().item() <= 12.0 * EPS[half] + (ref_img - ref).abs().max().item()
     # q-blocks whose two 16-row tiles are both marked in tile_skip are passed over: their rows keep the sentinel
-    skip = np.zeros(nW, np.int32)
-    nqt = -(-N // 16)
-    for wv in range(nW):
-        skip[wv] = int(g.integers(0, 1 << nqt)) & ~3                       # q-block 0 always runs
+    skip = _tile_skip_mask(g, nW, N)
     sentinel = torch.full((BW * N, nH * 32), 7.0, dtype=half, device=qkv.device)
     part = kernels.window_attention32(qkv, image, nW, N, n_types, tile_skip=dev(torch.from_numpy(skip)), out=sentinel).float().cpu()
-    rows = np.arange(BW * N)
-    t0 = 2 * ((rows % N) // 32)
-    sk = skip[(rows // N) % nW]
-    both = ((sk >> t0) & 1) & (((sk >> (t0 + 1)) & 1) | (16 * (t0 + 1) >= N))
-    skipped = torch.from_numpy(both.astype(bool))
+    skipped = _tile_skipped_rows(skip, BW, nW, N)
     assert torch.equal(part[~skipped], out[~skipped]) and bool((part[skipped] == 7.0).all())
 
 
-def test_window_attention32_extremes_and_rescale(half):
-    """Rows whose maximum grows by far more than the rescale threshold in the middle of the key range (a dominant key in a late
-    block), rows that START masked (shifted windows: the first key blocks of some queries hold -100 only), and a key that dominates
-    by > 80: finite, and within the rounding budget of the oracle."""
+def _extremes_inputs(half):
+    """(q2, k, v, rpb, window, lay) of test_window_attention32_extremes_and_rescale: one clip, nW = 8, nH = 2"""
     g = rng(31)
     window, shift = (8, 7, 7), (4, 3, 3)
     lay = O.window_layout(16, 14, 14, window, shift)
@@ -552,13 +584,22 @@ def test_window_attention32_extremes_and_rescale(half):
     rpb = torch.from_numpy((0.5 * g.standard_normal((2535, nH))).astype(np.float32))
     rpb[:, 1] = 0.0          # head 1: biases 0 / -100 only — exact in the fp16 image (a +96 logit against a rounded -100.3 would make
                              # the test measure the image's rounding under cancellation, which the dense kernel shares)
+    return q2, k, v, rpb, window, lay
+
+
+def test_window_attention32_extremes_and_rescale(half):
+    """Rows whose maximum grows by far more than the rescale threshold in the middle of the key range (a dominant key in a late
+    block), rows that START masked (shifted windows: the first key blocks of some queries hold -100 only), and a key that dominates
+    by > 80: finite, and within the rounding budget of the oracle."""
+    q2, k, v, rpb, window, lay = _extremes_inputs(half)
+    N, nW, nH = lay["N"], lay["nW"], 2
     ref = O.attention_core(q2 / kernels.LOG2E, k, v, rpb, None, window, lay).reshape(nW * N, nH * 32)
     tok, center = _tok_table(lay, window)
     qkv = dev(torch.stack([q2, k, v]).permute(0, 2, 1, 3, 4).reshape(3, nH, nW * N, 32).contiguous(), half)
     image = kernels.attn_bias32(dev(torch.from_numpy(tok)), dev(rpb), None, center, nW, N, True)
     out = kernels.window_attention32(qkv, image, nW, N).float().cpu()
     assert torch.isfinite(out).all()
-    assert (out - ref).abs().max().item() <= 6.4 * EPS[half] + 2.0 ** -7
+    assert (out - ref).abs().max().item() <= ATTN32_MAX * EPS[half] + IMAGE_ROUNDING
 
 
 @pytest.mark.parametrize("dims", [(16, 14, 14), (24, 7, 7)])
@@ -653,10 +694,7 @@ def test_window_attention32_writes_padding_rows_itself(half):
     rpb = torch.from_numpy((0.5 * g.standard_normal((2535, nH))).astype(np.float32))
     tok, center = _tok_table(lay, window)
     image = kernels.attn_bias32(dev(torch.from_numpy(tok)), dev(rpb), None, center, nW, N, True)
-    mask = np.zeros((nW, 13), np.uint32)
-    for wv in range(nW):
-        for r in np.nonzero(pad[wv].numpy())[0]:
-            mask[wv, r >> 5] |= np.uint32(1) << np.uint32(r & 31)
+    mask = _pad_mask_words(pad.numpy())
     ref = kernels.window_attention32(dev(filled.reshape(3, nH, BW * N, 32), half), image, nW, N).float().cpu()
     out = kernels.window_attention32(dev(holes.reshape(3, nH, BW * N, 32), half), image, nW, N, b_qkv=dev(bq),
                                      pad_mask=dev(torch.from_numpy(mask.view(np.int32)))).float().cpu()
@@ -767,6 +805,36 @@ def test_fragment_gather_reference_assert():
 
 
 # ------------------------------------------------------------------ fused proj + norm2 + Mlp (tail.hip)
+def _tail_draws(g, C, rows_a, rows_x, half):
+    """(t, A, x, wts): what every fused-tail test draws first, in this order — the attention rows (rounded to ``half``), the residual
+    stream, the three 16-bit weights, the three biases, norm2's gamma and beta; ``t`` draws on from the same generator.
+    wts = (Wp, bp, g2, b2n, W1, b1, W2, b2), the order ``_tail_reference`` and ``kernels.block_tail_pack`` take."""
+    hidden = 4 * C
+    t = lambda *s, sc=1.0: torch.from_numpy((g.standard_normal(s) * sc).astype(np.float32))      # noqa: E731
+    A = rnd(t(rows_a, C), half)
+    x = t(rows_x, C, sc=2.0)
+    Wp, W1, W2 = rnd(t(C, C, sc=0.15), half), rnd(t(hidden, C, sc=0.15), half), rnd(t(C, hidden, sc=0.08), half)
+    bp, b1, b2 = t(C, sc=0.3), t(hidden, sc=0.3), t(C, sc=0.3)
+    g2, b2n = 1 + 0.2 * t(C), 0.2 * t(C)
+    return t, A, x, (Wp, bp, g2, b2n, W1, b1, W2, b2)
+
+
+def _next_dst(lay2, L):
+    """int32 [L]: token -> its row in the next block's window order (un-padded partitions)"""
+    assert (lay2["src"] >= 0).all()
+    dst = np.empty(L, np.int32)
+    dst[lay2["src"]] = np.arange(L, dtype=np.int32)
+    return dst
+
+
+def _fp16_stream(x):
+    """the fp16 residual stream of test_block_tail_fp16_residual_stream: x narrowed, row 0 given +-60000, the fp16 maximum and a subnormal"""
+    x16 = x.to(torch.float16)
+    x16[0, :4] = torch.tensor([70000.0, -70000.0, 65504.0, 1e-7]).to(torch.float16)               # inf, -inf (a saturated producer never writes them), max, a subnormal
+    x16[0, :2] = torch.tensor([60000.0, -60000.0]).to(torch.float16)
+    return x16
+
+
 def _tail_reference(A, x, wts, half, lay, B, dims):
     """fp32 composition with the 16-bit operand roundings the launch applies (norm2 output, GELU output)."""
     Wp, bp, g2, b2n, W1, b1, W2, b2 = wts
@@ -800,29 +868,22 @@ def test_block_tail(C, dims, shift, nxt_shift, half):
     B, hidden = 2, 4 * C
     lay = O.window_layout(D, H, W, (8, 7, 7), shift)
     Lp, L = lay["nW"] * lay["N"], D * H * W
-    t = lambda *s, sc=1.0: torch.from_numpy((g.standard_normal(s) * sc).astype(np.float32))
-    A = rnd(t(B * Lp, C), half)
-    x = t(B * L, C, sc=2.0)
-    Wp, W1, W2 = rnd(t(C, C, sc=0.15), half), rnd(t(hidden, C, sc=0.15), half), rnd(t(C, hidden, sc=0.08), half)
-    bp, b1, b2 = t(C, sc=0.3), t(hidden, sc=0.3), t(C, sc=0.3)
-    g2, b2n = 1 + 0.2 * t(C), 0.2 * t(C)
-    wts = (Wp, bp, g2, b2n, W1, b1, W2, b2)
+    t, A, x, wts = _tail_draws(g, C, B * Lp, B * L, half)
+    Wp, bp, g2, b2n, W1, b1, W2, b2 = wts
     pack = kernels.block_tail_pack(dev(Wp, half), dev(bp), dev(g2), dev(b2n), dev(W1, half), dev(b1), dev(W2, half), dev(b2))
     ref = _tail_reference(A, x, wts, half, lay, B, dims)
     xd = dev(x.clone())
     kw = {}
     if nxt_shift is not None:
         lay2 = O.window_layout(D, H, W, (8, 7, 7), nxt_shift)
-        assert (lay2["src"] >= 0).all()
-        dst = np.empty(L, np.int32)
-        dst[lay2["src"]] = np.arange(L, dtype=np.int32)
+        dst = _next_dst(lay2, L)
         gn, bn = 1 + 0.2 * t(C), 0.2 * t(C)
         kw = dict(next_norm=(dev(gn), dev(bn)), next_dst=dev(torch.from_numpy(dst)), next_rows=L)
     out_ln = kernels.block_tail(dev(A, half), xd, pack, hidden, scatter_map=dev(torch.from_numpy(lay["src"].astype(np.int32))),
                                 map_rows=Lp, out_rows=L, **kw)
     got = xd.cpu()
     scale = ref.abs().max().item()
-    assert (got - ref).abs().max().item() <= 6 * EPS[half] * scale + 1e-4, ((got - ref).abs().max().item(), scale)
+    assert (got - ref).abs().max().item() <= tail_bound(half, scale), ((got - ref).abs().max().item(), scale)
     if Lp != L:
         # padded windows: the launch that walks the TOKENS (attn_gather = the inverse of the scatter map) instead of the window
         # rows computes every real token exactly as before
@@ -836,7 +897,7 @@ def test_block_tail(C, dims, shift, nxt_shift, half):
         ln = torch.nn.functional.layer_norm(got, (C,), gn, bn).reshape(B, D, H, W, C)
         ref_ln = O.gather_windows(ln, lay2).reshape(-1, C)
         d = (out_ln.float().cpu() - ref_ln).abs().max().item()
-        assert d <= 2 * EPS[half] * ref_ln.abs().max().item() + 1e-5, d
+        assert d <= emitted_bound(half, ref_ln.abs().max().item()), d
 
 
 @pytest.mark.parametrize("C,dims,shift,nxt_shift", [(384, (8, 14, 14), (0, 0, 0), (4, 3, 3)), (384, (16, 14, 14), (4, 3, 3), (0, 0, 0)),
@@ -856,18 +917,14 @@ def test_block_tail_emits_next_qkv(C, dims, shift, nxt_shift, half):
     lay2 = O.window_layout(D, H, W, (8, 7, 7), nxt_shift)
     Lp, L = lay["nW"] * lay["N"], D * H * W
     assert Lp == L and (lay2["src"] >= 0).all()
-    t = lambda *s, sc=1.0: torch.from_numpy((g.standard_normal(s) * sc).astype(np.float32))
-    A, x = rnd(t(B * Lp, C), half), t(B * L, C, sc=2.0)
-    Wp, W1, W2 = rnd(t(C, C, sc=0.15), half), rnd(t(hidden, C, sc=0.15), half), rnd(t(C, hidden, sc=0.08), half)
-    bp, b1, b2, g2, b2n = t(C, sc=0.3), t(hidden, sc=0.3), t(C, sc=0.3), 1 + 0.2 * t(C), 0.2 * t(C)
+    t, A, x, (Wp, bp, g2, b2n, W1, b1, W2, b2) = _tail_draws(g, C, B * Lp, B * L, half)
     Wq, bq = rnd(t(3 * C, C, sc=0.1), half), t(3 * C, sc=0.3)
     gn, bn = 1 + 0.2 * t(C), 0.2 * t(C)
     qs = 0.25
     pack = kernels.block_tail_pack(dev(Wp, half), dev(bp), dev(g2), dev(b2n), dev(W1, half), dev(b1), dev(W2, half), dev(b2))
     qpack = kernels.block_tail_qkv_pack(dev(Wq, half), hidden)
     assert qpack is not None
-    dst = np.empty(L, np.int32)
-    dst[lay2["src"]] = np.arange(L, dtype=np.int32)
+    dst = _next_dst(lay2, L)
     common = dict(scatter_map=dev(torch.from_numpy(lay["src"].astype(np.int32))), map_rows=Lp, out_rows=L,
                   next_norm=(dev(gn), dev(bn)), next_dst=dev(torch.from_numpy(dst)), next_rows=L)
     x_ln, x_qkv = dev(x.clone()), dev(x.clone())
@@ -877,14 +934,14 @@ def test_block_tail_emits_next_qkv(C, dims, shift, nxt_shift, half):
     assert qkv.shape == (3, nH, B * L, 32)
     ref = kernels.gemm(ln_rows, dev(Wq, half), dev(bq), _abi.EPI_QKV_BF16, num_heads=nH, q_scale=qs).reshape(3, nH, B * L, 32)
     d = (qkv.float() - ref.float()).abs().max().item()
-    assert d <= 2 * EPS[half] * ref.float().abs().max().item() + 1e-5, d
+    assert d <= emitted_bound(half, ref.float().abs().max().item()), d
     # and against the fp32 composition on the launch's residual output
     ln = torch.nn.functional.layer_norm(x_qkv.cpu(), (C,), gn, bn).reshape(B, D, H, W, C)
     rows = rnd(O.gather_windows(ln, lay2).reshape(-1, C), half)
     full = rows @ Wq.t() + bq
     full[:, :C] *= qs
     want = full.reshape(B * L, 3, nH, 32).permute(1, 2, 0, 3)
-    assert (qkv.float().cpu() - want).abs().max().item() <= 6 * EPS[half] * want.abs().max().item() + 1e-4
+    assert (qkv.float().cpu() - want).abs().max().item() <= tail_bound(half, want.abs().max().item())
 
 
 def test_block_tail_identity_map_and_unsupported(half):
@@ -1144,19 +1201,13 @@ def test_block_tail_fp16_residual_stream(C, dims, shift, nxt_shift, qkv, half):
     B, hidden = 2, 4 * C
     lay = O.window_layout(D, H, W, (8, 7, 7), shift)
     Lp, L = lay["nW"] * lay["N"], D * H * W
-    t = lambda *s, sc=1.0: torch.from_numpy((g.standard_normal(s) * sc).astype(np.float32))      # noqa: E731
-    A = rnd(t(B * Lp, C), half)
-    x16 = t(B * L, C, sc=2.0).to(torch.float16)
-    x16[0, :4] = torch.tensor([70000.0, -70000.0, 65504.0, 1e-7]).to(torch.float16)               # inf, -inf (a saturated producer never writes them), max, a subnormal
-    x16[0, :2] = torch.tensor([60000.0, -60000.0]).to(torch.float16)
-    Wp, W1, W2 = rnd(t(C, C, sc=0.15), half), rnd(t(hidden, C, sc=0.15), half), rnd(t(C, hidden, sc=0.08), half)
-    bp, b1, b2, g2, b2n = t(C, sc=0.3), t(hidden, sc=0.3), t(C, sc=0.3), 1 + 0.2 * t(C), 0.2 * t(C)
+    t, A, x, (Wp, bp, g2, b2n, W1, b1, W2, b2) = _tail_draws(g, C, B * Lp, B * L, half)
+    x16 = _fp16_stream(x)
     pack = kernels.block_tail_pack(dev(Wp, half), dev(bp), dev(g2), dev(b2n), dev(W1, half), dev(b1), dev(W2, half), dev(b2))
     kw = {}
     if nxt_shift is not None:
         lay2 = O.window_layout(D, H, W, (8, 7, 7), nxt_shift)
-        dst = np.empty(L, np.int32)
-        dst[lay2["src"]] = np.arange(L, dtype=np.int32)
+        dst = _next_dst(lay2, L)
         kw = dict(next_norm=(dev(1 + 0.2 * t(C)), dev(0.2 * t(C))), next_dst=dev(torch.from_numpy(dst)), next_rows=L)
         if qkv:
             wq = rnd(t(3 * C, C, sc=0.1), half)
