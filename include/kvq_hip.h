@@ -743,6 +743,45 @@ int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out, size_t coe
 int kvq_jpeg_idct_i420_host(const int16_t* coef, const uint16_t* qt, int T, int H, int W, uint8_t* frames_out);
 int kvq_jpeg_idct_i420(const void* coef, const void* qt, int T, int H, int W, uint8_t* frames_out, void* stream);
 
+/* Baseline JPEG, writing (Motion-JPEG frames): the mirror of the reader.  Colour conversion, chroma averaging, forward DCT and
+ * quantisation on the device (csrc/jpeg_enc.hip) or by the scalar twin, the Huffman entropy coder on the host (csrc/jpeg_enc.cpp,
+ * plain C++, no HIP call).  The hand-over between the two is the one above, so what one side writes the other reads.  The block
+ * analysis is defined to the bit in csrc/jpeg_fdct.hpp and reproduces the quantised coefficients of the IJG library's default
+ * ("slow integer") encoder on every block that holds a sample of the picture: JFIF's BT.601 full-range RGB -> YCbCr with 16
+ * fractional bits, chroma = the 2 x 2 average with the alternating 1 / 2 rounding bias (the last column / row replicated for odd
+ * W / H), planes padded to whole 16 x 16 MCUs by clamping the coordinates in each plane, level shift, rows-then-columns integer
+ * DCT scaled by 8, coefficient = sign(F) ((|F| + (d >> 1)) / d) with d = q << 3, the division carried out as a multiplication by a
+ * reciprocal prepared once per table.  Table entries are 8-bit, 1..255 (the block analysis clamps an entry outside that range,
+ * kvq_jpeg_encode refuses it).
+ *
+ * kvq_jpeg_quant_tables (host only): out = uint16 [3][64] (Y, Cb, Cr; natural order) for quality 1..100: the Annex K.1 tables scaled
+ * the IJG way, s = quality < 50 ? 5000 / quality : 200 - 2 quality, entry = clamp((base s + 50) / 100, 1, 255).
+ * kvq_jpeg_quantise_host (host only): out[i] = the quantiser above on F[i] (|F[i]| <= 32767, q in 1..255) — the reciprocal form
+ * on its own, so that it can be compared with the division over its whole range.
+ *
+ * kvq_jpeg_fdct: src = T frames on the device — src_format KVQ_SRC_U8: planar uint8 (3, T, H, W), R G B; KVQ_SRC_I420_BT601_FULL:
+ * T I420 frames, whose planes are taken as they are; any other format is KVQ_ERR_UNSUPPORTED (convert with kvq_yuv420_to_rgb) —
+ * and qt = uint16 [T][3][64] (device) -> coef_out = T x kvq_jpeg_coef_bytes(H, W) bytes of coefficients.  One launch; an RGB source
+ * is converted where its pixels are loaded, no intermediate frame is written.  Sizes and alignment as kvq_jpeg_idct_i420: T in
+ * 1..65535, H, W in 1..65535 with H W < 2^28, coef_out and qt 16-byte aligned (src: any address), else KVQ_ERR_SHAPE.
+ * kvq_jpeg_fdct_host: the same on host memory, bit-equal.
+ *
+ * kvq_jpeg_encode (host only) writes the coefficients of ONE frame as a baseline JFIF image into out[0 .. cap): SOI, APP0 (JFIF
+ * 1.01), one DQT per table (two when the Cb and Cr tables are equal), SOF0 (Y 2x2, Cb 1x1, Cr 1x1), the four Annex K.3 Huffman
+ * tables as one DHT each — left out with KVQ_JPEG_NO_DHT, the form of AVI "MJPG" frames, which the reader accepts — DRI and RSTn
+ * when restart_interval (MCUs, 0..65535) is not 0, SOS, the byte-stuffed scan, EOI.  *n = the image's length.  A coefficient outside
+ * baseline's categories (|AC| > 1023, |DC difference| > 2047) or a table entry outside 1..255 is KVQ_ERR_UNSUPPORTED naming the
+ * block; an image longer than cap is KVQ_ERR_WORKSPACE with *n = the length it needs.  Nothing is ever written at or past
+ * out + cap.  kvq_jpeg_encode_bound(H, W): a capacity that is always enough (0 for a size outside the limits above). */
+enum { KVQ_JPEG_NO_DHT = 1 };
+int kvq_jpeg_quant_tables(int quality, uint16_t* out /* [3][64] */);
+int kvq_jpeg_quantise_host(const int32_t* F, size_t n, int q, int16_t* out);
+int kvq_jpeg_fdct_host(const uint8_t* src, int src_format, int T, int H, int W, const uint16_t* qt, int16_t* coef_out);
+int kvq_jpeg_fdct(const void* src, int src_format, int T, int H, int W, const void* qt, void* coef_out, void* stream);
+size_t kvq_jpeg_encode_bound(int H, int W);
+int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt /* [3][64] */, int H, int W, int restart_interval, int flags, uint8_t* out,
+                    size_t cap, size_t* n);
+
 /* torchvision Resize on a tensor (= bilinear, align_corners=False, no antialias; get_resize_function,
  * fusion_datasets.py:229-241) + crop + (v-mean)/std: get_resized_video (:244-252), get_resizecrop_video
  * (:299-316).  video u8|fp32 (C,T,H,W) -> resized to (rh,rw) -> crop [cy:cy+oh, cx:cx+ow] -> out fp32

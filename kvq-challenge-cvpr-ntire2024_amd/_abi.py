@@ -126,6 +126,7 @@ FRAG_MAX_CLIPS = 16
 # KvqSrcFormat: the frame type of a source (the ``src_is_u8`` argument / field).  The I420 values: planar YUV 4:2:0, frame-major
 SRC_F32, SRC_U8, SRC_I420_BT601_LIMITED, SRC_I420_BT601_FULL, SRC_I420_BT709_LIMITED, SRC_I420_BT709_FULL = range(6)
 I420_FORMATS = (SRC_I420_BT601_LIMITED, SRC_I420_BT601_FULL, SRC_I420_BT709_LIMITED, SRC_I420_BT709_FULL)
+JPEG_NO_DHT = 1      # kvq_jpeg_encode flag: leave the DHT segments out (the Annex K tables are implied)
 
 
 def i420_format(matrix="bt601", full_range=False) -> int:
@@ -312,6 +313,12 @@ SYMBOLS = {
     "kvq_jpeg_coeffs": (i32, [p_void, sz, p_void, sz, p_void]),
     "kvq_jpeg_idct_i420_host": (i32, [p_void, p_void, i32, i32, i32, p_void]),
     "kvq_jpeg_idct_i420": (i32, [p_void, p_void, i32, i32, i32, p_void, p_void]),
+    "kvq_jpeg_quant_tables": (i32, [i32, p_void]),
+    "kvq_jpeg_quantise_host": (i32, [p_void, sz, i32, p_void]),
+    "kvq_jpeg_fdct_host": (i32, [p_void, i32, i32, i32, i32, p_void, p_void]),
+    "kvq_jpeg_fdct": (i32, [p_void, i32, i32, i32, i32, p_void, p_void, p_void]),
+    "kvq_jpeg_encode_bound": (sz, [i32, i32]),
+    "kvq_jpeg_encode": (i32, [p_void, p_void, i32, i32, i32, i32, p_void, sz, C.POINTER(sz)]),
     "kvq_fragment_gather_batch": (i32, [C.POINTER(KvqFragmentSource), i32, i32, p_void, p_void]),
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),

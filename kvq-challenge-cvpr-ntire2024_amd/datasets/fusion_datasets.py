@@ -742,6 +742,149 @@ def _jpeg_frames_to_device(vr, uniq, device):
     return kernels.jpeg_idct_i420(dev[:n * cb].view(torch.int16).view(n, cb // 2), dev[n * cb:].view(torch.uint16).view(n, 3, 64), vr.H, vr.W)
 
 
+class MjpegWriter:
+    """Motion-JPEG video written without a codec library, the mirror of ``MjpegFrameReader``: every frame one baseline 4:2:0 JFIF
+    image of IJG quality ``quality`` (``kernels.jpeg_quant_tables``), RSTn markers every ``restart_interval`` MCUs when that is not 0.
+    ``path`` picks the container the reader knows:
+      ``*.mjpeg`` / ``*.mjpg``  the images back to back
+      ``*.avi``                 RIFF AVI: ``hdrl`` (MJPG handler and compression, W, H, the rate ``fps``), a ``movi`` list of ``00dc``
+                                chunks and ``idx1``; the header and the index are completed by ``close()``.  A file that would pass
+                                ``AVI_LIMIT`` (1 GiB; OpenDML, which larger files need, is not written and not read) is a ValueError
+                                BEFORE the frame is written: the file stays a valid AVI of the frames so far
+      anything else             a directory of ``%06d.jpg`` files, numbered from 0
+    ``write(frames)``: a uint8 (3, T, H, W) tensor (R G B) or ``kernels.I420Frames`` of BT.601 full range — JFIF fixes that matrix, so
+    any other I420 format is a ValueError (convert with ``to_rgb()``).  On the device: ONE ``jpeg_fdct`` launch, ONE D2H copy of the
+    coefficients into pinned staging, then the entropy coder on the threads of the copy pool (the library calls release the GIL).
+    Host tensors go through the scalar twin of the launch (bit-equal).  ``write_coefficients(coef, H, W)`` takes coefficients that
+    are already on the host.  All frames of a video have the first frame's size.  Use as a context manager or call ``close()``."""
+
+    AVI_LIMIT = 1 << 30
+    _AVI_HEADER = 12 + 12 + 64 + 12 + 64 + 48 + 12      # RIFF, hdrl LIST, avih chunk, strl LIST, strh chunk, strf chunk, movi LIST
+
+    def __init__(self, path, fps, quality=90, restart_interval=0):
+        from fractions import Fraction
+        self.path, self.fps, self.quality, self.restart_interval = str(path), float(fps), int(quality), int(restart_interval)
+        if not self.fps > 0:
+            raise ValueError(f"MjpegWriter: fps must be positive, got {fps}")
+        if not 0 <= self.restart_interval <= 65535:
+            raise ValueError(f"MjpegWriter: restart_interval must be 0..65535, got {restart_interval}")
+        self.qt = kernels.jpeg_quant_tables(self.quality)
+        rate = Fraction(self.fps).limit_denominator(100000)
+        self._rate, self._scale = rate.numerator, rate.denominator
+        low = self.path.lower()
+        self.kind = "stream" if low.endswith((".mjpeg", ".mjpg")) else "avi" if low.endswith(".avi") else "dir"
+        self.H = self.W = None
+        self.frames = 0
+        self._qt_dev = {}
+        self._index = []                                     # avi: (offset from the 'movi' tag, length) per frame
+        if self.kind == "dir":
+            os.makedirs(self.path, exist_ok=True)
+            self._file = None
+        else:
+            self._file = open(self.path, "wb")
+            if self.kind == "avi":
+                self._file.write(b"\0" * self._AVI_HEADER)   # completed by close()
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _set_size(self, H, W):
+        if self.H is None:
+            self.H, self.W = int(H), int(W)
+            self._bound = kernels.jpeg_encode_bound(self.H, self.W)
+        elif (self.H, self.W) != (int(H), int(W)):
+            raise ValueError(f"{self.path}: a frame of {W} x {H} in a video of {self.W} x {self.H}")
+
+    def write(self, frames):
+        if self._closed:
+            raise ValueError(f"{self.path}: write() after close()")
+        i420 = isinstance(frames, kernels.I420Frames)
+        if i420 and frames.format != kernels._abi.SRC_I420_BT601_FULL:
+            raise ValueError(f"{self.path}: I420 frames of format {frames.format} — JFIF fixes BT.601 full range; convert them with to_rgb() first")
+        data = frames.data if i420 else frames
+        if not (data.dtype == torch.uint8 and len(frames.shape) == 4 and frames.shape[0] == 3):
+            raise ValueError(f"{self.path}: expected uint8 (3, T, H, W) frames or I420Frames, got {data.dtype} {tuple(frames.shape)}")
+        _, T, H, W = frames.shape
+        self._set_size(H, W)
+        if not data.is_cuda:
+            src = data.contiguous().numpy()
+            return self.write_coefficients(kernels.jpeg_fdct_host(src, self.qt, H, W, frames.format if i420 else kernels._abi.SRC_U8), H, W)
+        qt = self._qt_dev.get(data.device)
+        if qt is None:
+            qt = self._qt_dev[data.device] = torch.from_numpy(self.qt.view(np.int16)).to(data.device).view(torch.uint16)
+        coef = kernels.jpeg_fdct(frames if i420 else data.contiguous(), qt)
+        st, k = _Staging.get(coef.numel() * 2)
+        stage = st["buf"][k][:coef.numel() * 2].view(torch.int16).view(coef.shape)
+        stage.copy_(coef, non_blocking=True)
+        torch.cuda.current_stream(data.device).synchronize()
+        st["ev"][k] = None
+        return self.write_coefficients(stage.numpy(), H, W)
+
+    def _encode(self, coef):
+        """frames of coefficients -> list of bytes, on one thread"""
+        out = np.empty(self._bound, np.uint8)
+        return [kernels.jpeg_encode(c, self.qt, self.H, self.W, self.restart_interval, out=out).tobytes() for c in coef]
+
+    def write_coefficients(self, coef, H, W):
+        """coef: int16 numpy (T, jpeg_coef_bytes / 2), quantised with this writer's tables (``self.qt``), on the host"""
+        if self._closed:
+            raise ValueError(f"{self.path}: write() after close()")
+        self._set_size(H, W)
+        coef = np.ascontiguousarray(coef, np.int16).reshape(-1, kernels.jpeg_coef_bytes(H, W) // 2)
+        n = coef.shape[0]
+        nt = max(1, min(_COPY_THREADS, n))
+        bounds = np.linspace(0, n, nt + 1).astype(int)
+        jobs = [_copy_pool().submit(self._encode, coef[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+        for j in jobs:
+            for image in j.result():
+                self._append(image)
+
+    def _append(self, image):
+        if self.kind == "dir":
+            with open(os.path.join(self.path, "%06d.jpg" % self.frames), "wb") as f:
+                f.write(image)
+        elif self.kind == "stream":
+            self._file.write(image)
+        else:
+            pos, n = self._file.tell(), len(image)
+            total = pos + 8 + n + (n & 1) + 8 + 16 * (self.frames + 1)       # this chunk, then idx1
+            if total > self.AVI_LIMIT:
+                raise ValueError(f"{self.path}: frame {self.frames} would take the AVI file to {total} bytes, past {self.AVI_LIMIT} "
+                                 "(OpenDML is not written); start another file")
+            self._index.append((pos - (self._AVI_HEADER - 4), n))
+            self._file.write(b"00dc" + n.to_bytes(4, "little") + image + (b"\0" if n & 1 else b""))
+        self.frames += 1
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        if self._file is None:
+            return
+        if self.kind == "avi":
+            import struct
+            f, n, W, H = self._file, self.frames, self.W or 0, self.H or 0
+            end = f.tell()
+            f.write(b"idx1" + struct.pack("<I", 16 * n) + b"".join(b"00dc" + struct.pack("<III", 0x10, o, s) for o, s in self._index))
+            size = f.tell()
+            biggest = max((s for _, s in self._index), default=0)
+            avih = struct.pack("<14I", int(round(1e6 * self._scale / self._rate)), 0, 0, 0x10, n, 0, 1, biggest, W, H, 0, 0, 0, 0)
+            strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIII4H", 0, 0, 0, 0, self._scale, self._rate, 0, n, biggest, 0xFFFFFFFF, 0, 0, 0, W, H)
+            strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", W * H * 3, 0, 0, 0, 0)
+            head = (b"RIFF" + struct.pack("<I", size - 8) + b"AVI " + b"LIST" + struct.pack("<I", 4 + 64 + 12 + 64 + 48) + b"hdrl"
+                    + b"avih" + struct.pack("<I", 56) + avih + b"LIST" + struct.pack("<I", 4 + 64 + 48) + b"strl"
+                    + b"strh" + struct.pack("<I", 56) + strh + b"strf" + struct.pack("<I", 40) + strf
+                    + b"LIST" + struct.pack("<I", end - self._AVI_HEADER + 4) + b"movi")
+            assert len(head) == self._AVI_HEADER, len(head)
+            f.seek(0)
+            f.write(head)
+        self._file.close()
+
+
 def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601"):
     """Reference ``spatial_temporal_view_decomposition`` (:376-397), decode half: one reader, every frame fetched once and
     sent to the device once, as uint8; per view a uint8 (3, T, H, W) device tensor (frame gather + layout change in HBM) +

@@ -472,6 +472,88 @@ def jpeg_idct_i420(coef: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Op
     return I420Frames(out, H, W, _abi.SRC_I420_BT601_FULL)
 
 
+def jpeg_quant_tables(quality: int):
+    """uint16 (3, 64) numpy: the Y, Cb, Cr quantiser tables of an IJG quality 1..100, natural order (``kvq_jpeg_quant_tables``)"""
+    import numpy as np
+    out = np.empty((3, 64), np.uint16)
+    check(lib().kvq_jpeg_quant_tables(int(quality), out.ctypes.data), "kvq_jpeg_quant_tables")
+    return out
+
+
+def jpeg_quantise_host(F, q: int):
+    """the quantiser of csrc/jpeg_fdct.hpp on a numpy array of DCT outputs (|F| <= 32767), q in 1..255 -> int16 (``kvq_jpeg_quantise_host``)"""
+    import numpy as np
+    F = np.ascontiguousarray(F, np.int32)
+    out = np.empty(F.shape, np.int16)
+    check(lib().kvq_jpeg_quantise_host(F.ctypes.data, F.size, int(q), out.ctypes.data), "kvq_jpeg_quantise_host")
+    return out
+
+
+def _jpeg_qt_frames(qt, T: int):
+    """(3, 64) tables for every frame, or (T, 3, 64) -> (T, 3, 64)"""
+    if qt.numel() == 192 and T > 1:                     # copied as int16: the copy kernels know every signed type
+        return qt.contiguous().view(torch.int16).reshape(1, 3, 64).expand(T, 3, 64).contiguous().view(torch.uint16)
+    return qt.contiguous().reshape(T, 3, 64)
+
+
+def jpeg_fdct_host(src, qt, H: int, W: int, src_format: int = _abi.SRC_U8):
+    """the scalar twin of ``jpeg_fdct`` on numpy arrays: src uint8 (3, T, H, W) (``SRC_U8``) or (T, i420_frame_bytes)
+    (``SRC_I420_BT601_FULL``), qt uint16 (T, 3, 64) or (3, 64) -> int16 (T, jpeg_coef_bytes / 2)"""
+    import numpy as np
+    src = np.ascontiguousarray(src, np.uint8)
+    T = src.shape[1] if src_format == _abi.SRC_U8 else src.shape[0]
+    assert src.size == (3 * T * H * W if src_format == _abi.SRC_U8 else T * i420_frame_bytes(H, W)), (src.shape, T, H, W, src_format)
+    qt = np.ascontiguousarray(np.broadcast_to(np.asarray(qt, np.uint16).reshape(-1, 3, 64), (T, 3, 64)))
+    out = np.empty((T, jpeg_coef_bytes(H, W) // 2), np.int16)
+    check(lib().kvq_jpeg_fdct_host(src.ctypes.data, int(src_format), T, int(H), int(W), qt.ctypes.data, out.ctypes.data), "kvq_jpeg_fdct_host")
+    return out
+
+
+def jpeg_fdct(frames, qt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frames -> quantised JPEG coefficients, one launch (``kvq_jpeg_fdct``): the input of ``jpeg_encode`` and of ``jpeg_idct_i420``.
+    frames: a device uint8 (3, T, H, W) tensor (R G B) or ``I420Frames`` of format ``SRC_I420_BT601_FULL`` (anything else: convert
+    with ``to_rgb()``); qt uint16 (T, 3, 64) or (3, 64) on the device -> int16 (T, jpeg_coef_bytes / 2)."""
+    i420 = isinstance(frames, I420Frames)
+    data = frames.data if i420 else frames
+    _need_gpu(data, qt)
+    if i420 and frames.format != _abi.SRC_I420_BT601_FULL:
+        raise ValueError(f"jpeg_fdct: I420Frames of format {frames.format}; JFIF fixes BT.601 full range — convert with to_rgb() first")
+    assert data.dtype == torch.uint8 and data.is_contiguous() and len(frames.shape) == 4 and frames.shape[0] == 3, (data.dtype, tuple(frames.shape))
+    _, T, H, W = frames.shape
+    assert qt.dtype == torch.uint16 and qt.numel() in (192, 192 * T), (qt.dtype, tuple(qt.shape))
+    qt = _jpeg_qt_frames(qt, T)
+    n = jpeg_coef_bytes(H, W) // 2
+    if out is None:
+        out = torch.empty(T, n, dtype=torch.int16, device=data.device)
+    else:
+        assert out.dtype == torch.int16 and tuple(out.shape) == (T, n) and out.is_contiguous() and out.device == data.device
+    check(lib().kvq_jpeg_fdct(ptr(data), _frame_format(frames), T, H, W, ptr(qt), ptr(out), stream_of(data)), "kvq_jpeg_fdct")
+    return out
+
+
+def jpeg_encode_bound(H: int, W: int) -> int:
+    """a capacity that holds any frame of H x W written by ``jpeg_encode`` (``kvq_jpeg_encode_bound``)"""
+    n = lib().kvq_jpeg_encode_bound(int(H), int(W))
+    if n == 0:
+        raise ValueError(f"jpeg_encode_bound: a frame of {W} x {H} is outside what the library encodes")
+    return n
+
+
+def jpeg_encode(coef, qt, H: int, W: int, restart_interval: int = 0, dht: bool = True, out=None):
+    """``kvq_jpeg_encode`` (host only): one frame's coefficients, int16 numpy (jpeg_coef_bytes / 2,), and its tables uint16 (3, 64) ->
+    the baseline JFIF image as a uint8 numpy view of ``out`` (a uint8 numpy buffer; None: a new one of ``jpeg_encode_bound``).
+    ``dht=False`` leaves the Huffman tables out (AVI "MJPG" frames).  The ctypes call releases the GIL."""
+    import numpy as np
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size * 2 == jpeg_coef_bytes(H, W), (coef.dtype, coef.shape, H, W)
+    assert qt.dtype == np.uint16 and qt.flags.c_contiguous and qt.size == 192, (qt.dtype, qt.shape)
+    if out is None:
+        out = np.empty(jpeg_encode_bound(H, W), np.uint8)
+    n = C.c_size_t(0)
+    check(lib().kvq_jpeg_encode(coef.ctypes.data, qt.ctypes.data, int(H), int(W), int(restart_interval), 0 if dht else _abi.JPEG_NO_DHT,
+                                out.ctypes.data, out.size, C.byref(n)), "kvq_jpeg_encode")
+    return out[:n.value]
+
+
 def _frame_format(v) -> int:
     """KvqSrcFormat of a frame tensor / ``I420Frames``"""
     return v.format if isinstance(v, I420Frames) else int(v.dtype == torch.uint8)

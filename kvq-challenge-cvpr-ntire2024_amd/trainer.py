@@ -59,7 +59,9 @@ class _MapWriter:
                 b = st["bufs"][k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
             b.copy_(v, non_blocking=True)
         st["event"].record(stream)
-        st["pending"] = (name, {"frame_inds": item.get("frame_inds")} if isinstance(item, dict) else None, list(todo))
+        ksvqe = self.trainer.config["model"]["type"] == "KSVQE"
+        st["pending"] = (name, {"frame_inds": item.get("frame_inds"), "overlay_size": self.trainer._overlay_size(item, ksvqe)}
+                         if isinstance(item, dict) else None, list(todo))
 
     def flush(self):
         for lane in self.sets:
@@ -170,7 +172,7 @@ class Trainer:
             return None
         if not isinstance(qm, dict) or not qm.get("dir"):
             raise ValueError("quality_maps: expected {dir: <path>, cell: 8, overlay_frames: 0}")
-        unknown = set(qm) - {"dir", "cell", "overlay_frames"}
+        unknown = set(qm) - {"dir", "cell", "overlay_frames", "overlay_video", "overlay_quality"}
         if unknown:
             raise ValueError(f"quality_maps: unknown key(s) {sorted(unknown)}")
         cell, nov = int(qm.get("cell", 8)), int(qm.get("overlay_frames", 0))
@@ -179,6 +181,54 @@ class Trainer:
         if not 0 <= nov <= 16:
             raise ValueError(f"quality_maps.overlay_frames must be 0..16, got {nov}")
         return {"dir": str(qm["dir"]), "cell": cell, "overlay_frames": nov}
+
+    OVERLAY_VIDEO = ("avi", "mjpeg", "jpg")
+    OVERLAY_FPS = 2
+
+    def _overlay_video(self):
+        """yml ``quality_maps: {..., overlay_video: avi | mjpeg | jpg, overlay_quality: 90}``, parsed beside ``_quality_maps``: None, or
+        {"ext", "quality"} — the overlays then leave as Motion-JPEG, ``<dir>/<video_name>.overlay.<ext>`` (an AVI file, a raw stream, a
+        directory of .jpg frames), 2 frames per second, all clips in order and their slices in depth order, and the .npz carries
+        ``overlay_frame_inds`` (n_clips, n_ov), the source frame numbers, instead of ``overlay``"""
+        qm = self.config.get("quality_maps")
+        if not isinstance(qm, dict) or not qm.get("overlay_video"):
+            return None
+        ext, quality = str(qm["overlay_video"]).lower(), int(qm.get("overlay_quality", 90))
+        if ext not in self.OVERLAY_VIDEO:
+            raise ValueError(f"quality_maps.overlay_video must be one of {self.OVERLAY_VIDEO}, got {qm['overlay_video']!r}")
+        if not 1 <= quality <= 100:
+            raise ValueError(f"quality_maps.overlay_quality must be 1..100, got {quality}")
+        if int(qm.get("overlay_frames", 0)) == 0:
+            raise ValueError("quality_maps.overlay_video needs overlay_frames >= 1")
+        return {"ext": ext, "quality": quality}
+
+    def _overlay_tables(self, quality):
+        """the quantiser tables of the overlay video on the device, made once (outside any recording: ``_score_all`` asks first)"""
+        cache = self.__dict__.setdefault("_overlay_qt", {})
+        if quality not in cache:
+            cache[quality] = torch.from_numpy(kernels.jpeg_quant_tables(quality).view(np.int16)).to(self.device).view(torch.uint16)
+        return cache[quality]
+
+    def _overlay_coefficients(self, overlay, ov):
+        """painted overlays uint8 (n_clips, n_ov, 3, Hs, Ws) -> their quantised JPEG coefficients int16 (n_clips, n_ov, coef / 2): one
+        forward-DCT launch per frame (each (3, Hs, Ws) slice is a one-frame R G B source), part of a recorded forward.  The same bytes
+        per pixel as the overlay itself: this is what travels to the host in its place."""
+        n_clips, n_ov, _, Hs, Ws = overlay.shape
+        qt = self._overlay_tables(ov["quality"])
+        coef = torch.empty(n_clips, n_ov, kernels.jpeg_coef_bytes(Hs, Ws) // 2, dtype=torch.int16, device=overlay.device)
+        for b in range(n_clips):
+            for n in range(n_ov):
+                kernels.jpeg_fdct(overlay[b, n].unsqueeze(1), qt, out=coef[b, n].unsqueeze(0))
+        return coef
+
+    @staticmethod
+    def _overlay_size(item, ksvqe):
+        """(Hs, Ws) of the frames a video's overlays were painted on, from its dataset item"""
+        if isinstance(item, dict) and item.get("overlay_size") is not None:
+            return item["overlay_size"]
+        view = item.get("fragment" if ksvqe else "technical") if isinstance(item, dict) else None
+        vids = getattr(view, "videos", None)
+        return tuple(int(v) for v in vids[0].shape[-2:]) if vids else None
 
     @staticmethod
     def overlay_depths(D, n):
@@ -217,8 +267,12 @@ class Trainer:
                 painted = kernels.quality_paint(src, tok, cell=qm["cell"], overlay_depths=depths)
             else:
                 continue
+            ov = self._overlay_video()
             for name, t in zip(("heat", "cover", "overlay"), painted):
-                res[f"{key}/{name}"] = t
+                if name == "overlay" and ov is not None:
+                    res[f"{key}/overlay_coef"] = self._overlay_coefficients(t, ov)
+                else:
+                    res[f"{key}/{name}"] = t
         return res
 
     @staticmethod
@@ -265,15 +319,26 @@ class Trainer:
             if nrx:                              # window index -> (ry, rx) in anchors, (n_clips, T, 2)
                 arrays[f"{key}/regions"] = np.stack(np.divmod(arrays[f"{key}/regions"].astype(np.int32), np.int32(nrx)), -1).astype(np.int32)
         score = np.float32(host["score"]) if "score" in host else host["pred"].float().mean().numpy()
+        os.makedirs(qm["dir"], exist_ok=True)
         for key in keys:
             n_clips, D = arrays[f"{key}/token_map"].shape[:2]
             fi = self._maps_frame_inds(frame_item, n_clips, D)
             if fi is not None:
                 arrays[f"{key}/frame_inds"] = fi
             arrays[f"{key}/score"] = np.asarray(score, np.float32)
+            coef = arrays.pop(f"{key}/overlay_coef", None)
+            if coef is not None:
+                # the overlay video: slice n of a clip shows clip frame 2 depth[n], the first frame of that depth's pair
+                ov, depths = self._overlay_video(), self.overlay_depths(D, coef.shape[1])
+                size = self._overlay_size(frame_item, self.config["model"]["type"] == "KSVQE")
+                stem = os.path.basename(str(name)) + ("" if len(keys) == 1 else "." + key)
+                from .datasets.fusion_datasets import MjpegWriter
+                with MjpegWriter(os.path.join(qm["dir"], f"{stem}.overlay.{ov['ext']}"), self.OVERLAY_FPS, quality=ov["quality"]) as w:
+                    w.write_coefficients(coef.reshape(n_clips * coef.shape[1], -1), *size)
+                arrays[f"{key}/overlay_frame_inds"] = (fi[:, depths, 0] if fi is not None
+                                                       else np.broadcast_to(2 * np.asarray(depths, np.int64), coef.shape[:2]).copy())
         if len(keys) == 1:                       # one model key: no prefix
             arrays = {k.split("/", 1)[1]: v for k, v in arrays.items()}
-        os.makedirs(qm["dir"], exist_ok=True)
         path = os.path.join(qm["dir"], os.path.basename(str(name)) + ".npz")
         tmp = path + ".tmp.npz"
         np.savez(tmp, **arrays)
@@ -334,6 +399,8 @@ class Trainer:
         flags = torch.zeros(len(mine), dtype=torch.int32, device=self.device) if swins else None
         qm = self._quality_maps()
         writer = _MapWriter(self, qm, len(lanes)) if qm is not None else None
+        if qm is not None and self._overlay_video() is not None:
+            self._overlay_tables(self._overlay_video()["quality"])
         for st in lanes:
             for m in swins:
                 m.clear_range_flags(st)

@@ -1,0 +1,56 @@
+"""Write any video ``open_video`` reads — a ``.npy`` frame stack, a ``.y4m`` file, Motion-JPEG in any of its containers — as
+Motion-JPEG, without a codec library (``MjpegWriter``: forward DCT on the device, entropy coding on host threads; without a device the
+scalar twin of the launch, bit-equal).  DST picks the container: ``*.mjpeg`` / ``*.mjpg`` a raw stream, ``*.avi`` RIFF AVI, anything
+else a directory of ``%06d.jpg`` frames.  I420 sources in BT.601 full range are written from their planes as they are (no colour
+round trip); any other I420 format goes through ``to_rgb()``, which needs a device.
+
+    python tools/transcode_mjpeg.py SRC DST [--quality 90] [--fps F] [--restart-interval N] [--yuv-matrix bt601|bt709] [--device cuda|cpu]
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np, torch  # noqa: E401,E402
+import kvq_amd  # noqa: F401,E402
+from kvq_amd import _abi, kernels  # noqa: E402
+from kvq_amd.datasets import fusion_datasets as fd  # noqa: E402
+
+CHUNK = 32      # frames per FDCT launch and D2H copy
+
+
+def transcode(src, dst, quality=90, fps=None, restart_interval=0, yuv_matrix="bt601", device=None):
+    """-> the number of frames written.  ``fps`` None: the source's rate, 30 when it has none."""
+    device = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    vr = fd.open_video(src, yuv_matrix)
+    rate = fps if fps is not None else (getattr(vr, "fps", None) or 30.0)
+    with fd.MjpegWriter(dst, rate, quality=quality, restart_interval=restart_interval) as w:
+        for lo in range(0, len(vr), CHUNK):
+            frames = fd._frames_to_device(vr, np.arange(lo, min(lo + CHUNK, len(vr))), device)
+            if isinstance(frames, kernels.I420Frames):
+                if frames.format != _abi.SRC_I420_BT601_FULL:
+                    frames = frames.to_rgb()
+            else:
+                frames = frames.permute(3, 0, 1, 2).contiguous()          # (n, H, W, 3) -> (3, n, H, W)
+            w.write(frames)
+    return w.frames
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--fps", type=float, default=None)
+    ap.add_argument("--restart-interval", type=int, default=0)
+    ap.add_argument("--yuv-matrix", default="bt601", choices=("bt601", "bt709"))
+    ap.add_argument("--device", default=None, choices=("cuda", "cpu"))
+    a = ap.parse_args()
+    n = transcode(a.src, a.dst, a.quality, a.fps, a.restart_interval, a.yuv_matrix, a.device)
+    size = (sum(os.path.getsize(os.path.join(a.dst, f)) for f in os.listdir(a.dst)) if os.path.isdir(a.dst) else os.path.getsize(a.dst))
+    print(f"{a.dst}: {n} frames, {size} bytes")
+
+
+if __name__ == "__main__":
+    main()
