@@ -700,7 +700,8 @@ int kvq_yuv420_coeffs(int format /* KVQ_SRC_I420_* */, int32_t host_out6[6]);
 int kvq_yuv420_to_rgb(const void* frames, int T, int H, int W, int format, uint8_t* rgb_out, void* stream);
 
 /* Baseline JPEG (Motion-JPEG frames) -> I420 frames of format KVQ_SRC_I420_BT601_FULL, no codec library: the entropy decode on the
- * host (csrc/jpeg.cpp, plain C++, no HIP call), dequantisation + inverse DCT on the device (csrc/jpeg.hip) or by its scalar twin.
+ * host (csrc/jpeg.cpp, plain C++, no HIP call) — or on the device, one lane per restart interval: the block after this one —,
+ * dequantisation + inverse DCT on the device (csrc/jpeg.hip) or by its scalar twin.
  * The hand-over between the two is dense: per frame QUANTISED coefficients as int16, every 8 x 8 block 64 values in natural
  * (de-zigzagged) order, index 8 v + u for vertical frequency v and horizontal frequency u, the blocks de-interleaved from MCU order
  * into per-plane block raster over the MCU-padded planes: with mx = ceil(W / 16), my = ceil(H / 16) the Y blocks (2 my rows of 2 mx),
@@ -742,6 +743,47 @@ int kvq_jpeg_probe(const uint8_t* data, size_t n, KvqJpegInfo* info);
 int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out, size_t coef_cap, uint16_t* qt_out);
 int kvq_jpeg_idct_i420_host(const int16_t* coef, const uint16_t* qt, int T, int H, int W, uint8_t* frames_out);
 int kvq_jpeg_idct_i420(const void* coef, const void* qt, int T, int H, int W, uint8_t* frames_out, void* stream);
+
+/* Baseline JPEG, entropy decode on the device: the COMPRESSED images go up, one lane decodes one SEGMENT — a restart interval, or
+ * the whole scan of a frame without DRI: it starts byte-aligned with the DC predictors at 0 — into the same dense hand-over, to the
+ * bit (csrc/jpeg_huff.hpp is the one definition, shared by the launch and its host twin).  The host only walks markers.
+ *
+ * kvq_jpeg_index (host only, no HIP call) parses the image at data[0 .. n) as kvq_jpeg_probe does (same refusals; `info` is filled
+ * as there), then walks the entropy-coded bytes once: nseg = restart_interval ? ceil(MCUs / restart_interval) : 1 segments, segment s
+ * as seg_out[2 s] = begin, seg_out[2 s + 1] = end, byte offsets relative to `data`, end = the first 0xFF of the marker that closes
+ * it, which must be RST(s & 7), and EOI after the last one: a wrong, missing or surplus marker is KVQ_ERR_SHAPE.  seg_cap = the
+ * capacity of seg_out in segments: a smaller one than nseg is KVQ_ERR_WORKSPACE with only *nseg_out (= nseg) written.  tables_out
+ * receives the frame's table set (from its DHT segments, or Annex K.3 when it has none; identical tables stored once), qt_out the
+ * quantiser tables, uint16 [3][64] natural order.  n < 2^32.  No read leaves data[0 .. n).
+ *
+ * kvq_jpeg_entropy: bytes = nbytes (< 2^32) bytes on the device that hold T images; frames = uint32 [T][5], per frame {byte offset
+ * of its image, its first entry in segs, nseg, restart interval, index of its table set}; segs = uint32 [nsegs][2] as above
+ * (relative to the frame's image); tables = ntables sets -> coef_out = T x kvq_jpeg_coef_bytes(H, W) bytes, which the entry
+ * zero-fills itself on `stream`, and status_out = int32 [nsegs], ONE word per segment (no atomics: the caller reduces): 0, or
+ * cause | MCU << 8 with the MCU of the frame at which the decode stopped and cause 1 bits exhausted, 2 a code in no table, 3 a DC
+ * category above 15, 4 a zero run past coefficient 63, 5 eight or more bits left before the segment's end after its last MCU (the
+ * end is strict: kvq_jpeg_coeffs may accept such a segment, it accepts none that this refuses for another cause), 6 descriptors
+ * that do not fit nbytes / nsegs / ntables / the frame's MCU count (nothing is read through them); -1: the word was never written
+ * (a frame descriptor that does not fit, or nseg = 0: such a frame is skipped).  The coefficients of a segment with status != 0 are
+ * unspecified, inside the frame's own range.  The entry only enqueues (two fills and one launch): no allocation, no
+ * synchronisation, no blocking copy.  kvq_jpeg_entropy_host: the same on host memory, bit-equal in coefficients and status.
+ * T, H, W as kvq_jpeg_idct_i420; coef_out 16-byte aligned, frames / segs / tables / status_out 4-byte aligned, else KVQ_ERR_SHAPE. */
+typedef struct KvqJpegHuffTable {
+  uint16_t look[512];        /* (length << 8) | symbol for the codes of 1..9 bits by their first 9 bits, 0 = a longer code */
+  int32_t mincode[7], maxcode[7], valptr[7];   /* canonical ranges of the lengths 10..16; maxcode -1 = no code of that length */
+  uint8_t vals[256];
+} KvqJpegHuffTable;
+typedef struct KvqJpegTables {
+  int32_t ntab;              /* distinct tables in tab[] */
+  uint8_t dc[4], ac[4];      /* per component (Y, Cb, Cr; the fourth unused): its DC / AC table in tab[] */
+  KvqJpegHuffTable tab[6];
+} KvqJpegTables;
+int kvq_jpeg_index(const uint8_t* data, size_t n, KvqJpegInfo* info, uint32_t* seg_out, size_t seg_cap, size_t* nseg_out,
+                   KvqJpegTables* tables_out, uint16_t* qt_out);
+int kvq_jpeg_entropy_host(const uint8_t* bytes, size_t nbytes, const uint32_t* frames, const uint32_t* segs, size_t nsegs,
+                          const KvqJpegTables* tables, size_t ntables, int T, int H, int W, int16_t* coef_out, int32_t* status_out);
+int kvq_jpeg_entropy(const void* bytes, size_t nbytes, const void* frames, const void* segs, size_t nsegs, const void* tables,
+                     size_t ntables, int T, int H, int W, void* coef_out, void* status_out, void* stream);
 
 /* Baseline JPEG, writing (Motion-JPEG frames): the mirror of the reader.  Colour conversion, chroma averaging, forward DCT and
  * quantisation on the device (csrc/jpeg_enc.hip) or by the scalar twin, the Huffman entropy coder on the host (csrc/jpeg_enc.cpp,

@@ -173,6 +173,18 @@ class KvqJpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("supported", C.c_int32), ("has_dht", C.c_int32), ("frame_bytes", C.c_int64)]
 
 
+class KvqJpegHuffTable(C.Structure):
+    _fields_ = [("look", C.c_uint16 * 512), ("mincode", C.c_int32 * 7), ("maxcode", C.c_int32 * 7), ("valptr", C.c_int32 * 7),
+                ("vals", C.c_uint8 * 256)]
+
+
+class KvqJpegTables(C.Structure):
+    _fields_ = [("ntab", C.c_int32), ("dc", C.c_uint8 * 4), ("ac", C.c_uint8 * 4), ("tab", KvqJpegHuffTable * 6)]
+
+
+JPEG_TABLES_BYTES = C.sizeof(KvqJpegTables)      # 8196: one table set of kvq_jpeg_index / kvq_jpeg_entropy
+
+
 class KvqHeadTrainArgs(C.Structure):
     _fields_ = [("feat", p_void), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32), ("params", p_void),
                 ("p_drop", C.c_float), ("seed", C.c_uint32), ("step", C.c_uint32), ("workspace", p_void), ("workspace_bytes", C.c_size_t),
@@ -313,6 +325,9 @@ SYMBOLS = {
     "kvq_jpeg_coeffs": (i32, [p_void, sz, p_void, sz, p_void]),
     "kvq_jpeg_idct_i420_host": (i32, [p_void, p_void, i32, i32, i32, p_void]),
     "kvq_jpeg_idct_i420": (i32, [p_void, p_void, i32, i32, i32, p_void, p_void]),
+    "kvq_jpeg_index": (i32, [p_void, sz, C.POINTER(KvqJpegInfo), p_void, sz, C.POINTER(sz), p_void, p_void]),
+    "kvq_jpeg_entropy_host": (i32, [p_void, sz, p_void, p_void, sz, p_void, sz, i32, i32, i32, p_void, p_void]),
+    "kvq_jpeg_entropy": (i32, [p_void, sz, p_void, p_void, sz, p_void, sz, i32, i32, i32, p_void, p_void, p_void]),
     "kvq_jpeg_quant_tables": (i32, [i32, p_void]),
     "kvq_jpeg_quantise_host": (i32, [p_void, sz, i32, p_void]),
     "kvq_jpeg_fdct_host": (i32, [p_void, i32, i32, i32, i32, p_void, p_void]),

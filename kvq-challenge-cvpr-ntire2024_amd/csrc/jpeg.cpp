@@ -1,6 +1,7 @@
 // Host half of the Motion-JPEG reader (include/kvq_hip.h, "Baseline JPEG"): segment walk (kvq_jpeg_probe), baseline Huffman entropy
-// decode into the dense int16 coefficient hand-over (kvq_jpeg_coeffs) and the scalar twin of the IDCT launch
-// (kvq_jpeg_idct_i420_host).  Plain C++17: no HIP call and no HIP header, so the file also compiles with the host compiler alone
+// decode into the dense int16 coefficient hand-over (kvq_jpeg_coeffs), the scalar twin of the IDCT launch
+// (kvq_jpeg_idct_i420_host), and for the entropy decode on the device the segment index (kvq_jpeg_index: the marker walk and the
+// table sets) and the launch's host twin (kvq_jpeg_entropy_host, from csrc/jpeg_huff.hpp).  Plain C++17: no HIP call and no HIP header, so the file also compiles with the host compiler alone
 // (tools/jpeg_hostcheck.cpp builds it under the address and undefined-behaviour sanitizers).  Every read of the stream goes through
 // a bounds check against n; every coefficient is written at an index computed from the frame's own geometry, inside the
 // kvq_jpeg_coef_bytes(H, W) that coef_cap was checked against.
@@ -10,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/kvq_hip.h"
+#include "jpeg_huff.hpp"
 #include "jpeg_idct.hpp"
 #include "jpeg_tables.hpp"
 
@@ -388,6 +390,136 @@ extern "C" int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out,
     if (got < 0) set_error("kvq_jpeg_coeffs: missing EOI after the last MCU (the stream is truncated)");
     else set_error("kvq_jpeg_coeffs: marker FF%02X after the last MCU where EOI belongs", got);
     return KVQ_ERR_SHAPE;
+  }
+  return KVQ_OK;
+}
+
+// ---- entropy decode on the device: the host's share ---------------------------------------------------------------------------------
+namespace {
+
+void huff_export(const Huff& h, KvqJpegHuffTable& t) {
+  memset(&t, 0, sizeof(t));
+  memcpy(t.look, h.look, sizeof(t.look));
+  for (int l = 10; l <= 16; ++l) {
+    t.mincode[l - 10] = h.mincode[l]; t.maxcode[l - 10] = h.maxcode[l]; t.valptr[l - 10] = h.valptr[l];
+  }
+  memcpy(t.vals, h.vals, sizeof(t.vals));
+}
+
+// `t` into the set unless an identical table is there: its index
+int tables_add(KvqJpegTables& set, const KvqJpegHuffTable& t) {
+  for (int i = 0; i < set.ntab; ++i)
+    if (memcmp(&set.tab[i], &t, sizeof(t)) == 0) return i;
+  set.tab[set.ntab] = t;
+  return set.ntab++;
+}
+
+}  // namespace
+
+extern "C" int kvq_jpeg_index(const uint8_t* data, size_t n, KvqJpegInfo* info, uint32_t* seg_out, size_t seg_cap, size_t* nseg_out,
+                              KvqJpegTables* tables_out, uint16_t* qt_out) {
+  using namespace kvq;
+  JPEG_REQUIRE(data && info && seg_out && nseg_out && tables_out && qt_out, KVQ_ERR_NULL, "kvq_jpeg_index: NULL pointer");
+  static thread_local Parsed p;
+  static thread_local Huff std_tab[4];                       // Annex K: DC lum, DC chroma, AC lum, AC chroma
+  const int rc = parse(data, n, p, "kvq_jpeg_index");
+  *info = p.info;
+  if (rc) return rc;
+  const int H = p.info.height, W = p.info.width;
+  JPEG_REQUIRE(jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_index: frame of %d x %d", W, H);
+  JPEG_REQUIRE(n < ((size_t)1 << 32), KVQ_ERR_SHAPE, "kvq_jpeg_index: an image of %zu bytes (offsets are 32-bit)", n);
+  const JpegGeom g = jpeg_geom(H, W);
+  const uint32_t ri = (uint32_t)p.info.restart_interval;
+  const size_t nseg = jpeg_expected_segments(ri, g);
+  *nseg_out = nseg;
+  JPEG_REQUIRE(seg_cap >= nseg, KVQ_ERR_WORKSPACE, "kvq_jpeg_index: seg_out holds %zu segments, the frame has %zu", seg_cap, nseg);
+  const Huff* dc[3];
+  const Huff* ac[3];
+  if (!p.info.has_dht && !std_tab[0].present) {
+    huff_build(std_tab[0], STD_DC_LUM_BITS, STD_DC_VALS, 12);
+    huff_build(std_tab[1], STD_DC_CHR_BITS, STD_DC_VALS, 12);
+    huff_build(std_tab[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS, 162);
+    huff_build(std_tab[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS, 162);
+  }
+  for (int c = 0; c < 3; ++c) {
+    JPEG_REQUIRE(p.qt_present[p.comp[c].tq], KVQ_ERR_SHAPE, "kvq_jpeg_index: quantiser table %d of component %d is not defined", p.comp[c].tq, c);
+    if (p.info.has_dht) {
+      dc[c] = &p.dc[p.comp[c].td]; ac[c] = &p.ac[p.comp[c].ta];
+      JPEG_REQUIRE(dc[c]->present && ac[c]->present, KVQ_ERR_SHAPE, "kvq_jpeg_index: Huffman table %d/%d of component %d is not defined",
+                   p.comp[c].td, p.comp[c].ta, c);
+    } else {
+      dc[c] = &std_tab[p.comp[c].td ? 1 : 0]; ac[c] = &std_tab[p.comp[c].ta ? 3 : 2];
+    }
+  }
+  // the marker walk: every 0xFF that no 0x00 follows closes a segment
+  size_t pos = p.scan;
+  for (size_t s = 0; s < nseg; ++s) {
+    const size_t begin = pos;
+    size_t end = n;
+    while (pos < n) {
+      const uint8_t* f = (const uint8_t*)memchr(data + pos, 0xFF, n - pos);
+      if (!f) break;
+      const size_t q = (size_t)(f - data);
+      if (q + 1 < n && data[q + 1] == 0x00) { pos = q + 2; continue; }
+      end = q;
+      break;
+    }
+    const bool last = s + 1 == nseg;
+    const int want = last ? 0xD9 : 0xD0 + (int)(s & 7);
+    const long mcu = (long)(s + 1) * (long)ri;
+    int got = -1;
+    size_t after = end;
+    if (!read_marker(data, n, after, got)) {
+      if (last) set_error("kvq_jpeg_index: missing EOI after the last MCU (the stream is truncated)");
+      else set_error("kvq_jpeg_index: missing RST%d before MCU %ld (the stream is truncated or has no marker there)", want - 0xD0, mcu);
+      return KVQ_ERR_SHAPE;
+    }
+    if (got != want) {
+      if (last) set_error("kvq_jpeg_index: marker FF%02X after the last MCU where EOI belongs", got);
+      else set_error("kvq_jpeg_index: wrong restart marker FF%02X before MCU %ld, expected RST%d", got, mcu, want - 0xD0);
+      return KVQ_ERR_SHAPE;
+    }
+    seg_out[2 * s] = (uint32_t)begin;
+    seg_out[2 * s + 1] = (uint32_t)end;
+    pos = after;
+  }
+  memset(tables_out, 0, sizeof(*tables_out));
+  KvqJpegHuffTable t;
+  for (int c = 0; c < 3; ++c) {
+    huff_export(*dc[c], t);
+    tables_out->dc[c] = (uint8_t)tables_add(*tables_out, t);
+    huff_export(*ac[c], t);
+    tables_out->ac[c] = (uint8_t)tables_add(*tables_out, t);
+    for (int i = 0; i < 64; ++i) qt_out[64 * c + i] = p.qt[p.comp[c].tq][i];
+  }
+  return KVQ_OK;
+}
+
+extern "C" int kvq_jpeg_entropy_host(const uint8_t* bytes, size_t nbytes, const uint32_t* frames, const uint32_t* segs, size_t nsegs,
+                                     const KvqJpegTables* tables, size_t ntables, int T, int H, int W, int16_t* coef_out, int32_t* status_out) {
+  using namespace kvq;
+  JPEG_REQUIRE(bytes && frames && segs && tables && coef_out && status_out, KVQ_ERR_NULL, "kvq_jpeg_entropy_host: NULL pointer");
+  JPEG_REQUIRE(T > 0 && T < 65536 && jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_entropy_host: %d frames of %dx%d", T, H, W);
+  JPEG_REQUIRE(nbytes < ((size_t)1 << 32) && nsegs < ((size_t)1 << 32) && ntables > 0 && ntables < ((size_t)1 << 32), KVQ_ERR_SHAPE,
+               "kvq_jpeg_entropy_host: %zu bytes, %zu segments, %zu table sets", nbytes, nsegs, ntables);
+  const JpegGeom g = jpeg_geom(H, W);
+  memset(coef_out, 0, (size_t)T * g.blocks * 64 * sizeof(int16_t));
+  for (size_t i = 0; i < nsegs; ++i) status_out[i] = JPEG_ST_UNWRITTEN;
+  for (int t = 0; t < T; ++t) {
+    const uint32_t* f = frames + 5 * (size_t)t;
+    if (f[2] == 0 || f[1] > nsegs || f[2] > nsegs - f[1]) continue;
+    const bool frame_ok = jpeg_frame_ok(f, nbytes, (uint32_t)nsegs, (uint32_t)ntables, g) && jpeg_tables_ok(tables + f[4]);
+    for (uint32_t s = 0; s < f[2]; ++s) {
+      const uint32_t* sg = segs + 2 * ((size_t)f[1] + s);
+      int32_t st = jpeg_status(JPEG_ST_BAD_SEGMENT, 0);
+      if (frame_ok && jpeg_segment_ok(f, sg, nbytes)) {
+        const uint32_t first = f[3] ? s * f[3] : 0u;                // < g.nc: s < nseg = ceil(nc / ri)
+        const uint32_t left = (uint32_t)g.nc - first;
+        st = jpeg_huff_segment(bytes + f[0], sg[0], sg[1], tables + f[4], (int)first, (int)(f[3] && f[3] < left ? f[3] : left), g,
+                               coef_out + (size_t)t * g.blocks * 64);
+      }
+      status_out[f[1] + s] = st;
+    }
   }
   return KVQ_OK;
 }

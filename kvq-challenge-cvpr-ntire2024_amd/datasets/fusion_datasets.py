@@ -432,7 +432,9 @@ class MjpegFrameReader:
 
     ``len(reader)`` frames; ``reader[i]`` -> uint8 RGB (H, W, 3) on the host (entropy decode, the scalar twin of the IDCT launch,
     ``yuv420_to_rgb_host``); ``read_jpeg_into(indices, coef_out, qt_out)`` -> the quantised coefficients and quantiser tables
-    ``kernels.jpeg_idct_i420`` takes.  ``H``, ``W``, ``fps``, ``format``, ``frame_bytes`` as ``Y4mFrameReader``."""
+    ``kernels.jpeg_idct_i420`` takes; ``read_jpeg_bytes_into`` -> the compressed images and their segment index, what
+    ``kernels.jpeg_entropy`` takes; ``restart_intervals``: per frame the MCUs between RSTn markers (0 = none), from the probe at open.
+    ``H``, ``W``, ``fps``, ``format``, ``frame_bytes`` as ``Y4mFrameReader``."""
 
     def __init__(self, path):
         from .._abi import SRC_I420_BT601_FULL
@@ -463,6 +465,7 @@ class MjpegFrameReader:
                 self._index.append((path, pos, int(info.frame_bytes)))
                 pos += int(info.frame_bytes)
         self.H = self.W = None
+        self.restart_intervals = np.zeros(len(self._index), np.int64)      # per frame, MCUs between RSTn markers, 0 = none
         for i in range(len(self._index)):
             if self._index[i][2] == 0:
                 raise ValueError(f"{self._index[i][0]}: frame {i}: the file is empty")
@@ -475,6 +478,7 @@ class MjpegFrameReader:
                 raise ValueError(f"{self._index[i][0]}: frame {i}: {msg}")
             if self.H is None:
                 self.H, self.W = int(info.height), int(info.width)
+            self.restart_intervals[i] = int(info.restart_interval)
         self.frame_bytes = kernels.i420_frame_bytes(self.H, self.W)
         self.coef_bytes = kernels.jpeg_coef_bytes(self.H, self.W)
         self._coeffs = None
@@ -487,6 +491,16 @@ class MjpegFrameReader:
     def _frame(self, i):
         return self._bytes(*self._index[int(i)])
 
+    def _mapped(self, file, off, n):
+        """as ``_bytes`` for the copy into staging: a stream or an AVI file is mapped ONCE per reader (slices of a read-only mapping
+        are safe from any thread; a mapping per frame costs as much host time as indexing the frame), a directory's files one by one"""
+        if file != self.path:
+            return self._bytes(file, off, n)
+        whole = self.__dict__.get("_whole")
+        if whole is None:
+            whole = self._whole = np.memmap(file, dtype=np.uint8, mode="r")
+        return whole[off:off + n]
+
     def __len__(self):
         return len(self._index)
 
@@ -498,6 +512,26 @@ class MjpegFrameReader:
             rc, msg = kernels.jpeg_coeffs(self._bytes(file, off, n), coef_out[j], qt_out[j])
             if rc:
                 raise ValueError(f"{file}: frame {int(i)}: {msg}")
+
+    def segment_counts(self, indices):
+        """per frame of ``indices`` the segments ``kvq_jpeg_index`` finds: one per restart interval, one for a frame without DRI"""
+        ri = self.restart_intervals[np.asarray(indices, np.int64)]
+        nc = self.coef_bytes // 768
+        return np.where(ri > 0, -(-nc // np.maximum(ri, 1)), 1).astype(np.int64)
+
+    def read_jpeg_bytes_into(self, indices, data_out, offsets, desc_out, segs_out, seg_offsets, tables_out, qt_out):
+        """frames[indices] as they are, for the entropy decode on the device: the image of frame j copied to ``data_out[offsets[j]:]``
+        (uint8), its segment index to ``segs_out[seg_offsets[j]:]`` (uint32 (n, 2), ``segment_counts`` entries), its table set to
+        ``tables_out[j]`` (uint8 (JPEG_TABLES_BYTES,)), its quantiser tables to ``qt_out[j]`` and ``desc_out[j]`` = {offset, first
+        segment, nseg, restart interval, 0}; host numpy views (pinned staging); the library call releases the GIL.  A frame the
+        index refuses gets nseg = 0: the launch skips it and the caller hands it to ``kvq_jpeg_coeffs``, whose verdict counts."""
+        for j, i in enumerate(indices):
+            file, off, n = self._index[int(i)]
+            dst = data_out[int(offsets[j]):int(offsets[j]) + n]
+            dst[...] = self._mapped(file, off, n)
+            s0, cap = int(seg_offsets[j]), int(seg_offsets[j + 1] - seg_offsets[j])
+            rc, info, nseg, _ = kernels.jpeg_index(dst, segs_out[s0:s0 + cap], tables_out[j], qt_out[j])
+            desc_out[j] = (int(offsets[j]), s0, nseg if rc == 0 and nseg == cap else 0, int(self.restart_intervals[int(i)]), 0)
 
     def i420(self, i):
         """frame i as its I420 bytes (frame_bytes,), decoded on the host"""
@@ -664,15 +698,16 @@ _COPY_POOL = None
 _COPY_THREADS = 4
 
 
-def _frames_to_device(vr, uniq, device):
+def _frames_to_device(vr, uniq, device, entropy=None):
     """The sampled frames ``uniq`` of a reader -> ONE uint8 (n, H, W, 3) device tensor: gathered into pinned staging memory
     by a few host threads (numpy copies release the GIL), then a single asynchronous H2D copy on the current stream.
     A reader of I420 frames (``read_i420_into``: ``Y4mFrameReader``) stages its payload as it is — 1.5 B/pixel through the gather
     and the copy instead of 3 — and the result is a ``kernels.I420Frames`` (n, frame_bytes).
-    A Motion-JPEG reader (``read_jpeg_into``: ``MjpegFrameReader``) goes through ``_jpeg_frames_to_device``."""
+    A Motion-JPEG reader (``read_jpeg_into``: ``MjpegFrameReader``) goes through ``_jpeg_frames_to_device``; ``entropy`` ("auto" |
+    "host" | "device", None: the module's ``JPEG_ENTROPY``) says where its frames are entropy-decoded and applies to no other reader."""
     global _COPY_POOL
     if hasattr(vr, "read_jpeg_into"):
-        return _jpeg_frames_to_device(vr, uniq, device)
+        return _jpeg_frames_to_device(vr, uniq, device, entropy)
     i420 = hasattr(vr, "read_i420_into")
     if i420:
         first, read = None, vr.read_i420_into
@@ -717,11 +752,34 @@ def _copy_pool():
     return _COPY_POOL
 
 
-def _jpeg_frames_to_device(vr, uniq, device):
-    """The sampled frames of a Motion-JPEG reader -> ``kernels.I420Frames``: the host threads of the copy pool entropy-decode them
-    into pinned staging (quantised int16 coefficients, 3 B/pixel, then the quantiser tables; the library calls release the GIL), ONE
-    asynchronous H2D copy carries both, ONE ``jpeg_idct_i420`` launch on the current stream reconstructs the frames.  Without a
-    device the scalar twin of the launch runs instead (bit-equal)."""
+JPEG_ENTROPY = "auto"                                    # the default of ``_frames_to_device(..., jpeg_entropy=None)``
+JPEG_ENTROPY_MODES = ("auto", "host", "device")
+# what "auto" may choose for a GPU target when every frame of the call has a restart interval: README.md, "Motion-JPEG input"
+_JPEG_ENTROPY_AUTO_DEVICE = True
+
+
+def jpeg_entropy_mode(value=None):
+    """``value`` (None: the module default ``JPEG_ENTROPY``) as one of "auto" | "host" | "device", else a ValueError naming the three"""
+    value = JPEG_ENTROPY if value is None else value
+    if value not in JPEG_ENTROPY_MODES:
+        raise ValueError(f"jpeg_entropy must be one of 'auto', 'host', 'device', got {value!r}")
+    return value
+
+
+def _jpeg_frames_to_device(vr, uniq, device, entropy=None):
+    """The sampled frames of a Motion-JPEG reader -> ``kernels.I420Frames``.  ``entropy`` (None: ``JPEG_ENTROPY``):
+      "host"    the host threads of the copy pool entropy-decode the frames into pinned staging (quantised int16 coefficients,
+                3 B/pixel, then the quantiser tables; the library calls release the GIL), ONE asynchronous H2D copy carries both, ONE
+                ``jpeg_idct_i420`` launch on the current stream reconstructs the frames.  Without a device the scalar twin of the
+                launch runs instead (bit-equal).
+      "device"  ``_jpeg_frames_entropy_on_device``: the compressed bytes go up and ``jpeg_entropy`` decodes them
+      "auto"    "device" for a GPU target when every frame of the call has a restart interval, "host" otherwise"""
+    entropy = jpeg_entropy_mode(entropy)
+    on_gpu = torch.device(device).type == "cuda"
+    if entropy == "auto":
+        entropy = "device" if _JPEG_ENTROPY_AUTO_DEVICE and on_gpu and bool((vr.restart_intervals[np.asarray(uniq, np.int64)] > 0).all()) else "host"
+    if entropy == "device":
+        return _jpeg_frames_entropy_on_device(vr, uniq, device)
     n, cb = len(uniq), vr.coef_bytes
     nbytes = n * (cb + 384)                              # cb is a multiple of 768: the tables start 16-byte aligned
     st, k = _Staging.get(nbytes)
@@ -733,13 +791,109 @@ def _jpeg_frames_to_device(vr, uniq, device):
     jobs = [_copy_pool().submit(vr.read_jpeg_into, uniq[a:b], coef[a:b], qt[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
     for j in jobs:
         j.result()
-    if torch.device(device).type != "cuda":
+    if not on_gpu:
         return kernels.I420Frames(torch.from_numpy(kernels.jpeg_idct_i420_host(coef, qt, vr.H, vr.W)), vr.H, vr.W, vr.format)
     dev = stage.to(device, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev.device))
     st["ev"][k] = ev
     return kernels.jpeg_idct_i420(dev[:n * cb].view(torch.int16).view(n, cb // 2), dev[n * cb:].view(torch.uint16).view(n, 3, 64), vr.H, vr.W)
+
+
+class _StatusStaging:
+    """a small pinned buffer per thread for the status words of ``jpeg_entropy`` (its D2H copy is waited for before the call returns)"""
+    _local = threading.local()
+
+    @classmethod
+    def get(cls, n):
+        buf = getattr(cls._local, "buf", None)
+        if buf is None or buf.numel() < n:
+            buf = cls._local.buf = torch.empty(max(1024, int(n * 1.25)), dtype=torch.int32).pin_memory()
+        return buf[:n]
+
+
+def _jpeg_frames_entropy_on_device(vr, uniq, device):
+    """``_jpeg_frames_to_device`` with the entropy decode on the device.  The copy pool's threads copy the COMPRESSED images into pinned
+    staging and index their segments (``read_jpeg_bytes_into``: a marker walk, no decode); identical table sets are kept once; ONE
+    H2D copy carries quantiser tables, descriptors, segments, bytes and table sets; ``jpeg_entropy`` decodes every restart interval
+    (a frame without DRI: one segment) in one lane; ONE small D2H copy brings the status words back behind an event this function
+    waits for.  Every frame with a status other than 0 — and every frame the index refused — is decoded again by
+    ``kvq_jpeg_coeffs`` on the host, whose verdict is final: an error is the ValueError of the host path, a success sends that frame's
+    coefficients up in place of the device's.  The unchanged ``jpeg_idct_i420`` launch follows.  Without a device the host twins of
+    both launches run (bit-equal)."""
+    n, cb, TB = len(uniq), vr.coef_bytes, kernels.JPEG_TABLES_BYTES
+    sizes = np.array([vr._index[int(i)][2] for i in uniq], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    seg_offsets = np.concatenate([[0], np.cumsum(vr.segment_counts(uniq))])
+    nseg, ndata = int(seg_offsets[-1]), int(offsets[-1])
+    o_desc = n * 384
+    o_segs = o_desc + n * 20
+    o_data = o_segs + nseg * 8
+    o_tab = -(-(o_data + ndata) // 4) * 4
+    nbytes = o_tab + n * TB                              # room for one table set per frame; what is used goes up
+    if o_tab >= 1 << 32:
+        raise ValueError(f"{vr.path}: {n} frames of {ndata} compressed bytes in one call (the offsets are 32-bit)")
+    st, k = _Staging.get(nbytes)
+    stage = st["buf"][k][:nbytes]
+    host = stage.numpy()
+    qt, desc = host[:o_desc].view(np.uint16).reshape(n, 3, 64), host[o_desc:o_segs].view(np.uint32).reshape(n, 5)
+    segs, data = host[o_segs:o_data].view(np.uint32).reshape(nseg, 2), host[o_data:o_data + ndata]
+    host[o_data + ndata:o_tab] = 0
+    tables = np.empty((n, TB), np.uint8)
+    nt = max(1, min(_COPY_THREADS, n))
+    bounds = np.linspace(0, n, nt + 1).astype(int)
+    jobs = [_copy_pool().submit(vr.read_jpeg_bytes_into, uniq[a:b], data, offsets[a:b], desc[a:b], segs, seg_offsets[a:b + 1], tables[a:b],
+                                qt[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+    for j in jobs:
+        j.result()
+    sets, seen = host[o_tab:].reshape(n, TB), {}
+    for j in range(n):
+        if desc[j, 2]:
+            key = tables[j].tobytes()
+            if key not in seen:
+                seen[key] = len(seen)
+                sets[seen[key]] = tables[j]
+            desc[j, 4] = seen[key]
+    nsets = max(1, len(seen))
+    if not seen:
+        sets[0] = 0
+    used = o_tab + nsets * TB
+    on_gpu = torch.device(device).type == "cuda"
+
+    def redo(status):
+        """(frame numbers to decode on the host, their coefficients): the index refused them or a segment's status is not 0"""
+        bad = [j for j in range(n) if desc[j, 2] == 0 or status[seg_offsets[j]:seg_offsets[j + 1]].any()]
+        coef = np.empty((len(bad), cb // 2), np.int16)
+        for r, j in enumerate(bad):
+            file, off, nb = vr._index[int(uniq[j])]
+            rc, msg = kernels.jpeg_coeffs(vr._bytes(file, off, nb), coef[r], qt[j])
+            if rc:
+                raise ValueError(f"{file}: frame {int(uniq[j])}: {msg}")
+        return bad, coef
+
+    if not on_gpu:
+        coef, status = kernels.jpeg_entropy_host(data, desc, segs, np.ascontiguousarray(sets[:nsets]), n, vr.H, vr.W)
+        bad, again = redo(status)
+        coef[bad] = again
+        return kernels.I420Frames(torch.from_numpy(kernels.jpeg_idct_i420_host(coef, qt.copy(), vr.H, vr.W)), vr.H, vr.W, vr.format)
+    dev = stage[:used].to(device, non_blocking=True)
+    stream = torch.cuda.current_stream(dev.device)
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    st["ev"][k] = ev
+    coef, status = kernels.jpeg_entropy(dev[o_data:o_data + ndata], dev[o_desc:o_segs].view(torch.int32).view(n, 5),
+                                        dev[o_segs:o_data].view(torch.int32).view(nseg, 2), dev[o_tab:used].view(nsets, TB), n, vr.H, vr.W)
+    back = _StatusStaging.get(nseg)
+    back.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(stream)
+    done.synchronize()                                   # the wait is here, not inside the library
+    bad, again = redo(back.numpy())
+    dqt = dev[:o_desc].view(torch.uint16).view(n, 3, 64)
+    if bad:                                              # rare: pageable copies, ordered on the stream behind the entropy launch
+        coef[torch.tensor(bad, device=dev.device)] = torch.from_numpy(again).to(dev.device)
+        dqt = torch.from_numpy(qt.copy().view(np.int16)).to(dev.device).view(torch.uint16)
+    return kernels.jpeg_idct_i420(coef, dqt, vr.H, vr.W)
 
 
 class MjpegWriter:
@@ -885,7 +1039,7 @@ class MjpegWriter:
         self._file.close()
 
 
-def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601"):
+def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601", jpeg_entropy=None):
     """Reference ``spatial_temporal_view_decomposition`` (:376-397), decode half: one reader, every frame fetched once and
     sent to the device once, as uint8; per view a uint8 (3, T, H, W) device tensor (frame gather + layout change in HBM) +
     the sampled indices.  I420 frames (a ``.y4m`` file): per view a ``kernels.I420Frames`` — a gather of whole frames, no
@@ -893,7 +1047,7 @@ def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601"):
     vr = open_video(path, yuv_matrix)
     frame_inds = {k: s(len(vr), is_train) for k, s in samplers.items()}
     uniq = np.unique(np.concatenate(list(frame_inds.values()), 0))
-    frames = _frames_to_device(vr, uniq, device)                               # (n, H, W, 3) uint8
+    frames = _frames_to_device(vr, uniq, device, jpeg_entropy)                 # (n, H, W, 3) uint8
     video = {}
     for k, inds in frame_inds.items():
         pos = torch.from_numpy(np.searchsorted(uniq, inds).astype(np.int64)).to(frames.device)
@@ -932,6 +1086,8 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
         import os.path as osp
         super().__init__()
         self.opt, self.namelist, self.device = opt, namelist, _default_device(device)
+        if opt.get("jpeg_entropy") is not None:          # yml data.<split>.args.jpeg_entropy: refused here, not at the first item
+            jpeg_entropy_mode(opt["jpeg_entropy"])
         self.ann_file, self.data_prefix, self.data_prefix_3D = opt["anno_file"], opt["data_prefix"], opt["data_prefix_3D"]
         self.sample_types, self.feature_type, self.phase = opt["sample_types"], opt["feature_type"], opt["phase"]
         self.augment = opt.get("augment", False)
@@ -968,7 +1124,8 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
     def __getitem__(self, index):
         info = self.video_infos[index]
         feat = self._features(info["video_name"])
-        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"))
+        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"),
+                                            self.opt.get("jpeg_entropy"))
         data = {}
         for stype, sopt in self.sample_types.items():
             kw = dict(sopt, phase="test")
@@ -996,6 +1153,8 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
         import os.path as osp
         super().__init__()
         self.opt, self.namelist, self.device = opt, namelist, _default_device(device)
+        if opt.get("jpeg_entropy") is not None:          # yml data.<split>.args.jpeg_entropy: refused here, not at the first item
+            jpeg_entropy_mode(opt["jpeg_entropy"])
         self.ann_file, self.data_prefix = opt["anno_file"], opt["data_prefix"]
         self.sample_types, self.phase = opt["sample_types"], opt["phase"]
         self.augment = opt.get("augment", False)
@@ -1028,7 +1187,8 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
             np.random.seed(1234 + index)
             _pyrandom.seed(1234 + index)
             torch.manual_seed(1234 + index)
-        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"))
+        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"),
+                                            self.opt.get("jpeg_entropy"))
         data, k = {}, None
         resize = ori = None
         for stype, sopt in self.sample_types.items():       # order of the reference's three calls per view (:455-459)

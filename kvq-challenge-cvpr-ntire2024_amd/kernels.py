@@ -472,6 +472,58 @@ def jpeg_idct_i420(coef: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Op
     return I420Frames(out, H, W, _abi.SRC_I420_BT601_FULL)
 
 
+JPEG_TABLES_BYTES = _abi.JPEG_TABLES_BYTES
+
+
+def jpeg_index(buf, seg_out, tables_out, qt_out):
+    """``kvq_jpeg_index`` (host only): the image in the uint8 numpy array ``buf`` -> its segments in ``seg_out`` uint32 (cap, 2)
+    (byte ranges relative to ``buf``), its table set in ``tables_out`` uint8 (JPEG_TABLES_BYTES,), its quantiser tables in ``qt_out``
+    uint16 (3, 64) -> (status, ``_abi.KvqJpegInfo``, nseg, message).  The call releases the GIL."""
+    import numpy as np
+    info, nseg = _abi.KvqJpegInfo(), C.c_size_t(0)
+    assert seg_out.dtype == np.uint32 and seg_out.flags.c_contiguous and tables_out.nbytes == JPEG_TABLES_BYTES and qt_out.nbytes == 384
+    rc = lib().kvq_jpeg_index(buf.ctypes.data, buf.size, C.byref(info), seg_out.ctypes.data, seg_out.size // 2, C.byref(nseg),
+                              tables_out.ctypes.data, qt_out.ctypes.data)
+    return rc, info, int(nseg.value), (lib().kvq_last_error().decode() if rc else "")
+
+
+def jpeg_entropy_host(data, frames, segs, tables, T: int, H: int, W: int):
+    """the host twin of ``jpeg_entropy`` on numpy arrays (``kvq_jpeg_entropy_host``): data uint8 (nbytes,), frames uint32 (T, 5), segs
+    uint32 (nsegs, 2), tables uint8 (ntables, JPEG_TABLES_BYTES) -> (coef int16 (T, jpeg_coef_bytes / 2), status int32 (nsegs,))"""
+    import numpy as np
+    assert data.dtype == np.uint8 and frames.dtype == np.uint32 and segs.dtype == np.uint32 and tables.dtype == np.uint8
+    assert all(a.flags.c_contiguous for a in (data, frames, segs, tables)) and frames.shape == (T, 5)
+    assert segs.ndim == 2 and segs.shape[1] == 2 and tables.ndim == 2 and tables.shape[1] == JPEG_TABLES_BYTES
+    coef = np.empty((T, jpeg_coef_bytes(H, W) // 2), np.int16)
+    status = np.empty(segs.shape[0], np.int32)
+    check(lib().kvq_jpeg_entropy_host(data.ctypes.data, data.size, frames.ctypes.data, segs.ctypes.data, segs.shape[0], tables.ctypes.data,
+                                      tables.shape[0], int(T), int(H), int(W), coef.ctypes.data, status.ctypes.data), "kvq_jpeg_entropy_host")
+    return coef, status
+
+
+def jpeg_entropy(data: torch.Tensor, frames: torch.Tensor, segs: torch.Tensor, tables: torch.Tensor, T: int, H: int, W: int,
+                 coef: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """Compressed baseline-JPEG frames -> their quantised coefficients, one launch, one lane per restart interval
+    (``kvq_jpeg_entropy``).  data uint8 (nbytes,): the images; frames int32 (T, 5): per frame {byte offset, first segment, nseg, restart
+    interval, table set}; segs int32 (nsegs, 2): byte ranges relative to the frame's image; tables uint8 (ntables, JPEG_TABLES_BYTES);
+    all on the device (the int32 tensors carry uint32 values) -> (coef int16 (T, jpeg_coef_bytes / 2), zero-filled by the entry,
+    status int32 (nsegs,): 0 = the segment decoded).  Only enqueues: the caller reads ``status`` after the stream has reached it."""
+    _need_gpu(data, frames, segs, tables, coef, status)
+    assert data.dtype == torch.uint8 and frames.dtype == torch.int32 and segs.dtype == torch.int32 and tables.dtype == torch.uint8
+    assert all(a.is_contiguous() for a in (data, frames, segs, tables)) and tuple(frames.shape) == (T, 5)
+    assert segs.dim() == 2 and segs.shape[1] == 2 and tables.dim() == 2 and tables.shape[1] == JPEG_TABLES_BYTES
+    n = jpeg_coef_bytes(H, W) // 2
+    if coef is None:
+        coef = torch.empty(T, n, dtype=torch.int16, device=data.device)
+    if status is None:
+        status = torch.empty(segs.shape[0], dtype=torch.int32, device=data.device)
+    assert coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() == T * n
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == segs.shape[0]
+    check(lib().kvq_jpeg_entropy(ptr(data), data.numel(), ptr(frames), ptr(segs), segs.shape[0], ptr(tables), tables.shape[0], int(T), int(H),
+                                 int(W), ptr(coef), ptr(status), stream_of(data)), "kvq_jpeg_entropy")
+    return coef, status
+
+
 def jpeg_quant_tables(quality: int):
     """uint16 (3, 64) numpy: the Y, Cb, Cr quantiser tables of an IJG quality 1..100, natural order (``kvq_jpeg_quant_tables``)"""
     import numpy as np

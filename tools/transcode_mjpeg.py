@@ -4,7 +4,10 @@ scalar twin of the launch, bit-equal).  DST picks the container: ``*.mjpeg`` / `
 else a directory of ``%06d.jpg`` frames.  I420 sources in BT.601 full range are written from their planes as they are (no colour
 round trip); any other I420 format goes through ``to_rgb()``, which needs a device.
 
-    python tools/transcode_mjpeg.py SRC DST [--quality 90] [--fps F] [--restart-interval N] [--yuv-matrix bt601|bt709] [--device cuda|cpu]
+``--restart-interval row`` writes one restart interval per MCU row (ceil(W / 16) MCUs): the setting for datasets meant to be read
+back at speed, since the reader entropy-decodes the restart intervals of a frame in parallel on the device (README.md).
+
+    python tools/transcode_mjpeg.py SRC DST [--quality 90] [--fps F] [--restart-interval N|row] [--yuv-matrix bt601|bt709] [--device cuda|cpu]
 """
 import argparse
 import os
@@ -20,10 +23,21 @@ from kvq_amd.datasets import fusion_datasets as fd  # noqa: E402
 CHUNK = 32      # frames per FDCT launch and D2H copy
 
 
+def restart_mcus(value, W):
+    """``--restart-interval``: a number of MCUs, or ``row`` = ceil(W / 16), one interval per MCU row of a frame W pixels wide"""
+    if str(value) == "row":
+        return (int(W) + 15) // 16
+    try:
+        return int(value)
+    except ValueError:
+        raise ValueError(f"--restart-interval must be a number of MCUs or 'row', got {value!r}") from None
+
+
 def transcode(src, dst, quality=90, fps=None, restart_interval=0, yuv_matrix="bt601", device=None):
-    """-> the number of frames written.  ``fps`` None: the source's rate, 30 when it has none."""
+    """-> the number of frames written.  ``fps`` None: the source's rate, 30 when it has none.  ``restart_interval``: MCUs, or "row"."""
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     vr = fd.open_video(src, yuv_matrix)
+    restart_interval = restart_mcus(restart_interval,getattr(vr, "W", None) or np.asarray(vr[0]).shape[1])
     rate = fps if fps is not None else (getattr(vr, "fps", None) or 30.0)
     with fd.MjpegWriter(dst, rate, quality=quality, restart_interval=restart_interval) as w:
         for lo in range(0, len(vr), CHUNK):
@@ -43,7 +57,7 @@ def main():
     ap.add_argument("dst")
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--fps", type=float, default=None)
-    ap.add_argument("--restart-interval", type=int, default=0)
+    ap.add_argument("--restart-interval", default="0", help="MCUs between RSTn markers (0: none), or 'row': one interval per MCU row")
     ap.add_argument("--yuv-matrix", default="bt601", choices=("bt601", "bt709"))
     ap.add_argument("--device", default=None, choices=("cuda", "cpu"))
     a = ap.parse_args()
