@@ -824,6 +824,35 @@ size_t kvq_jpeg_encode_bound(int H, int W);
 int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt /* [3][64] */, int H, int W, int restart_interval, int flags, uint8_t* out,
                     size_t cap, size_t* n);
 
+/* Baseline JPEG, writing: the entropy CODING on the device, one lane per 8 x 8 block (csrc/jpeg_enc_entropy.hip; csrc/jpeg_enc_huff.hpp
+ * is the one definition of a block's coding, shared with the host twin).  An image is header + scan + FF D9:
+ *
+ * kvq_jpeg_encode_header (host only): the bytes kvq_jpeg_encode writes in front of the scan, SOI .. SOS, into out[0 .. cap); arguments,
+ * refusals and *n as there.
+ *
+ * kvq_jpeg_encode_scans: coef = T frames of coefficients on the device, back to back, as kvq_jpeg_fdct writes them -> every frame's
+ * entropy-coded segment — all that kvq_jpeg_encode writes between its SOS header and its FF D9: the stuffed bytes, the last byte of
+ * every restart interval padded with 1 bits, RSTn between the intervals — packed back to back in frame order into out[0 .. cap)
+ * (device, cap < 2^32), and frames_out = uint32 [T][3] {offset, length, status} (device):
+ *   0  coded
+ *   1  a coefficient is outside baseline's categories (kvq_jpeg_encode names it); length 0, the other frames are not affected
+ *   2  capacity: the frame ends past cap and is not written; offset and length are exact all the same, so
+ *      offset[T-1] + length[T-1] is the capacity a second call needs
+ * Every store to out is compared against cap first.  No intermediate stream is kept: a lane regenerates the bytes it owns, so the
+ * workspace (device, 16-byte aligned) is 12 bytes per block and 24 per frame whatever the data — kvq_jpeg_scans_workspace_bytes(T, H, W);
+ * less is KVQ_ERR_WORKSPACE with nothing enqueued, so no store ever depends on a workspace that is too small.  Only enqueues on
+ * `stream`: the zero-fill of the 8 T bytes it needs, six launches; no synchronisation, no blocking copy, no host read of device data;
+ * every output byte has one writer, two calls give equal bytes.  T, H, W as kvq_jpeg_fdct, restart_interval 0..65535; coef 16-byte,
+ * frames_out 4-byte aligned, else KVQ_ERR_SHAPE.
+ * kvq_jpeg_encode_scans_host: the same phases on host memory, equal in every byte of out and every word of frames_out. */
+int kvq_jpeg_encode_header(const uint16_t* qt /* [3][64] */, int H, int W, int restart_interval, int flags, uint8_t* out, size_t cap,
+                           size_t* n);
+size_t kvq_jpeg_scans_workspace_bytes(int T, int H, int W);
+int kvq_jpeg_encode_scans_host(const int16_t* coef, int T, int H, int W, int restart_interval, uint8_t* out, size_t cap,
+                               uint32_t* frames_out, void* workspace, size_t workspace_bytes);
+int kvq_jpeg_encode_scans(const void* coef, int T, int H, int W, int restart_interval, void* out, size_t cap, void* frames_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* torchvision Resize on a tensor (= bilinear, align_corners=False, no antialias; get_resize_function,
  * fusion_datasets.py:229-241) + crop + (v-mean)/std: get_resized_video (:244-252), get_resizecrop_video
  * (:299-316).  video u8|fp32 (C,T,H,W) -> resized to (rh,rw) -> crop [cy:cy+oh, cx:cx+ow] -> out fp32

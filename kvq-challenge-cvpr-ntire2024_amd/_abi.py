@@ -334,6 +334,10 @@ SYMBOLS = {
     "kvq_jpeg_fdct": (i32, [p_void, i32, i32, i32, i32, p_void, p_void, p_void]),
     "kvq_jpeg_encode_bound": (sz, [i32, i32]),
     "kvq_jpeg_encode": (i32, [p_void, p_void, i32, i32, i32, i32, p_void, sz, C.POINTER(sz)]),
+    "kvq_jpeg_encode_header": (i32, [p_void, i32, i32, i32, i32, p_void, sz, C.POINTER(sz)]),
+    "kvq_jpeg_scans_workspace_bytes": (sz, [i32, i32, i32]),
+    "kvq_jpeg_encode_scans_host": (i32, [p_void, i32, i32, i32, i32, p_void, sz, p_void, p_void, sz]),
+    "kvq_jpeg_encode_scans": (i32, [p_void, i32, i32, i32, i32, p_void, sz, p_void, p_void, sz, p_void]),
     "kvq_fragment_gather_batch": (i32, [C.POINTER(KvqFragmentSource), i32, i32, p_void, p_void]),
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),

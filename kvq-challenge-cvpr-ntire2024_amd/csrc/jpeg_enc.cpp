@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/kvq_hip.h"
+#include "jpeg_enc_huff.hpp"
 #include "jpeg_fdct.hpp"
 #include "jpeg_tables.hpp"
 
@@ -33,26 +34,6 @@ const uint8_t STD_Q_LUM[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 1
 const uint8_t STD_Q_CHR[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
                                47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-
-// (length << 16) | code of every symbol of the four Annex K tables: DC lum, DC chroma, AC lum, AC chroma
-struct EncTables {
-  uint32_t t[4][256];
-  EncTables() {
-    memset(t, 0, sizeof(t));
-    fill(t[0], STD_DC_LUM_BITS, STD_DC_VALS);
-    fill(t[1], STD_DC_CHR_BITS, STD_DC_VALS);
-    fill(t[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS);
-    fill(t[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS);
-  }
-  static void fill(uint32_t* t, const uint8_t bits[16], const uint8_t* vals) {
-    uint32_t code = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; ++l) {
-      for (int i = 0; i < bits[l - 1]; ++i) t[vals[k++]] = ((uint32_t)l << 16) | code++;
-      code <<= 1;
-    }
-  }
-};
 
 // the image under construction: nothing is stored at or past cap, pos keeps counting so that the caller learns what was needed
 struct Out {
@@ -82,7 +63,9 @@ struct Out {
   }
 };
 
-inline int category(int32_t a) { return a ? 32 - __builtin_clz((uint32_t)a) : 0; }      // a >= 0: bits of its magnitude
+inline int category(int32_t a) { return jpeg_enc_category(a); }
+
+const JpegEncTables ENC = jpeg_enc_tables();      // jpeg_enc_huff.hpp
 
 }  // namespace
 
@@ -153,20 +136,8 @@ extern "C" size_t kvq_jpeg_encode_bound(int H, int W) {
   return 1024 + (size_t)g.blocks * 416 + (size_t)g.nc * 4;
 }
 
-extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, int W, int restart_interval, int flags, uint8_t* out,
-                               size_t cap, size_t* n_out) {
-  JPEG_REQUIRE(coef && qt && out && n_out, KVQ_ERR_NULL, "kvq_jpeg_encode: NULL pointer");
-  *n_out = 0;
-  JPEG_REQUIRE(jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_encode: frame of %d x %d", W, H);
-  JPEG_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, KVQ_ERR_SHAPE, "kvq_jpeg_encode: restart interval %d is outside 0..65535",
-               restart_interval);
-  JPEG_REQUIRE((flags & ~KVQ_JPEG_NO_DHT) == 0, KVQ_ERR_SHAPE, "kvq_jpeg_encode: unknown flags 0x%x", flags);
-  for (int i = 0; i < 192; ++i)
-    JPEG_REQUIRE(qt[i] >= 1 && qt[i] <= 255, KVQ_ERR_UNSUPPORTED, "kvq_jpeg_encode: quantiser %d (table %d, entry %d) — baseline tables are 8-bit, 1..255",
-                 (int)qt[i], i / 64, i % 64);
-  static const EncTables enc;
-  const JpegGeom g = jpeg_geom(H, W);
-  Out o{out, cap, 0, 0, 0};
+// SOI .. SOS of the image kvq_jpeg_encode writes, through o
+static void put_header(Out& o, const uint16_t* qt, int H, int W, int restart_interval, int flags) {
   static const uint8_t APP0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
   o.put16(0xFFD8);
   o.bytes(APP0, sizeof(APP0));
@@ -192,6 +163,39 @@ extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, i
   if (restart_interval) { o.put16(0xFFDD); o.put16(4); o.put16((unsigned)restart_interval); }
   static const uint8_t SOS[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
   o.bytes(SOS, sizeof(SOS));
+}
+
+// the checks kvq_jpeg_encode and kvq_jpeg_encode_header share; `who` names the entry in the message
+static int check_image_args(const char* who, const uint16_t* qt, int H, int W, int restart_interval, int flags) {
+  JPEG_REQUIRE(jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "%s: frame of %d x %d", who, W, H);
+  JPEG_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, KVQ_ERR_SHAPE, "%s: restart interval %d is outside 0..65535", who, restart_interval);
+  JPEG_REQUIRE((flags & ~KVQ_JPEG_NO_DHT) == 0, KVQ_ERR_SHAPE, "%s: unknown flags 0x%x", who, flags);
+  for (int i = 0; i < 192; ++i)
+    JPEG_REQUIRE(qt[i] >= 1 && qt[i] <= 255, KVQ_ERR_UNSUPPORTED, "%s: quantiser %d (table %d, entry %d) — baseline tables are 8-bit, 1..255", who,
+                 (int)qt[i], i / 64, i % 64);
+  return KVQ_OK;
+}
+
+extern "C" int kvq_jpeg_encode_header(const uint16_t* qt, int H, int W, int restart_interval, int flags, uint8_t* out, size_t cap, size_t* n_out) {
+  JPEG_REQUIRE(qt && out && n_out, KVQ_ERR_NULL, "kvq_jpeg_encode_header: NULL pointer");
+  *n_out = 0;
+  if (const int rc = check_image_args("kvq_jpeg_encode_header", qt, H, W, restart_interval, flags)) return rc;
+  Out o{out, cap, 0, 0, 0};
+  put_header(o, qt, H, W, restart_interval, flags);
+  *n_out = o.pos;
+  JPEG_REQUIRE(o.pos <= cap, KVQ_ERR_WORKSPACE, "kvq_jpeg_encode_header: out holds %zu bytes, the header needs %zu", cap, o.pos);
+  return KVQ_OK;
+}
+
+extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, int W, int restart_interval, int flags, uint8_t* out,
+                               size_t cap, size_t* n_out) {
+  JPEG_REQUIRE(coef && qt && out && n_out, KVQ_ERR_NULL, "kvq_jpeg_encode: NULL pointer");
+  *n_out = 0;
+  if (const int rc = check_image_args("kvq_jpeg_encode", qt, H, W, restart_interval, flags)) return rc;
+  const JpegEncTables& enc = ENC;
+  const JpegGeom g = jpeg_geom(H, W);
+  Out o{out, cap, 0, 0, 0};
+  put_header(o, qt, H, W, restart_interval, flags);
   const int16_t* plane[3] = {coef, coef + (size_t)g.ny * 64, coef + (size_t)(g.ny + g.nc) * 64};
   int32_t pred[3] = {0, 0, 0};
   int mcu = 0;
@@ -235,5 +239,60 @@ extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, i
   *n_out = o.pos;
   JPEG_REQUIRE(o.pos <= cap, KVQ_ERR_WORKSPACE, "kvq_jpeg_encode: out holds %zu bytes, this %d x %d frame needs %zu (kvq_jpeg_encode_bound: %zu)",
                cap, W, H, o.pos, kvq_jpeg_encode_bound(H, W));
+  return KVQ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The scans of T frames, the phases of jpeg_enc_huff.hpp in loops: the twin of kvq_jpeg_encode_scans (jpeg_enc_entropy.hip)
+
+extern "C" size_t kvq_jpeg_scans_workspace_bytes(int T, int H, int W) {
+  if (T <= 0 || T >= 65536 || !jpeg_size_ok(H, W)) return 0;
+  return jpeg_scans_workspace((size_t)T, jpeg_geom(H, W));
+}
+
+extern "C" int kvq_jpeg_encode_scans_host(const int16_t* coef, int T, int H, int W, int restart_interval, uint8_t* out, size_t cap,
+                                          uint32_t* frames_out, void* workspace, size_t workspace_bytes) {
+  JPEG_REQUIRE(coef && out && frames_out && workspace, KVQ_ERR_NULL, "kvq_jpeg_encode_scans_host: NULL pointer");
+  JPEG_REQUIRE(T > 0 && T < 65536 && jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_encode_scans_host: %d frames of %dx%d", T, H, W);
+  JPEG_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, KVQ_ERR_SHAPE, "kvq_jpeg_encode_scans_host: restart interval %d is outside 0..65535",
+               restart_interval);
+  JPEG_REQUIRE(cap < ((size_t)1 << 32), KVQ_ERR_SHAPE, "kvq_jpeg_encode_scans_host: a capacity of %zu bytes; offsets are 32-bit", cap);
+  JPEG_REQUIRE((((uintptr_t)coef | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)frames_out & 3) == 0, KVQ_ERR_SHAPE,
+               "kvq_jpeg_encode_scans_host: coef and workspace must be 16-byte aligned, frames_out 4-byte aligned");
+  JpegScansPlan p{};
+  p.coef = coef; p.out = out; p.frames_out = frames_out;
+  p.cap = cap; p.T = (uint32_t)T; p.ri = (uint32_t)restart_interval; p.g = jpeg_geom(H, W);
+  JPEG_REQUIRE(workspace_bytes >= jpeg_scans_workspace((size_t)T, p.g), KVQ_ERR_WORKSPACE,
+               "kvq_jpeg_encode_scans_host: a workspace of %zu bytes; %d frames of %dx%d need %zu (kvq_jpeg_scans_workspace_bytes)", workspace_bytes, T, H,
+               W, jpeg_scans_workspace((size_t)T, p.g));
+  jpeg_scans_layout(p, workspace);
+  memset(p.fr32, 0, 8 * (size_t)T);
+  const uint32_t* tab = &ENC.t[0][0];
+  const uint32_t blocks = (uint32_t)p.g.blocks;
+  for (uint32_t t = 0; t < p.T; ++t)
+    for (uint32_t s = 0; s < blocks; ++s) jpeg_scans_count(p, tab, t, s);
+  for (uint32_t t = 0; t < p.T; ++t) {
+    uint64_t x = 0;
+    for (uint32_t s = 0; s < blocks; ++s) {
+      const JpegScanSeg e = jpeg_scans_seg(p, p.fr32[2 * (size_t)t] != 0u, t, s);
+      p.pos[(size_t)t * blocks + s] = e.e ? (x + 7u) & ~(uint64_t)7 : x;
+      x = jpeg_scan_apply(e, x);
+    }
+    p.fr64[2 * (size_t)t] = (x + 7u) >> 3;
+  }
+  for (uint32_t t = 0; t < p.T; ++t)
+    for (uint32_t s = 0; s < blocks; ++s) jpeg_scans_ffcount(p, tab, t, s);
+  for (uint32_t t = 0; t < p.T; ++t) {
+    uint32_t x = 0;
+    for (uint32_t s = 0; s < blocks; ++s) {
+      const uint32_t n = p.cnt[(size_t)t * blocks + s];
+      p.cnt[(size_t)t * blocks + s] = x;
+      x += n;
+    }
+    p.fr32[2 * (size_t)t + 1] = x;
+  }
+  jpeg_scans_frames(p);
+  for (uint32_t t = 0; t < p.T; ++t)
+    for (uint32_t s = 0; s < blocks; ++s) jpeg_scans_write(p, tab, t, s);
   return KVQ_OK;
 }

@@ -896,6 +896,19 @@ def _jpeg_frames_entropy_on_device(vr, uniq, device):
     return kernels.jpeg_idct_i420(coef, dqt, vr.H, vr.W)
 
 
+JPEG_WRITE_ENTROPY = "auto"                              # the default of ``MjpegWriter(..., entropy=None)``
+# what "auto" chooses for frames on the device: the device coder was above the host coder in every round of MjpegWriter.write at
+# q50 / q75 / q90, with and without restart markers (README.md, "Motion-JPEG output"; profiles/mjpeg_write_entropy_probe.txt)
+_JPEG_WRITE_AUTO_DEVICE = True
+
+
+def jpeg_write_entropy_mode(mode):
+    """``mode`` if it is one of ``JPEG_ENTROPY_MODES``, else a ValueError that names them"""
+    if mode not in JPEG_ENTROPY_MODES:
+        raise ValueError(f"entropy={mode!r}: one of {', '.join(JPEG_ENTROPY_MODES)}")
+    return mode
+
+
 class MjpegWriter:
     """Motion-JPEG video written without a codec library, the mirror of ``MjpegFrameReader``: every frame one baseline 4:2:0 JFIF
     image of IJG quality ``quality`` (``kernels.jpeg_quant_tables``), RSTn markers every ``restart_interval`` MCUs when that is not 0.
@@ -910,13 +923,21 @@ class MjpegWriter:
     any other I420 format is a ValueError (convert with ``to_rgb()``).  On the device: ONE ``jpeg_fdct`` launch, ONE D2H copy of the
     coefficients into pinned staging, then the entropy coder on the threads of the copy pool (the library calls release the GIL).
     Host tensors go through the scalar twin of the launch (bit-equal).  ``write_coefficients(coef, H, W)`` takes coefficients that
-    are already on the host.  All frames of a video have the first frame's size.  Use as a context manager or call ``close()``."""
+    are already on the host.  All frames of a video have the first frame's size.  Use as a context manager or call ``close()``.
+    ``entropy`` ("auto" | "host" | "device", None: the module's ``JPEG_WRITE_ENTROPY``) says where the frames of ``write()`` are
+    entropy-coded.  "host" is the path above.  "device" (device frames only; host frames are a ValueError): ``jpeg_fdct``, then
+    ``kernels.jpeg_encode_scans`` — one lane per block —, the T x 12-byte table of {offset, length, status} comes down, then ONE copy
+    of exactly the scans' bytes into pinned staging; an image is the header (built once per writer) + its scan + FF D9.  A table
+    that reports a short capacity makes one second call with the capacity it names; a frame with a coefficient outside baseline's
+    range has its coefficients brought down and goes through ``kernels.jpeg_encode``, whose refusal is the writer's.  The files of
+    the two paths are equal byte for byte.  "auto": "device" for frames on the device (``_JPEG_WRITE_AUTO_DEVICE``), "host" otherwise.  ``write_coefficients`` is always the host coder."""
 
     AVI_LIMIT = 1 << 30
     _AVI_HEADER = 12 + 12 + 64 + 12 + 64 + 48 + 12      # RIFF, hdrl LIST, avih chunk, strl LIST, strh chunk, strf chunk, movi LIST
 
-    def __init__(self, path, fps, quality=90, restart_interval=0):
+    def __init__(self, path, fps, quality=90, restart_interval=0, entropy=None):
         from fractions import Fraction
+        self.entropy = jpeg_write_entropy_mode(JPEG_WRITE_ENTROPY if entropy is None else entropy)
         self.path, self.fps, self.quality, self.restart_interval = str(path), float(fps), int(quality), int(restart_interval)
         if not self.fps > 0:
             raise ValueError(f"MjpegWriter: fps must be positive, got {fps}")
@@ -950,6 +971,7 @@ class MjpegWriter:
         if self.H is None:
             self.H, self.W = int(H), int(W)
             self._bound = kernels.jpeg_encode_bound(self.H, self.W)
+            self._head = kernels.jpeg_encode_header(self.qt, self.H, self.W, self.restart_interval).tobytes()
         elif (self.H, self.W) != (int(H), int(W)):
             raise ValueError(f"{self.path}: a frame of {W} x {H} in a video of {self.W} x {self.H}")
 
@@ -963,6 +985,8 @@ class MjpegWriter:
         if not (data.dtype == torch.uint8 and len(frames.shape) == 4 and frames.shape[0] == 3):
             raise ValueError(f"{self.path}: expected uint8 (3, T, H, W) frames or I420Frames, got {data.dtype} {tuple(frames.shape)}")
         _, T, H, W = frames.shape
+        if self.entropy == "device" and not data.is_cuda:
+            raise ValueError(f"{self.path}: entropy='device' codes frames that are on the device; `frames` is on {data.device}")
         self._set_size(H, W)
         if not data.is_cuda:
             src = data.contiguous().numpy()
@@ -971,12 +995,50 @@ class MjpegWriter:
         if qt is None:
             qt = self._qt_dev[data.device] = torch.from_numpy(self.qt.view(np.int16)).to(data.device).view(torch.uint16)
         coef = kernels.jpeg_fdct(frames if i420 else data.contiguous(), qt)
+        if self.entropy == "device" or (self.entropy == "auto" and _JPEG_WRITE_AUTO_DEVICE):
+            return self._write_scans(coef, H, W)
         st, k = _Staging.get(coef.numel() * 2)
         stage = st["buf"][k][:coef.numel() * 2].view(torch.int16).view(coef.shape)
         stage.copy_(coef, non_blocking=True)
         torch.cuda.current_stream(data.device).synchronize()
         st["ev"][k] = None
         return self.write_coefficients(stage.numpy(), H, W)
+
+    @staticmethod
+    def _down(src, nbytes, stream):
+        """the first ``nbytes`` bytes of the device tensor ``src`` -> a uint8 numpy view of pinned staging, after the stream reached it"""
+        st, k = _Staging.get(nbytes)
+        stage = st["buf"][k][:nbytes]
+        stage.copy_(src.reshape(-1).view(torch.uint8)[:nbytes], non_blocking=True)
+        stream.synchronize()
+        st["ev"][k] = None
+        return stage.numpy()
+
+    def _write_scans(self, coef, H, W):
+        """device coefficients -> images through the device entropy coder (class docstring)"""
+        T = coef.shape[0]
+        stream = torch.cuda.current_stream(coef.device)
+        cap = None
+        for attempt in range(2):
+            out, frames = kernels.jpeg_encode_scans(coef, H, W, self.restart_interval, cap)
+            table = self._down(frames, T * 12, stream).view(np.uint32).reshape(T, 3).astype(np.int64)
+            status, need = table[:, 2], int(table[-1, 0] + table[-1, 1])
+            if not (status == kernels.JPEG_SCAN_CAPACITY).any():
+                break
+            if attempt:
+                raise RuntimeError(f"{self.path}: the device entropy coder reports a short capacity with the {cap} bytes it asked for")
+            cap = need
+        bad = np.nonzero(status == kernels.JPEG_SCAN_RANGE)[0]
+        again = {}
+        if bad.size:                                             # rare: the host coder's verdict and message are final
+            down = coef[torch.from_numpy(bad).to(coef.device)].cpu().numpy()
+            buf = np.empty(self._bound, np.uint8)
+            for r, j in enumerate(bad):
+                again[int(j)] = kernels.jpeg_encode(down[r], self.qt, self.H, self.W, self.restart_interval, out=buf).tobytes()
+        scans = self._down(out, need, stream) if need else np.empty(0, np.uint8)
+        for j in range(T):
+            o, n = int(table[j, 0]), int(table[j, 1])
+            self._append(again[j] if j in again else self._head + scans[o:o + n].tobytes() + b"\xff\xd9")
 
     def _encode(self, coef):
         """frames of coefficients -> list of bytes, on one thread"""

@@ -606,6 +606,85 @@ def jpeg_encode(coef, qt, H: int, W: int, restart_interval: int = 0, dht: bool =
     return out[:n.value]
 
 
+def jpeg_encode_header(qt, H: int, W: int, restart_interval: int = 0, dht: bool = True):
+    """``kvq_jpeg_encode_header`` (host only): the bytes ``jpeg_encode`` writes in front of the scan, SOI .. SOS, as a uint8 numpy array.
+    An image is this + its scan (``jpeg_encode_scans``) + FF D9."""
+    import numpy as np
+    assert qt.dtype == np.uint16 and qt.flags.c_contiguous and qt.size == 192, (qt.dtype, qt.shape)
+    out = np.empty(1024, np.uint8)
+    n = C.c_size_t(0)
+    check(lib().kvq_jpeg_encode_header(qt.ctypes.data, int(H), int(W), int(restart_interval), 0 if dht else _abi.JPEG_NO_DHT, out.ctypes.data,
+                                       out.size, C.byref(n)), "kvq_jpeg_encode_header")
+    return out[:n.value].copy()
+
+
+# ``jpeg_encode_scans`` without ``cap``: room for the scans of 1 / JPEG_SCANS_FRACTION of the coefficient bytes = 32 bytes per block
+# (q90 1080p takes about 14, the worst case is 208)
+JPEG_SCANS_FRACTION = 4
+JPEG_SCAN_OK, JPEG_SCAN_RANGE, JPEG_SCAN_CAPACITY = 0, 1, 2
+
+
+def jpeg_scans_workspace_bytes(T: int, H: int, W: int) -> int:
+    """workspace of ``jpeg_encode_scans`` for T frames of H x W (``kvq_jpeg_scans_workspace_bytes``): 12 bytes per block, 24 per frame"""
+    n = lib().kvq_jpeg_scans_workspace_bytes(int(T), int(H), int(W))
+    if n == 0:
+        raise ValueError(f"jpeg_scans_workspace_bytes: {T} frames of {W} x {H} are outside what the library encodes")
+    return n
+
+
+def _aligned16(n: int, dtype):
+    """a numpy array of n elements whose data is 16-byte aligned"""
+    import numpy as np
+    item = np.dtype(dtype).itemsize
+    raw = np.empty(n * item + 16, np.uint8)
+    o = (-raw.ctypes.data) % 16
+    return raw[o:o + n * item].view(dtype)
+
+
+def jpeg_encode_scans_host(coef, H: int, W: int, restart_interval: int = 0, cap: Optional[int] = None, workspace_bytes: Optional[int] = None):
+    """the host twin of ``jpeg_encode_scans`` on numpy arrays (``kvq_jpeg_encode_scans_host``): coef int16 (T, jpeg_coef_bytes / 2) ->
+    (out uint8 (cap,), frames uint32 (T, 3)); equal to the launch in every byte of out[:total] and every word of frames"""
+    import numpy as np
+    n = jpeg_coef_bytes(H, W) // 2
+    coef = np.ascontiguousarray(coef, np.int16).reshape(-1, n)
+    T = coef.shape[0]
+    if coef.ctypes.data % 16:
+        a = _aligned16(coef.size, np.int16).reshape(coef.shape)
+        a[...] = coef
+        coef = a
+    cap = coef.nbytes // JPEG_SCANS_FRACTION if cap is None else int(cap)
+    if workspace_bytes is None:
+        workspace_bytes = jpeg_scans_workspace_bytes(T, H, W)
+    out, frames, ws = np.empty(max(cap, 1), np.uint8), np.empty((T, 3), np.uint32), _aligned16(max(int(workspace_bytes), 1), np.uint8)
+    check(lib().kvq_jpeg_encode_scans_host(coef.ctypes.data, T, int(H), int(W), int(restart_interval), out.ctypes.data, cap, frames.ctypes.data,
+                                           ws.ctypes.data, int(workspace_bytes)), "kvq_jpeg_encode_scans_host")
+    return out[:cap], frames
+
+
+def jpeg_encode_scans(coef: torch.Tensor, H: int, W: int, restart_interval: int = 0, cap: Optional[int] = None,
+                      workspace: Optional[torch.Tensor] = None):
+    """Quantised coefficients -> the frames' entropy-coded scans, one lane per 8 x 8 block (``kvq_jpeg_encode_scans``): what ``jpeg_encode``
+    writes between its SOS header and its FF D9, packed back to back.  coef: device int16 (T, jpeg_coef_bytes / 2) as ``jpeg_fdct`` writes
+    it -> (out uint8 (cap,), frames int32 (T, 3): per frame {offset, length, status}, uint32 values; status ``JPEG_SCAN_OK``, ``_RANGE`` (a
+    coefficient baseline cannot code: ``jpeg_encode`` names it), ``_CAPACITY`` (offset + length of the last frame is the ``cap`` that is
+    enough)), both on the device.  ``cap`` defaults to 1 / ``JPEG_SCANS_FRACTION`` of the coefficient bytes; ``workspace``: a device
+    uint8 tensor of ``jpeg_scans_workspace_bytes``.  Only
+    enqueues: the caller reads ``frames`` after the stream has reached it."""
+    _need_gpu(coef, workspace)
+    n = jpeg_coef_bytes(H, W) // 2
+    assert coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() % n == 0 and coef.numel() > 0, (coef.dtype, tuple(coef.shape), H, W)
+    T = coef.numel() // n
+    cap = coef.numel() * 2 // JPEG_SCANS_FRACTION if cap is None else int(cap)
+    if workspace is None:
+        workspace = torch.empty(jpeg_scans_workspace_bytes(T, H, W), dtype=torch.uint8, device=coef.device)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == coef.device
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=coef.device)
+    frames = torch.empty(T, 3, dtype=torch.int32, device=coef.device)
+    check(lib().kvq_jpeg_encode_scans(ptr(coef), T, int(H), int(W), int(restart_interval), ptr(out), cap, ptr(frames), ptr(workspace),
+                                      workspace.numel(), stream_of(coef)), "kvq_jpeg_encode_scans")
+    return out[:cap], frames
+
+
 def _frame_format(v) -> int:
     """KvqSrcFormat of a frame tensor / ``I420Frames``"""
     return v.format if isinstance(v, I420Frames) else int(v.dtype == torch.uint8)

@@ -6,8 +6,11 @@ round trip); any other I420 format goes through ``to_rgb()``, which needs a devi
 
 ``--restart-interval row`` writes one restart interval per MCU row (ceil(W / 16) MCUs): the setting for datasets meant to be read
 back at speed, since the reader entropy-decodes the restart intervals of a frame in parallel on the device (README.md).
+``--entropy`` says where the frames are entropy-CODED: ``host`` (the threads of the copy pool), ``device`` (one lane per block; needs
+``--device cuda``) or ``auto`` (``MjpegWriter``'s default); the files are equal byte for byte.
 
     python tools/transcode_mjpeg.py SRC DST [--quality 90] [--fps F] [--restart-interval N|row] [--yuv-matrix bt601|bt709] [--device cuda|cpu]
+                                    [--entropy auto|host|device]
 """
 import argparse
 import os
@@ -33,13 +36,13 @@ def restart_mcus(value, W):
         raise ValueError(f"--restart-interval must be a number of MCUs or 'row', got {value!r}") from None
 
 
-def transcode(src, dst, quality=90, fps=None, restart_interval=0, yuv_matrix="bt601", device=None):
-    """-> the number of frames written.  ``fps`` None: the source's rate, 30 when it has none.  ``restart_interval``: MCUs, or "row"."""
+def transcode(src, dst, quality=90, fps=None, restart_interval=0, yuv_matrix="bt601", device=None, entropy=None):
+    """-> the number of frames written.  ``entropy``: ``MjpegWriter``'s.  ``fps`` None: the source's rate, 30 when it has none.  ``restart_interval``: MCUs, or "row"."""
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     vr = fd.open_video(src, yuv_matrix)
-    restart_interval = restart_mcus(restart_interval,getattr(vr, "W", None) or np.asarray(vr[0]).shape[1])
+    restart_interval = restart_mcus(restart_interval, getattr(vr, "W", None) or np.asarray(vr[0]).shape[1])
     rate = fps if fps is not None else (getattr(vr, "fps", None) or 30.0)
-    with fd.MjpegWriter(dst, rate, quality=quality, restart_interval=restart_interval) as w:
+    with fd.MjpegWriter(dst, rate, quality=quality, restart_interval=restart_interval, entropy=entropy) as w:
         for lo in range(0, len(vr), CHUNK):
             frames = fd._frames_to_device(vr, np.arange(lo, min(lo + CHUNK, len(vr))), device)
             if isinstance(frames, kernels.I420Frames):
@@ -60,8 +63,9 @@ def main():
     ap.add_argument("--restart-interval", default="0", help="MCUs between RSTn markers (0: none), or 'row': one interval per MCU row")
     ap.add_argument("--yuv-matrix", default="bt601", choices=("bt601", "bt709"))
     ap.add_argument("--device", default=None, choices=("cuda", "cpu"))
+    ap.add_argument("--entropy", default=None, choices=fd.JPEG_ENTROPY_MODES, help="where the frames are entropy-coded (default: the writer's)")
     a = ap.parse_args()
-    n = transcode(a.src, a.dst, a.quality, a.fps, a.restart_interval, a.yuv_matrix, a.device)
+    n = transcode(a.src, a.dst, a.quality, a.fps, a.restart_interval, a.yuv_matrix, a.device, a.entropy)
     size = (sum(os.path.getsize(os.path.join(a.dst, f)) for f in os.listdir(a.dst)) if os.path.isdir(a.dst) else os.path.getsize(a.dst))
     print(f"{a.dst}: {n} frames, {size} bytes")
 
