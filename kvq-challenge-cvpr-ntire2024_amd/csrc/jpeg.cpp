@@ -11,51 +11,40 @@
 #include <string.h>
 
 #include "../../include/kvq_hip.h"
+#include "jpeg_host.hpp"
 #include "jpeg_huff.hpp"
 #include "jpeg_idct.hpp"
 #include "jpeg_tables.hpp"
-
-namespace kvq {
-void set_error(const char* fmt, ...);      // common.cpp (the stand-alone check program brings its own)
-}
 
 namespace {
 
 using namespace kvq;
 
-#define JPEG_REQUIRE(cond, code, ...)  \
-  do {                                 \
-    if (!(cond)) {                     \
-      kvq::set_error(__VA_ARGS__);     \
-      return code;                     \
-    }                                  \
-  } while (0)
-
-// canonical Huffman code of one table: codes of length l run from mincode[l] to maxcode[l]; the first 9 bits resolve short codes at once
+// one Huffman table of the stream, in the layout both decoders read (include/kvq_hip.h: KvqJpegHuffTable)
 struct Huff {
   bool present;
-  int32_t mincode[17], maxcode[17], valptr[17];
-  uint8_t vals[256];
-  uint16_t look[512];      // (length << 8) | symbol for codes of 1..9 bits, 0 = longer
+  KvqJpegHuffTable t;
 };
 
+// canonical code: the codes of length l are `code` .. code + cnt - 1; those of 1..9 bits go into the lookahead, the ranges of 10..16 are kept
 bool huff_build(Huff& h, const uint8_t bits[16], const uint8_t* vals, int nvals) {
   memset(&h, 0, sizeof(h));
-  memcpy(h.vals, vals, (size_t)nvals);
+  memcpy(h.t.vals, vals, (size_t)nvals);
   int32_t code = 0;
   int k = 0;
   for (int l = 1; l <= 16; ++l) {
-    h.valptr[l] = k;
-    h.mincode[l] = code;
     const int cnt = bits[l - 1];
     if (code + cnt > (1 << l)) return false;          // more codes of this length than the prefix code has room for
-    if (l <= 9)
+    if (l <= 9) {
       for (int i = 0; i < cnt; ++i)
-        for (int f = 0; f < (1 << (9 - l)); ++f) h.look[((code + i) << (9 - l)) | f] = (uint16_t)((l << 8) | vals[k + i]);
-    code += cnt;
+        for (int f = 0; f < (1 << (9 - l)); ++f) h.t.look[((code + i) << (9 - l)) | f] = (uint16_t)((l << 8) | vals[k + i]);
+    } else {
+      h.t.valptr[l - 10] = k;
+      h.t.mincode[l - 10] = code;
+      h.t.maxcode[l - 10] = cnt ? code + cnt - 1 : -1;
+    }
+    code = (code + cnt) << 1;
     k += cnt;
-    h.maxcode[l] = cnt ? code - 1 : -1;
-    code <<= 1;
   }
   h.present = true;
   return true;
@@ -224,6 +213,7 @@ struct Bits {
   size_t pos, n;
   uint64_t acc;
   int nbits;
+  static constexpr bool own_tables = true;                    // huff_build's (lengths 0..9, indices below 256): no masks, 3 % at q50
   void fill() {
     while (nbits <= 56 && pos < n) {
       const uint8_t b = d[pos];
@@ -251,41 +241,21 @@ struct Bits {
   }
 };
 
-enum { SYM_TRUNCATED = -1, SYM_BAD_CODE = -2 };
-
-int decode_symbol(Bits& b, const Huff& h) {
-  const uint32_t w = b.peek16();
-  const uint16_t e = h.look[w >> 7];
-  int len = e >> 8, sym = e & 255;
-  if (!len) {
-    for (len = 10; len <= 16; ++len) {
-      const int32_t code = (int32_t)(w >> (16 - len));
-      if (code <= h.maxcode[len] && code >= h.mincode[len]) { sym = h.vals[h.valptr[len] + code - h.mincode[len]]; break; }
-    }
-    if (len > 16) return b.nbits < 16 ? SYM_TRUNCATED : SYM_BAD_CODE;
-  }
-  if (len > b.nbits) return SYM_TRUNCATED;
-  b.nbits -= len;
-  return sym;
-}
-
-inline int32_t extend(uint32_t v, int s) { return v < (1u << (s - 1)) ? (int32_t)v - (1 << s) + 1 : (int32_t)v; }
-
 // one block into blk[64] (zeroed by the caller), natural order.  0, or the error text's cause
 const char* decode_block(Bits& b, const Huff& dc, const Huff& ac, int32_t& pred, int16_t* blk) {
-  int t = decode_symbol(b, dc);
-  if (t == SYM_TRUNCATED) return "the entropy-coded data is truncated";
-  if (t == SYM_BAD_CODE) return "a code that is in no Huffman table";
+  int t = jpeg_huff_symbol(b, &dc.t);
+  if (t == -JPEG_ST_TRUNCATED) return "the entropy-coded data is truncated";
+  if (t == -JPEG_ST_BAD_CODE) return "a code that is in no Huffman table";
   if (t > 15) return "a DC difference of more than 15 bits";
   uint32_t v = 0;
   if (!b.take(t, v)) return "the entropy-coded data is truncated";
-  pred = (int16_t)(pred + (t ? extend(v, t) : 0));           // kept to 16 bits, as it is stored
+  pred = (int16_t)(pred + (t ? jpeg_extend(v, t) : 0));           // kept to 16 bits, as it is stored
   blk[0] = (int16_t)pred;
   int k = 1;
   while (k < 64) {
-    const int rs = decode_symbol(b, ac);
-    if (rs == SYM_TRUNCATED) return "the entropy-coded data is truncated";
-    if (rs == SYM_BAD_CODE) return "a code that is in no Huffman table";
+    const int rs = jpeg_huff_symbol(b, &ac.t);
+    if (rs == -JPEG_ST_TRUNCATED) return "the entropy-coded data is truncated";
+    if (rs == -JPEG_ST_BAD_CODE) return "a code that is in no Huffman table";
     const int r = rs >> 4, s = rs & 15;
     if (s == 0) {
       if (r != 15) break;                                     // EOB
@@ -296,7 +266,7 @@ const char* decode_block(Bits& b, const Huff& dc, const Huff& ac, int32_t& pred,
     k += r;
     if (k > 63) return "a zero run past coefficient 63";
     if (!b.take(s, v)) return "the entropy-coded data is truncated";
-    blk[ZIGZAG[k]] = (int16_t)extend(v, s);
+    blk[ZIGZAG[k]] = (int16_t)jpeg_extend(v, s);
     ++k;
   }
   return nullptr;
@@ -311,6 +281,43 @@ bool expect_marker(Bits& b, int want, int& got) {
   if (got != want) return false;
   b.pos = pos;
   return true;
+}
+
+// the verdict on what stands where RST(want - 0xD0) before MCU `mcu` or, `last`, EOI belongs: got < 0 = no marker at all
+int marker_verdict(const char* who, bool last, int want, int got, long mcu) {
+  if (last && got < 0) set_error("%s: missing EOI after the last MCU (the stream is truncated)", who);
+  else if (last) set_error("%s: marker FF%02X after the last MCU where EOI belongs", who, got);
+  else if (got < 0) set_error("%s: missing RST%d before MCU %ld (the stream is truncated or has no marker there)", who, want - 0xD0, mcu);
+  else set_error("%s: wrong restart marker FF%02X before MCU %ld, expected RST%d", who, got, mcu, want - 0xD0);
+  return KVQ_ERR_SHAPE;
+}
+
+// ITU-T T.81 Annex K.3, what a stream without any DHT segment implies: DC lum, DC chroma, AC lum, AC chroma
+struct StdTables {
+  Huff h[4];
+  StdTables() {
+    huff_build(h[0], STD_DC_LUM_BITS, STD_DC_VALS, 12);
+    huff_build(h[1], STD_DC_CHR_BITS, STD_DC_VALS, 12);
+    huff_build(h[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS, 162);
+    huff_build(h[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS, 162);
+  }
+};
+
+// the tables the scan of a parsed image uses: per component its DC and AC table, and its quantiser table into qt_out[64 c ..]
+int resolve_tables(const Parsed& p, const char* who, const Huff* dc[3], const Huff* ac[3], uint16_t* qt_out) {
+  static const StdTables std_tab;
+  for (int c = 0; c < 3; ++c) {
+    JPEG_REQUIRE(p.qt_present[p.comp[c].tq], KVQ_ERR_SHAPE, "%s: quantiser table %d of component %d is not defined", who, p.comp[c].tq, c);
+    if (p.info.has_dht) {
+      dc[c] = &p.dc[p.comp[c].td]; ac[c] = &p.ac[p.comp[c].ta];
+      JPEG_REQUIRE(dc[c]->present && ac[c]->present, KVQ_ERR_SHAPE, "%s: Huffman table %d/%d of component %d is not defined", who, p.comp[c].td,
+                   p.comp[c].ta, c);
+    } else {                                                    // no DHT at all: table 0 = luminance, any other = chrominance
+      dc[c] = &std_tab.h[p.comp[c].td ? 1 : 0]; ac[c] = &std_tab.h[p.comp[c].ta ? 3 : 2];
+    }
+    for (int i = 0; i < 64; ++i) qt_out[64 * c + i] = p.qt[p.comp[c].tq][i];
+  }
+  return KVQ_OK;
 }
 
 }  // namespace
@@ -332,7 +339,6 @@ extern "C" int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out,
   using namespace kvq;
   JPEG_REQUIRE(data && coef_out && qt_out, KVQ_ERR_NULL, "kvq_jpeg_coeffs: NULL pointer");
   static thread_local Parsed p;
-  static thread_local Huff std_tab[4];                       // Annex K: DC lum, DC chroma, AC lum, AC chroma
   if (const int rc = parse(data, n, p, "kvq_jpeg_coeffs")) return rc;
   const int H = p.info.height, W = p.info.width;
   JPEG_REQUIRE(jpeg_size_ok(H, W), KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: frame of %d x %d", W, H);
@@ -341,27 +347,8 @@ extern "C" int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out,
   JPEG_REQUIRE(coef_cap >= bytes, KVQ_ERR_WORKSPACE, "kvq_jpeg_coeffs: coef_out holds %zu bytes, a %d x %d frame needs %zu", coef_cap, W, H, bytes);
   const Huff* dc[3];
   const Huff* ac[3];
-  if (!p.info.has_dht) {
-    if (!std_tab[0].present) {
-      huff_build(std_tab[0], STD_DC_LUM_BITS, STD_DC_VALS, 12);
-      huff_build(std_tab[1], STD_DC_CHR_BITS, STD_DC_VALS, 12);
-      huff_build(std_tab[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS, 162);
-      huff_build(std_tab[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS, 162);
-    }
-  }
-  for (int c = 0; c < 3; ++c) {
-    JPEG_REQUIRE(p.qt_present[p.comp[c].tq], KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: quantiser table %d of component %d is not defined", p.comp[c].tq, c);
-    if (p.info.has_dht) {
-      dc[c] = &p.dc[p.comp[c].td]; ac[c] = &p.ac[p.comp[c].ta];
-      JPEG_REQUIRE(dc[c]->present && ac[c]->present, KVQ_ERR_SHAPE, "kvq_jpeg_coeffs: Huffman table %d/%d of component %d is not defined",
-                   p.comp[c].td, p.comp[c].ta, c);
-    } else {                                                  // no DHT at all: table 0 = luminance, any other = chrominance
-      dc[c] = &std_tab[p.comp[c].td ? 1 : 0]; ac[c] = &std_tab[p.comp[c].ta ? 3 : 2];
-    }
-    for (int i = 0; i < 64; ++i) qt_out[64 * c + i] = p.qt[p.comp[c].tq][i];
-  }
+  if (const int rc = resolve_tables(p, "kvq_jpeg_coeffs", dc, ac, qt_out)) return rc;
   memset(coef_out, 0, bytes);
-  int16_t* plane[3] = {coef_out, coef_out + (size_t)g.ny * 64, coef_out + (size_t)(g.ny + g.nc) * 64};
   Bits b{data, p.scan, n, 0, 0};
   int32_t pred[3] = {0, 0, 0};
   const int ri = p.info.restart_interval;
@@ -370,41 +357,24 @@ extern "C" int kvq_jpeg_coeffs(const uint8_t* data, size_t n, int16_t* coef_out,
     for (int x = 0; x < g.mx; ++x, ++mcu) {
       if (ri && mcu && mcu % ri == 0) {
         const int want = 0xD0 + ((mcu / ri - 1) & 7);
-        if (!expect_marker(b, want, got)) {
-          if (got < 0) set_error("kvq_jpeg_coeffs: missing RST%d before MCU %d (the stream is truncated or has no marker there)", want - 0xD0, mcu);
-          else set_error("kvq_jpeg_coeffs: wrong restart marker FF%02X before MCU %d, expected RST%d", got, mcu, want - 0xD0);
-          return KVQ_ERR_SHAPE;
-        }
+        if (!expect_marker(b, want, got)) return marker_verdict("kvq_jpeg_coeffs", false, want, got, mcu);
         pred[0] = pred[1] = pred[2] = 0;
       }
       for (int k = 0; k < 6; ++k) {
         const int c = k < 4 ? 0 : k - 3;
-        const size_t blk = c == 0 ? (size_t)(2 * y + (k >> 1)) * (2 * g.mx) + 2 * x + (k & 1) : (size_t)y * g.mx + x;
-        if (const char* why = decode_block(b, *dc[c], *ac[c], pred[c], plane[c] + blk * 64)) {
+        int16_t* blk = coef_out + (size_t)jpeg_mcu_block(g, (uint32_t)y, (uint32_t)x, (uint32_t)k) * 64;
+        if (const char* why = decode_block(b, *dc[c], *ac[c], pred[c], blk)) {
           set_error("kvq_jpeg_coeffs: %s (MCU %d of %d, block %d)", why, mcu, g.nc, k);
           return KVQ_ERR_SHAPE;
         }
       }
     }
-  if (!expect_marker(b, 0xD9, got)) {
-    if (got < 0) set_error("kvq_jpeg_coeffs: missing EOI after the last MCU (the stream is truncated)");
-    else set_error("kvq_jpeg_coeffs: marker FF%02X after the last MCU where EOI belongs", got);
-    return KVQ_ERR_SHAPE;
-  }
+  if (!expect_marker(b, 0xD9, got)) return marker_verdict("kvq_jpeg_coeffs", true, 0xD9, got, mcu);
   return KVQ_OK;
 }
 
 // ---- entropy decode on the device: the host's share ---------------------------------------------------------------------------------
 namespace {
-
-void huff_export(const Huff& h, KvqJpegHuffTable& t) {
-  memset(&t, 0, sizeof(t));
-  memcpy(t.look, h.look, sizeof(t.look));
-  for (int l = 10; l <= 16; ++l) {
-    t.mincode[l - 10] = h.mincode[l]; t.maxcode[l - 10] = h.maxcode[l]; t.valptr[l - 10] = h.valptr[l];
-  }
-  memcpy(t.vals, h.vals, sizeof(t.vals));
-}
 
 // `t` into the set unless an identical table is there: its index
 int tables_add(KvqJpegTables& set, const KvqJpegHuffTable& t) {
@@ -421,7 +391,6 @@ extern "C" int kvq_jpeg_index(const uint8_t* data, size_t n, KvqJpegInfo* info, 
   using namespace kvq;
   JPEG_REQUIRE(data && info && seg_out && nseg_out && tables_out && qt_out, KVQ_ERR_NULL, "kvq_jpeg_index: NULL pointer");
   static thread_local Parsed p;
-  static thread_local Huff std_tab[4];                       // Annex K: DC lum, DC chroma, AC lum, AC chroma
   const int rc = parse(data, n, p, "kvq_jpeg_index");
   *info = p.info;
   if (rc) return rc;
@@ -435,22 +404,8 @@ extern "C" int kvq_jpeg_index(const uint8_t* data, size_t n, KvqJpegInfo* info, 
   JPEG_REQUIRE(seg_cap >= nseg, KVQ_ERR_WORKSPACE, "kvq_jpeg_index: seg_out holds %zu segments, the frame has %zu", seg_cap, nseg);
   const Huff* dc[3];
   const Huff* ac[3];
-  if (!p.info.has_dht && !std_tab[0].present) {
-    huff_build(std_tab[0], STD_DC_LUM_BITS, STD_DC_VALS, 12);
-    huff_build(std_tab[1], STD_DC_CHR_BITS, STD_DC_VALS, 12);
-    huff_build(std_tab[2], STD_AC_LUM_BITS, STD_AC_LUM_VALS, 162);
-    huff_build(std_tab[3], STD_AC_CHR_BITS, STD_AC_CHR_VALS, 162);
-  }
-  for (int c = 0; c < 3; ++c) {
-    JPEG_REQUIRE(p.qt_present[p.comp[c].tq], KVQ_ERR_SHAPE, "kvq_jpeg_index: quantiser table %d of component %d is not defined", p.comp[c].tq, c);
-    if (p.info.has_dht) {
-      dc[c] = &p.dc[p.comp[c].td]; ac[c] = &p.ac[p.comp[c].ta];
-      JPEG_REQUIRE(dc[c]->present && ac[c]->present, KVQ_ERR_SHAPE, "kvq_jpeg_index: Huffman table %d/%d of component %d is not defined",
-                   p.comp[c].td, p.comp[c].ta, c);
-    } else {
-      dc[c] = &std_tab[p.comp[c].td ? 1 : 0]; ac[c] = &std_tab[p.comp[c].ta ? 3 : 2];
-    }
-  }
+  uint16_t qt[192];                                          // qt_out is written once the walk has succeeded
+  if (const int rc = resolve_tables(p, "kvq_jpeg_index", dc, ac, qt)) return rc;
   // the marker walk: every 0xFF that no 0x00 follows closes a segment
   size_t pos = p.scan;
   for (size_t s = 0; s < nseg; ++s) {
@@ -466,32 +421,20 @@ extern "C" int kvq_jpeg_index(const uint8_t* data, size_t n, KvqJpegInfo* info, 
     }
     const bool last = s + 1 == nseg;
     const int want = last ? 0xD9 : 0xD0 + (int)(s & 7);
-    const long mcu = (long)(s + 1) * (long)ri;
     int got = -1;
     size_t after = end;
-    if (!read_marker(data, n, after, got)) {
-      if (last) set_error("kvq_jpeg_index: missing EOI after the last MCU (the stream is truncated)");
-      else set_error("kvq_jpeg_index: missing RST%d before MCU %ld (the stream is truncated or has no marker there)", want - 0xD0, mcu);
-      return KVQ_ERR_SHAPE;
-    }
-    if (got != want) {
-      if (last) set_error("kvq_jpeg_index: marker FF%02X after the last MCU where EOI belongs", got);
-      else set_error("kvq_jpeg_index: wrong restart marker FF%02X before MCU %ld, expected RST%d", got, mcu, want - 0xD0);
-      return KVQ_ERR_SHAPE;
-    }
+    if (!read_marker(data, n, after, got)) got = -1;
+    if (got != want) return marker_verdict("kvq_jpeg_index", last, want, got, (long)(s + 1) * (long)ri);
     seg_out[2 * s] = (uint32_t)begin;
     seg_out[2 * s + 1] = (uint32_t)end;
     pos = after;
   }
   memset(tables_out, 0, sizeof(*tables_out));
-  KvqJpegHuffTable t;
   for (int c = 0; c < 3; ++c) {
-    huff_export(*dc[c], t);
-    tables_out->dc[c] = (uint8_t)tables_add(*tables_out, t);
-    huff_export(*ac[c], t);
-    tables_out->ac[c] = (uint8_t)tables_add(*tables_out, t);
-    for (int i = 0; i < 64; ++i) qt_out[64 * c + i] = p.qt[p.comp[c].tq][i];
+    tables_out->dc[c] = (uint8_t)tables_add(*tables_out, dc[c]->t);
+    tables_out->ac[c] = (uint8_t)tables_add(*tables_out, ac[c]->t);
   }
+  memcpy(qt_out, qt, sizeof(qt));
   return KVQ_OK;
 }
 
@@ -508,18 +451,10 @@ extern "C" int kvq_jpeg_entropy_host(const uint8_t* bytes, size_t nbytes, const 
   for (int t = 0; t < T; ++t) {
     const uint32_t* f = frames + 5 * (size_t)t;
     if (f[2] == 0 || f[1] > nsegs || f[2] > nsegs - f[1]) continue;
-    const bool frame_ok = jpeg_frame_ok(f, nbytes, (uint32_t)nsegs, (uint32_t)ntables, g) && jpeg_tables_ok(tables + f[4]);
-    for (uint32_t s = 0; s < f[2]; ++s) {
-      const uint32_t* sg = segs + 2 * ((size_t)f[1] + s);
-      int32_t st = jpeg_status(JPEG_ST_BAD_SEGMENT, 0);
-      if (frame_ok && jpeg_segment_ok(f, sg, nbytes)) {
-        const uint32_t first = f[3] ? s * f[3] : 0u;                // < g.nc: s < nseg = ceil(nc / ri)
-        const uint32_t left = (uint32_t)g.nc - first;
-        st = jpeg_huff_segment(bytes + f[0], sg[0], sg[1], tables + f[4], (int)first, (int)(f[3] && f[3] < left ? f[3] : left), g,
-                               coef_out + (size_t)t * g.blocks * 64);
-      }
-      status_out[f[1] + s] = st;
-    }
+    const KvqJpegTables* set = tables + (f[4] < ntables ? f[4] : 0);      // a table set that does not exist is refused before it is read
+    for (uint32_t s = 0; s < f[2]; ++s)
+      status_out[f[1] + s] = jpeg_entropy_segment(f, s, set, bytes, nbytes, segs, (uint32_t)nsegs, (uint32_t)ntables, g,
+                                                  coef_out + (size_t)t * g.blocks * 64);
   }
   return KVQ_OK;
 }
@@ -534,10 +469,8 @@ extern "C" int kvq_jpeg_idct_i420_host(const int16_t* coef, const uint16_t* qt, 
   for (int t = 0; t < T; ++t) {
     const int16_t* cf = coef + (size_t)t * g.blocks * 64;
     for (int b = 0; b < g.blocks; ++b) {
-      const int c = b < g.ny ? 0 : (b < g.ny + g.nc ? 1 : 2);
-      const int id = c == 0 ? b : b - g.ny - (c - 1) * g.nc;
-      const int bpr = c == 0 ? 2 * g.mx : g.mx, ph = c == 0 ? H : ch, pw = c == 0 ? W : cw;
-      const int by = id / bpr, bx = id - by * bpr;
+      const JpegPlaneBlock pb = jpeg_plane_block(g, b);
+      const int c = pb.c, by = pb.by, bx = pb.bx, ph = c == 0 ? H : ch, pw = c == 0 ? W : cw;
       if (8 * by >= ph || 8 * bx >= pw) continue;            // a block that lies wholly in the MCU padding
       const uint16_t* q = qt + ((size_t)t * 3 + c) * 64;
       int32_t ws[8][8], v[8];

@@ -2,30 +2,20 @@
 // (kvq_jpeg_quant_tables), the scalar twin of the forward-DCT launch (kvq_jpeg_fdct_host, the arithmetic of jpeg_fdct.hpp) and the
 // baseline Huffman entropy coder that turns one frame of the dense coefficient hand-over into a JFIF image (kvq_jpeg_encode).
 // Plain C++17 like jpeg.cpp: no HIP call and no HIP header (tools/jpeg_enc_hostcheck.cpp builds it under the host sanitizers).
-// Every byte of the image goes through Out::put, which compares against the capacity first.
+// The Huffman coding of a block is jpeg_enc_huff.hpp's jpeg_enc_block, for kvq_jpeg_encode as for the scans.  Every byte of the image
+// goes through Out::put, which compares against the capacity first.
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/kvq_hip.h"
 #include "jpeg_enc_huff.hpp"
 #include "jpeg_fdct.hpp"
+#include "jpeg_host.hpp"
 #include "jpeg_tables.hpp"
-
-namespace kvq {
-void set_error(const char* fmt, ...);      // common.cpp (the stand-alone check program brings its own)
-}
 
 namespace {
 
 using namespace kvq;
-
-#define JPEG_REQUIRE(cond, code, ...)  \
-  do {                                 \
-    if (!(cond)) {                     \
-      kvq::set_error(__VA_ARGS__);     \
-      return code;                     \
-    }                                  \
-  } while (0)
 
 // ITU-T T.81 Annex K.1, natural order
 const uint8_t STD_Q_LUM[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
@@ -47,7 +37,8 @@ struct Out {
   }
   void put16(unsigned v) { put((uint8_t)(v >> 8)); put((uint8_t)v); }
   void bytes(const uint8_t* s, size_t n) { for (size_t i = 0; i < n; ++i) put(s[i]); }
-  void bits(uint32_t code, int len) {                          // len in 0..27
+  bool full() const { return false; }                          // a sink of jpeg_enc_block that takes every block whole
+  void put(uint32_t code, int len) {                           // len in 0..27
     acc = (acc << len) | code;
     nbits += len;
     while (nbits >= 8) {
@@ -58,12 +49,10 @@ struct Out {
     }
   }
   void flush() {                                               // pad the last byte with 1 bits
-    if (nbits) bits((1u << (8 - nbits)) - 1u, 8 - nbits);
+    if (nbits) put((1u << (8 - nbits)) - 1u, 8 - nbits);
     acc = 0;
   }
 };
-
-inline int category(int32_t a) { return jpeg_enc_category(a); }
 
 const JpegEncTables ENC = jpeg_enc_tables();      // jpeg_enc_huff.hpp
 
@@ -108,10 +97,8 @@ extern "C" int kvq_jpeg_fdct_host(const uint8_t* src, int src_format, int T, int
     }
     int16_t* cf = coef_out + (size_t)t * g.blocks * 64;
     for (int b = 0; b < g.blocks; ++b) {
-      const int c = b < g.ny ? 0 : (b < g.ny + g.nc ? 1 : 2);
-      const int id = c == 0 ? b : b - g.ny - (c - 1) * g.nc;
-      const int bpr = c == 0 ? 2 * g.mx : g.mx;
-      const int by = id / bpr, bx = id - by * bpr;
+      const JpegPlaneBlock pb = jpeg_plane_block(g, b);
+      const int c = pb.c, by = pb.by, bx = pb.bx;
       int32_t ws[8][8], v[8];
       for (int r = 0; r < 8; ++r) {
         for (int u = 0; u < 8; ++u) v[u] = jpeg_src_sample(src, rgb, T, H, W, t, c, 8 * by + r, 8 * bx + u) - 128;
@@ -192,11 +179,9 @@ extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, i
   JPEG_REQUIRE(coef && qt && out && n_out, KVQ_ERR_NULL, "kvq_jpeg_encode: NULL pointer");
   *n_out = 0;
   if (const int rc = check_image_args("kvq_jpeg_encode", qt, H, W, restart_interval, flags)) return rc;
-  const JpegEncTables& enc = ENC;
   const JpegGeom g = jpeg_geom(H, W);
   Out o{out, cap, 0, 0, 0};
   put_header(o, qt, H, W, restart_interval, flags);
-  const int16_t* plane[3] = {coef, coef + (size_t)g.ny * 64, coef + (size_t)(g.ny + g.nc) * 64};
   int32_t pred[3] = {0, 0, 0};
   int mcu = 0;
   for (int y = 0; y < g.my; ++y)
@@ -208,30 +193,20 @@ extern "C" int kvq_jpeg_encode(const int16_t* coef, const uint16_t* qt, int H, i
       }
       for (int k = 0; k < 6; ++k) {
         const int c = k < 4 ? 0 : k - 3;
-        const size_t bi = c == 0 ? (size_t)(2 * y + (k >> 1)) * (2 * g.mx) + 2 * x + (k & 1) : (size_t)y * g.mx + x;
-        const int16_t* blk = plane[c] + bi * 64;
-        const uint32_t* dct = enc.t[c ? 1 : 0];
-        const uint32_t* act = enc.t[c ? 3 : 2];
+        const size_t b = jpeg_mcu_block(g, (uint32_t)y, (uint32_t)x, (uint32_t)k);
+        const int16_t* blk = coef + b * 64;
         const int32_t diff = blk[0] - pred[c];
+        const bool ok = jpeg_enc_block(blk, pred[c], c != 0, &ENC.t[0][0], o);
         pred[c] = blk[0];
-        int s = category(diff < 0 ? -diff : diff);
-        JPEG_REQUIRE(s <= 11, KVQ_ERR_UNSUPPORTED, "kvq_jpeg_encode: DC difference %d (plane %d, block %zu) is outside baseline's +-2047", diff, c, bi);
-        o.bits(dct[s] & 0xFFFFu, (int)(dct[s] >> 16));
-        if (s) o.bits((uint32_t)(diff < 0 ? diff + (1 << s) - 1 : diff), s);
-        int run = 0;
-        for (int i = 1; i < 64; ++i) {
-          const int32_t v = blk[ZIGZAG[i]];
-          if (v == 0) { ++run; continue; }
-          for (; run > 15; run -= 16) o.bits(act[0xF0] & 0xFFFFu, (int)(act[0xF0] >> 16));
-          s = category(v < 0 ? -v : v);
-          JPEG_REQUIRE(s <= 10, KVQ_ERR_UNSUPPORTED, "kvq_jpeg_encode: coefficient %d (plane %d, block %zu, zigzag position %d) is outside baseline's +-1023",
-                       v, c, bi, i);
-          const uint32_t e = act[(run << 4) | s];
-          o.bits(e & 0xFFFFu, (int)(e >> 16));
-          o.bits((uint32_t)(v < 0 ? v + (1 << s) - 1 : v), s);
-          run = 0;
-        }
-        if (run) o.bits(act[0] & 0xFFFFu, (int)(act[0] >> 16));      // EOB: zeros up to coefficient 63
+        if (ok) continue;
+        // baseline has no code for a value of this block: name the first one in coding order
+        const size_t bi = b - (c == 0 ? 0 : (size_t)g.ny + (size_t)(c - 1) * g.nc);      // the block inside its plane
+        JPEG_REQUIRE(jpeg_enc_category(diff < 0 ? -diff : diff) <= 11, KVQ_ERR_UNSUPPORTED,
+                     "kvq_jpeg_encode: DC difference %d (plane %d, block %zu) is outside baseline's +-2047", diff, c, bi);
+        int i = 1;
+        for (int32_t v; i < 63 && (v = blk[ZIGZAG[i]], jpeg_enc_category(v < 0 ? -v : v) <= 10);) ++i;
+        JPEG_REQUIRE(false, KVQ_ERR_UNSUPPORTED, "kvq_jpeg_encode: coefficient %d (plane %d, block %zu, zigzag position %d) is outside baseline's +-1023",
+                     (int)blk[ZIGZAG[i]], c, bi, i);
       }
     }
   o.flush();

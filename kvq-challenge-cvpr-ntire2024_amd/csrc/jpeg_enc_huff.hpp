@@ -1,9 +1,11 @@
 // The ONE definition of the baseline Huffman CODING of one 8 x 8 block of the coefficient hand-over (jpeg_idct.hpp: JpegGeom), shared
-// by kvq_jpeg_encode_scans (jpeg_enc_entropy.hip, one lane per block) and its host twin kvq_jpeg_encode_scans_host (jpeg_enc.cpp):
+// by kvq_jpeg_encode_scans (jpeg_enc_entropy.hip, one lane per block), its host twin kvq_jpeg_encode_scans_host and the whole-image
+// coder kvq_jpeg_encode (both jpeg_enc.cpp):
 // the scan order, the DC predictor, the code length, the emission into a bit sink and the range verdict — and the phases that turn
 // T frames of coefficients into their byte-stuffed scans, one function per phase and per block, which the launch calls from a lane
 // and the twin from a loop.  No HIP header: the one device-only construct, the integer atomic OR (a compiler builtin), sits
-// behind __HIP_DEVICE_COMPILE__.  The bytes are those of kvq_jpeg_encode between its SOS header and its EOI, which the tests pin.
+// behind __HIP_DEVICE_COMPILE__.  The bytes are those of kvq_jpeg_encode between its SOS header and its EOI; the tests pin them to a numpy
+// restatement (tests/jpeg_enc_ref.py) and to libjpeg's (tests/golden/mjpeg_enc.npz).
 //
 // Scan order of a frame: MCU raster, within an MCU Y00 Y01 Y10 Y11 Cb Cr: scan index s = 6 mcu + k.  Restart interval i holds the
 // MCUs [i ri, (i + 1) ri); without DRI (ri = 0) the frame is one interval.  A block's DC predictor is the DC of the previous block
@@ -28,11 +30,6 @@
 #include "jpeg_idct.hpp"
 #include "jpeg_tables.hpp"
 
-#if defined(__HIPCC__)
-#define KVQ_JPEG_HD_MEMBER __host__ __device__ inline __attribute__((always_inline))
-#else
-#define KVQ_JPEG_HD_MEMBER inline
-#endif
 #if defined(__clang__)
 #define KVQ_JPEG_UNROLL _Pragma("unroll")
 #else
@@ -67,12 +64,10 @@ constexpr JpegEncTables jpeg_enc_tables() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scan order
-// the block of scan index s (< g.blocks) in the hand-over: exactly kvq_jpeg_encode's bi, plus its plane's first block
+// the block of scan index s (< g.blocks) in the hand-over
 KVQ_JPEG_HD uint32_t jpeg_enc_block_index(const JpegGeom& g, uint32_t s) {
-  const uint32_t mcu = s / 6u, k = s - 6u * mcu;
-  if (k >= 4u) return (uint32_t)g.ny + (k - 4u) * (uint32_t)g.nc + mcu;
-  const uint32_t y = mcu / (uint32_t)g.mx, x = mcu - y * (uint32_t)g.mx;
-  return (2u * y + (k >> 1)) * (2u * (uint32_t)g.mx) + 2u * x + (k & 1u);
+  const uint32_t mcu = s / 6u, y = mcu / (uint32_t)g.mx;
+  return jpeg_mcu_block(g, y, mcu - y * (uint32_t)g.mx, s - 6u * mcu);
 }
 // true: MCU `mcu` opens a restart interval (the first MCU of the frame included)
 KVQ_JPEG_HD bool jpeg_enc_interval_start(uint32_t mcu, uint32_t ri) { return mcu == 0u || (ri && mcu % ri == 0u); }

@@ -48,15 +48,7 @@ __global__ __launch_bounds__(JPEG_ENTROPY_LANES) void jpeg_entropy_kernel(JpegEn
   }
   __syncthreads();
   if (s >= f[2]) return;
-  const uint32_t sg[2] = {p.segs[2 * ((size_t)f[1] + s)], p.segs[2 * ((size_t)f[1] + s) + 1]};
-  int32_t st = jpeg_status(JPEG_ST_BAD_SEGMENT, 0);
-  if (frame_ok && jpeg_tables_ok(&set) && jpeg_segment_ok(f, sg, p.nbytes)) {
-    const uint32_t first = f[3] ? s * f[3] : 0u;                      // < g.nc: s < nseg = ceil(nc / ri)
-    const uint32_t left = (uint32_t)p.g.nc - first;
-    st = jpeg_huff_segment(p.bytes + f[0], sg[0], sg[1], &set, (int)first, (int)(f[3] && f[3] < left ? f[3] : left), p.g,
-                           p.coef + (size_t)t * p.g.blocks * 64);
-  }
-  p.status[f[1] + s] = st;
+  p.status[f[1] + s] = jpeg_entropy_segment(f, s, &set, p.bytes, p.nbytes, p.segs, p.nsegs, p.ntables, p.g, p.coef + (size_t)t * p.g.blocks * 64);
 }
 
 }  // namespace kvq

@@ -20,12 +20,17 @@
 // Status: 0, or JPEG_ST_* | (the frame's MCU number at which the decode stopped << 8).  The causes are the ones kvq_jpeg_coeffs
 // knows, and the end is STRICT: after the last MCU fewer than 8 bits may remain before `end` (kvq_jpeg_coeffs drops up to a
 // refill's worth of whole bytes there).  Stricter than the host decoder in that one place, laxer nowhere.
+//
+// The table layout, the symbol decode (jpeg_huff_symbol), the sign extension and the zigzag order are also kvq_jpeg_coeffs's.  Its
+// bit reader and block loop (Bits, decode_block in jpeg.cpp) stay a second pair on purpose: that byte-wise reader accepts a few stray
+// bytes in front of a marker where this one reports JPEG_ST_TRAILING, and the frame reader relies on "device strict, host final".
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/kvq_hip.h"
 #include "jpeg_idct.hpp"
+#include "jpeg_tables.hpp"
 
 namespace kvq {
 
@@ -42,12 +47,7 @@ constexpr int32_t JPEG_ST_UNWRITTEN = -1;      // what the entries fill status_o
 
 KVQ_JPEG_HD int32_t jpeg_status(int cause, int mcu) { return (int32_t)((uint32_t)cause | ((uint32_t)mcu << 8)); }
 
-KVQ_JPEG_HD int jpeg_zigzag(int k) {
-  static constexpr uint8_t Z[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-  return Z[k & 63];
-}
+KVQ_JPEG_HD int jpeg_zigzag(int k) { return ZIGZAG[k & 63]; }
 
 // the segment's bits, most significant first; `end` (or an 0xFF that no 0x00 follows) ends the supply, asking for more is an error
 struct JpegBits {
@@ -55,61 +55,63 @@ struct JpegBits {
   uint32_t pos, end;
   uint64_t acc;
   int nbits;              // valid low bits of acc, 0..64
+  static constexpr bool own_tables = false;     // the tables come from the caller's memory: what is read from them is masked
+
+  KVQ_JPEG_HD_MEMBER void fill() {
+    if (nbits > 32) return;
+    if (end - pos >= 4) {                                               // pos <= end always
+      uint32_t w;
+      memcpy(&w, buf + pos, 4);                                         // one unaligned load
+      w = __builtin_bswap32(w);
+      const uint32_t x = ~w;                                            // a zero byte of x is an 0xFF of w
+      if (!((x - 0x01010101u) & ~x & 0x80808080u)) {
+        acc = (acc << 32) | w;
+        nbits += 32;
+        pos += 4;
+        return;
+      }
+    }
+    for (int i = 0; i < 8 && nbits <= 56 && pos < end; ++i) {
+      const uint8_t v = buf[pos];
+      if (v == 0xFF) {
+        if (end - pos < 2 || buf[pos + 1] != 0x00) return;              // no stuffed byte: stay in front of it
+        pos += 2;
+      } else {
+        pos += 1;
+      }
+      acc = (acc << 8) | v;
+      nbits += 8;
+    }
+  }
+  // the next 16 bits, zero-padded where the supply has ended
+  KVQ_JPEG_HD_MEMBER uint32_t peek16() {
+    if (nbits < 16) fill();
+    return nbits >= 16 ? (uint32_t)(acc >> (nbits - 16)) & 0xFFFFu : (uint32_t)(acc << (16 - nbits)) & 0xFFFFu;
+  }
+  // k in 0..16
+  KVQ_JPEG_HD_MEMBER bool take(int k, uint32_t& out) {
+    if (nbits < k) fill();
+    if (nbits < k) return false;
+    out = k ? (uint32_t)(acc >> (nbits - k)) & ((1u << k) - 1u) : 0u;
+    nbits -= k;
+    return true;
+  }
 };
 
-KVQ_JPEG_HD void jpeg_bits_fill(JpegBits& b) {
-  if (b.nbits > 32) return;
-  if (b.end - b.pos >= 4) {                                           // pos <= end always
-    uint32_t w;
-    memcpy(&w, b.buf + b.pos, 4);                                     // one unaligned load
-    w = __builtin_bswap32(w);
-    const uint32_t x = ~w;                                            // a zero byte of x is an 0xFF of w
-    if (!((x - 0x01010101u) & ~x & 0x80808080u)) {
-      b.acc = (b.acc << 32) | w;
-      b.nbits += 32;
-      b.pos += 4;
-      return;
-    }
-  }
-  for (int i = 0; i < 8 && b.nbits <= 56 && b.pos < b.end; ++i) {
-    const uint8_t v = b.buf[b.pos];
-    if (v == 0xFF) {
-      if (b.end - b.pos < 2 || b.buf[b.pos + 1] != 0x00) return;      // no stuffed byte: stay in front of it
-      b.pos += 2;
-    } else {
-      b.pos += 1;
-    }
-    b.acc = (b.acc << 8) | v;
-    b.nbits += 8;
-  }
-}
-
-// the next 16 bits, zero-padded where the supply has ended
-KVQ_JPEG_HD uint32_t jpeg_bits_peek16(JpegBits& b) {
-  if (b.nbits < 16) jpeg_bits_fill(b);
-  return b.nbits >= 16 ? (uint32_t)(b.acc >> (b.nbits - 16)) & 0xFFFFu : (uint32_t)(b.acc << (16 - b.nbits)) & 0xFFFFu;
-}
-
-// k in 0..16
-KVQ_JPEG_HD bool jpeg_bits_take(JpegBits& b, int k, uint32_t& out) {
-  if (b.nbits < k) jpeg_bits_fill(b);
-  if (b.nbits < k) return false;
-  out = k ? (uint32_t)(b.acc >> (b.nbits - k)) & ((1u << k) - 1u) : 0u;
-  b.nbits -= k;
-  return true;
-}
-
-// a symbol 0..255, or -JPEG_ST_TRUNCATED / -JPEG_ST_BAD_CODE
-KVQ_JPEG_HD int jpeg_huff_symbol(JpegBits& b, const KvqJpegHuffTable* h) {
-  const uint32_t w = jpeg_bits_peek16(b);
+// a symbol 0..255, or -JPEG_ST_TRUNCATED / -JPEG_ST_BAD_CODE.  Bits: peek16() as above, nbits, from which the code's length is taken,
+// and own_tables — false: the table may hold anything, so a length from look[] is masked to 0..15 and the index into vals[] to 8 bits
+template <class Bits>
+KVQ_JPEG_HD int jpeg_huff_symbol(Bits& b, const KvqJpegHuffTable* h) {
+  const uint32_t w = b.peek16();
   const uint32_t e = h->look[w >> 7];
-  int len = (int)(e >> 8) & 15, sym = (int)(e & 255);
+  constexpr int len_mask = Bits::own_tables ? 255 : 15, val_mask = Bits::own_tables ? -1 : 255;
+  int len = (int)(e >> 8) & len_mask, sym = (int)(e & 255);
   if (!len) {
     len = 17;
     for (int l = 10; l <= 16; ++l) {
       const int32_t code = (int32_t)(w >> (16 - l));
       if (code <= h->maxcode[l - 10] && code >= h->mincode[l - 10]) {
-        sym = h->vals[(uint32_t)(h->valptr[l - 10] + code - h->mincode[l - 10]) & 255u];
+        sym = h->vals[(h->valptr[l - 10] + code - h->mincode[l - 10]) & val_mask];
         len = l;
         break;
       }
@@ -148,7 +150,7 @@ KVQ_JPEG_HD int32_t jpeg_huff_segment(const uint8_t* buf, uint32_t begin, uint32
     if (dc && sym > 15) return jpeg_status(JPEG_ST_BAD_DC, first_mcu + m);
     const int size = dc ? sym : (sym & 15), run = dc ? 0 : (sym >> 4);
     uint32_t v = 0;
-    if (!jpeg_bits_take(b, size, v)) return jpeg_status(JPEG_ST_TRUNCATED, first_mcu + m);
+    if (!b.take(size, v)) return jpeg_status(JPEG_ST_TRUNCATED, first_mcu + m);
     int32_t value = size ? jpeg_extend(v, size) : 0;
     bool close = false;
     if (dc) {
@@ -168,9 +170,7 @@ KVQ_JPEG_HD int32_t jpeg_huff_segment(const uint8_t* buf, uint32_t begin, uint32
       if (k > 63) return jpeg_status(JPEG_ST_BAD_RUN, first_mcu + m);
     }
     if (value) {                                                      // an AC value is never 0 (size >= 1); a DC of 0 is not stored
-      const size_t blk = j < 4 ? (size_t)(2 * y + (j >> 1)) * (size_t)(2 * g.mx) + (size_t)(2 * x + (j & 1))
-                               : (size_t)g.ny + (size_t)(j - 4) * g.nc + (size_t)y * g.mx + x;
-      coef[blk * 64 + jpeg_zigzag(k)] = (int16_t)value;
+      coef[(size_t)jpeg_mcu_block(g, (uint32_t)y, (uint32_t)x, (uint32_t)j) * 64 + jpeg_zigzag(k)] = (int16_t)value;
     }
     if (dc || size) close = ++k == 64;
     if (close) {
@@ -202,6 +202,18 @@ KVQ_JPEG_HD bool jpeg_tables_ok(const KvqJpegTables* t) {
 }
 KVQ_JPEG_HD bool jpeg_segment_ok(const uint32_t* frame, const uint32_t* seg, uint64_t nbytes) {
   return seg[0] <= seg[1] && (uint64_t)seg[1] <= nbytes - frame[0];
+}
+
+// Segment s of the frame f, for both entries: the descriptor checks, then the decode into `coef`, the frame's coefficients.  The
+// caller has checked s < f[2] and f[1] <= nsegs, f[2] <= nsegs - f[1] (the frame's entries lie in segs); `set` is the frame's table
+// set, tables + f[4] or a copy of it, and is read only where jpeg_frame_ok holds.
+KVQ_JPEG_HD int32_t jpeg_entropy_segment(const uint32_t* f, uint32_t s, const KvqJpegTables* set, const uint8_t* bytes, uint64_t nbytes,
+                                         const uint32_t* segs, uint32_t nsegs, uint32_t ntables, const JpegGeom& g, int16_t* coef) {
+  const uint32_t sg[2] = {segs[2 * ((size_t)f[1] + s)], segs[2 * ((size_t)f[1] + s) + 1]};
+  if (!(jpeg_frame_ok(f, nbytes, nsegs, ntables, g) && jpeg_tables_ok(set) && jpeg_segment_ok(f, sg, nbytes))) return jpeg_status(JPEG_ST_BAD_SEGMENT, 0);
+  const uint32_t first = f[3] ? s * f[3] : 0u;                          // < g.nc: s < nseg = ceil(nc / ri)
+  const uint32_t left = (uint32_t)g.nc - first;
+  return jpeg_huff_segment(bytes + f[0], sg[0], sg[1], set, (int)first, (int)(f[3] && f[3] < left ? f[3] : left), g, coef);
 }
 
 }  // namespace kvq

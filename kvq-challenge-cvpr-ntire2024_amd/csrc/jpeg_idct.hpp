@@ -1,7 +1,7 @@
 // The ONE definition of the JPEG block reconstruction (dequantise, 8 x 8 inverse DCT, level shift, clamp) that kvq_jpeg_idct_i420
 // (jpeg.hip), its scalar twin kvq_jpeg_idct_i420_host (jpeg.cpp) and the numpy restatement (tests/jpeg_ref.py) share, and the
-// geometry of the coefficient hand-over between the host entropy decoder and the launch.  No HIP dependency: jpeg.cpp includes it
-// under the host compiler alone.
+// geometry of the coefficient hand-over between the entropy decoders / coders and the DCT launches (JpegGeom and the two index maps
+// below it).  No HIP dependency: jpeg.cpp includes it under the host compiler alone.
 //
 // Arithmetic: the "slow integer" IDCT of the Independent JPEG Group's library (Loeffler-Ligtenberg-Moschytz, 12 multiplies per 1-D
 // pass, constants with CONST_BITS = 13 fractional bits), whose output is what the common decoders produce:
@@ -25,8 +25,10 @@
 
 #if defined(__HIPCC__)
 #define KVQ_JPEG_HD __host__ __device__ inline __attribute__((always_inline))
+#define KVQ_JPEG_HD_MEMBER __host__ __device__ inline __attribute__((always_inline))
 #else
 #define KVQ_JPEG_HD static inline
+#define KVQ_JPEG_HD_MEMBER inline
 #endif
 
 namespace kvq {
@@ -96,5 +98,24 @@ KVQ_JPEG_HD JpegGeom jpeg_geom(int H, int W) {
   return g;
 }
 static inline bool jpeg_size_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535 && (long)H * W < (1L << 28); }
+
+// Scan order -> hand-over: block k (0..5: Y00 Y01 Y10 Y11 Cb Cr) of the MCU in MCU row y, MCU column x, as its index in the frame
+KVQ_JPEG_HD uint32_t jpeg_mcu_block(const JpegGeom& g, uint32_t y, uint32_t x, uint32_t k) {
+  if (k >= 4u) return (uint32_t)g.ny + (k - 4u) * (uint32_t)g.nc + y * (uint32_t)g.mx + x;
+  return (2u * y + (k >> 1)) * (2u * (uint32_t)g.mx) + 2u * x + (k & 1u);
+}
+// Hand-over -> picture: block b (< g.blocks) of the frame is block (by, bx) of component c's plane
+struct JpegPlaneBlock {
+  int c, by, bx;
+};
+KVQ_JPEG_HD JpegPlaneBlock jpeg_plane_block(const JpegGeom& g, int b) {
+  JpegPlaneBlock p;
+  p.c = b < g.ny ? 0 : (b < g.ny + g.nc ? 1 : 2);
+  const int id = p.c == 0 ? b : b - g.ny - (p.c - 1) * g.nc;
+  const int bpr = p.c == 0 ? 2 * g.mx : g.mx;
+  p.by = id / bpr;
+  p.bx = id - p.by * bpr;
+  return p;
+}
 
 }  // namespace kvq

@@ -705,7 +705,6 @@ def _frames_to_device(vr, uniq, device, entropy=None):
     and the copy instead of 3 — and the result is a ``kernels.I420Frames`` (n, frame_bytes).
     A Motion-JPEG reader (``read_jpeg_into``: ``MjpegFrameReader``) goes through ``_jpeg_frames_to_device``; ``entropy`` ("auto" |
     "host" | "device", None: the module's ``JPEG_ENTROPY``) says where its frames are entropy-decoded and applies to no other reader."""
-    global _COPY_POOL
     if hasattr(vr, "read_jpeg_into"):
         return _jpeg_frames_to_device(vr, uniq, device, entropy)
     i420 = hasattr(vr, "read_i420_into")
@@ -721,14 +720,7 @@ def _frames_to_device(vr, uniq, device, entropy=None):
     stage = st["buf"][k][:nbytes].view((n,) + shape)
     host = stage.numpy()
     if read is not None:
-        if _COPY_POOL is None:
-            from concurrent.futures import ThreadPoolExecutor
-            _COPY_POOL = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix="kvq-copy")
-        nt = max(1, min(_COPY_THREADS, n // 8))
-        bounds = np.linspace(0, n, nt + 1).astype(int)
-        jobs = [_COPY_POOL.submit(read, uniq[a:b], host[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-        for j in jobs:
-            j.result()
+        list(_fan_out(n, n // 8, lambda a, b: read(uniq[a:b], host[a:b])))
     elif hasattr(vr, "get_batch"):                      # decord: one decode call for all frames
         host[...] = vr.get_batch([int(i) for i in uniq]).asnumpy()
     else:
@@ -750,6 +742,14 @@ def _copy_pool():
         from concurrent.futures import ThreadPoolExecutor
         _COPY_POOL = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix="kvq-copy")
     return _COPY_POOL
+
+
+def _fan_out(n, chunks, job):
+    """``job(a, b)`` on the copy pool's threads for the at most min(``_COPY_THREADS``, ``chunks``) ranges [a, b) that split range(n)
+    evenly: all are submitted at once, the results come in order as they are asked for"""
+    bounds = np.linspace(0, n, max(1, min(_COPY_THREADS, chunks)) + 1).astype(int)
+    jobs = [_copy_pool().submit(job, a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+    return map(lambda j: j.result(), jobs)
 
 
 JPEG_ENTROPY = "auto"                                    # the default of ``_frames_to_device(..., jpeg_entropy=None)``
@@ -786,11 +786,7 @@ def _jpeg_frames_to_device(vr, uniq, device, entropy=None):
     stage = st["buf"][k][:nbytes]
     host = stage.numpy()
     coef, qt = host[:n * cb].view(np.int16).reshape(n, cb // 2), host[n * cb:].view(np.uint16).reshape(n, 3, 64)
-    nt = max(1, min(_COPY_THREADS, n))
-    bounds = np.linspace(0, n, nt + 1).astype(int)
-    jobs = [_copy_pool().submit(vr.read_jpeg_into, uniq[a:b], coef[a:b], qt[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-    for j in jobs:
-        j.result()
+    list(_fan_out(n, n, lambda a, b: vr.read_jpeg_into(uniq[a:b], coef[a:b], qt[a:b])))
     if not on_gpu:
         return kernels.I420Frames(torch.from_numpy(kernels.jpeg_idct_i420_host(coef, qt, vr.H, vr.W)), vr.H, vr.W, vr.format)
     dev = stage.to(device, non_blocking=True)
@@ -840,12 +836,8 @@ def _jpeg_frames_entropy_on_device(vr, uniq, device):
     segs, data = host[o_segs:o_data].view(np.uint32).reshape(nseg, 2), host[o_data:o_data + ndata]
     host[o_data + ndata:o_tab] = 0
     tables = np.empty((n, TB), np.uint8)
-    nt = max(1, min(_COPY_THREADS, n))
-    bounds = np.linspace(0, n, nt + 1).astype(int)
-    jobs = [_copy_pool().submit(vr.read_jpeg_bytes_into, uniq[a:b], data, offsets[a:b], desc[a:b], segs, seg_offsets[a:b + 1], tables[a:b],
-                                qt[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-    for j in jobs:
-        j.result()
+    list(_fan_out(n, n, lambda a, b: vr.read_jpeg_bytes_into(uniq[a:b], data, offsets[a:b], desc[a:b], segs, seg_offsets[a:b + 1], tables[a:b],
+                                                             qt[a:b])))
     sets, seen = host[o_tab:].reshape(n, TB), {}
     for j in range(n):
         if desc[j, 2]:
@@ -1052,11 +1044,8 @@ class MjpegWriter:
         self._set_size(H, W)
         coef = np.ascontiguousarray(coef, np.int16).reshape(-1, kernels.jpeg_coef_bytes(H, W) // 2)
         n = coef.shape[0]
-        nt = max(1, min(_COPY_THREADS, n))
-        bounds = np.linspace(0, n, nt + 1).astype(int)
-        jobs = [_copy_pool().submit(self._encode, coef[a:b]) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-        for j in jobs:
-            for image in j.result():
+        for images in _fan_out(n, n, lambda a, b: self._encode(coef[a:b])):
+            for image in images:
                 self._append(image)
 
     def _append(self, image):

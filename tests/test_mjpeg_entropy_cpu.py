@@ -108,6 +108,26 @@ def test_index_refuses_what_the_decoder_refuses():
             assert hmsg.replace("kvq_jpeg_coeffs: ", "") == msg.replace("kvq_jpeg_index: ", ""), (what, hmsg, msg)
 
 
+def test_the_decoder_and_the_index_word_the_four_marker_faults_alike():
+    H, W, ri = 45, 70, 3                                             # 15 MCUs: five segments
+    jpg = jc.synthetic((H, W, ri, False))
+    segs, _ = jc.marker_search(jpg)
+    assert len(segs) == 5 and jc.host_coeffs(jpg, H, W)[0] == OK and jc.index(jpg)[0] == OK
+    m = int(segs[1, 1])                                              # the marker that closes segment 1: RST1, before MCU 6
+    assert jpg[m:m + 2] == b"\xff\xd1" and jpg[-2:] == b"\xff\xd9"
+    faults = {
+        "missing RSTn": (jpg[:m], "missing RST1 before MCU 6 (the stream is truncated or has no marker there)"),
+        "wrong RSTn": (jpg[:m + 1] + b"\xd5" + jpg[m + 2:], "wrong restart marker FFD5 before MCU 6, expected RST1"),
+        "missing EOI": (jpg[:-2], "missing EOI after the last MCU (the stream is truncated)"),
+        "another marker where EOI belongs": (jpg[:-1] + b"\xe0", "marker FFE0 after the last MCU where EOI belongs"),
+    }
+    for what, (bad, text) in faults.items():
+        rc, _, _, _, _, msg = jc.index(bad)
+        hrc, _, _, hmsg = jc.host_coeffs(bad, H, W)
+        assert rc == ERR_SHAPE and hrc == ERR_SHAPE, (what, msg, hmsg)
+        assert msg == "kvq_jpeg_index: " + text and hmsg == "kvq_jpeg_coeffs: " + text, (what, msg, hmsg)
+
+
 def test_index_parses_like_the_probe(golden):
     g = golden("mjpeg.npz")
     for name in ("progressive", "s422", "s444", "gray", "cmyk"):

@@ -212,6 +212,25 @@ def test_encode_refusals():
         assert lib.kvq_jpeg_encode(args[0], args[1], H, W, 0, 0, args[2], 64, args[3]) == ERR_NULL
 
 
+@pytest.mark.parametrize("ac_fault", [True, False])
+def test_encode_names_the_first_value_without_a_baseline_code_in_coding_order(ac_fault):
+    """one MCU (six blocks).  Block 1's DC difference has category 12; with ``ac_fault`` block 0 also carries AC values of category 11 at
+    zigzag positions 5 and 9, and block 0, position 5 comes first in coding order"""
+    lib = _abi.lib()
+    H = W = 16
+    coef = np.zeros((6, 64), np.int16)
+    coef[1:4, 0] = 2048                                                                   # Y01 against Y00's 0; Y10, Y11 repeat it: difference 0
+    if ac_fault:
+        coef[0, jpeg_ref.ZIGZAG[5]], coef[0, jpeg_ref.ZIGZAG[9]] = -1500, 1024
+    rc, n, _ = lib_encode(coef, kernels.jpeg_quant_tables(50), H, W)
+    msg = lib.kvq_last_error().decode()
+    assert rc == ERR_UNSUPPORTED and n == 0
+    if ac_fault:
+        assert msg == "kvq_jpeg_encode: coefficient -1500 (plane 0, block 0, zigzag position 5) is outside baseline's +-1023", msg
+    else:
+        assert msg == "kvq_jpeg_encode: DC difference 2048 (plane 0, block 1) is outside baseline's +-2047", msg
+
+
 @pytest.mark.parametrize("name", UNALIGNED)
 def test_a_foreign_decoder_opens_what_the_library_writes(analysed, name):
     Image = pytest.importorskip("PIL.Image")

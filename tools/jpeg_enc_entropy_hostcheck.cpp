@@ -8,7 +8,6 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -I include tools/jpeg_enc_entropy_hostcheck.cpp
 //       kvq-challenge-cvpr-ntire2024_amd/csrc/jpeg_enc.cpp -o /tmp/jpeg_enc_entropy_hostcheck
 //   /tmp/jpeg_enc_entropy_hostcheck /tmp/jpeg_enc_fixtures/*.rgb
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,19 +15,7 @@
 
 #include <vector>
 
-#include "kvq_hip.h"
-
-// what common.cpp provides inside the library
-static thread_local char g_err[512] = "";
-namespace kvq {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-}  // namespace kvq
-extern "C" const char* kvq_last_error(void) { return g_err; }
+#include "jpeg_hostcheck_common.hpp"      // set_error / kvq_last_error (g_err), read_file, read_rgb_planar
 
 // int16 coefficients of one frame: 6 blocks of 64 per 16 x 16 MCU (kvq_jpeg_coef_bytes lives in csrc/jpeg.cpp, which this does not link)
 static size_t coef_elems(int H, int W) { return (size_t)((H + 15) / 16) * ((W + 15) / 16) * 384; }
@@ -130,17 +117,8 @@ static int check_pixels(const char* what, const uint8_t* planar, int T, int H, i
 
 static int check_file(const char* path) {
   int H = 0, W = 0, q = 0;
-  const char* us = strrchr(path, 'x');
-  while (us && us > path && us[-1] >= '0' && us[-1] <= '9') --us;
-  if (!us || sscanf(us, "%dx%d_q%d.rgb", &H, &W, &q) != 3) return fail(path, "name does not end in _<H>x<W>_q<quality>.rgb", 0);
-  FILE* f = fopen(path, "rb");
-  if (!f) return fail(path, "cannot open", 0);
-  std::vector<uint8_t> rgb((size_t)H * W * 3), planar(rgb.size());
-  const size_t got = fread(rgb.data(), 1, rgb.size(), f);
-  fclose(f);
-  if (got != rgb.size()) return fail(path, "shorter than H x W x 3 bytes", 0);
-  for (size_t i = 0; i < (size_t)H * W; ++i)
-    for (int c = 0; c < 3; ++c) planar[(size_t)c * H * W + i] = rgb[3 * i + c];
+  std::vector<uint8_t> planar;
+  if (const char* why = read_rgb_planar(path, H, W, q, planar)) return fail(path, why, 0);
   return check_pixels(path, planar.data(), 1, H, W, q, 0, 0, false);
 }
 

@@ -10,7 +10,6 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -I include tools/jpeg_enc_hostcheck.cpp
 //       kvq-challenge-cvpr-ntire2024_amd/csrc/jpeg_enc.cpp kvq-challenge-cvpr-ntire2024_amd/csrc/jpeg.cpp -o /tmp/jpeg_enc_hostcheck
 //   /tmp/jpeg_enc_hostcheck /tmp/jpeg_enc_fixtures/*.rgb
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,19 +17,7 @@
 
 #include <vector>
 
-#include "kvq_hip.h"
-
-// what common.cpp provides inside the library
-static thread_local char g_err[512] = "";
-namespace kvq {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-}  // namespace kvq
-extern "C" const char* kvq_last_error(void) { return g_err; }
+#include "jpeg_hostcheck_common.hpp"      // set_error / kvq_last_error (g_err), read_file, read_rgb_planar
 
 static int fail(const char* what, const char* step, int rc) {
   fprintf(stderr, "FAIL %s: %s (status %d, message '%s')\n", what, step, rc, g_err);
@@ -64,23 +51,11 @@ static int check_frame(const char* what, const uint8_t* src, int format, int H, 
 
 static int check_file(const char* path) {
   int H = 0, W = 0, q = 0;
-  const char* us = strrchr(path, 'x');
-  while (us && us > path && us[-1] >= '0' && us[-1] <= '9') --us;
-  if (!us || sscanf(us, "%dx%d_q%d.rgb", &H, &W, &q) != 3) return fail(path, "name does not end in _<H>x<W>_q<quality>.rgb", 0);
-  FILE* f = fopen(path, "rb");
-  if (!f) return fail(path, "cannot open", 0);
-  std::vector<uint8_t> rgb((size_t)H * W * 3);
-  const size_t got = fread(rgb.data(), 1, rgb.size(), f);
-  fclose(f);
-  if (got != rgb.size()) return fail(path, "shorter than H x W x 3 bytes", 0);
-  uint8_t* planar = (uint8_t*)malloc(rgb.size());
-  for (size_t i = 0; i < (size_t)H * W; ++i)
-    for (int c = 0; c < 3; ++c) planar[(size_t)c * H * W + i] = rgb[3 * i + c];
+  std::vector<uint8_t> planar;
+  if (const char* why = read_rgb_planar(path, H, W, q, planar)) return fail(path, why, 0);
   uint16_t qt[192];
-  int bad = kvq_jpeg_quant_tables(q, qt) != KVQ_OK ? fail(path, "tables", 0) : 0;
-  if (!bad) bad = check_frame(path, planar, KVQ_SRC_U8, H, W, qt, 0, 0);
-  free(planar);
-  return bad;
+  if (kvq_jpeg_quant_tables(q, qt) != KVQ_OK) return fail(path, "tables", 0);
+  return check_frame(path, planar.data(), KVQ_SRC_U8, H, W, qt, 0, 0);
 }
 
 int main(int argc, char** argv) {

@@ -9,7 +9,6 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -I include
 //       tools/jpeg_hostcheck.cpp kvq-challenge-cvpr-ntire2024_amd/csrc/jpeg.cpp -o /tmp/jpeg_hostcheck
 //   /tmp/jpeg_hostcheck /tmp/jpeg_fixtures/*.jpg
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,19 +16,7 @@
 
 #include <vector>
 
-#include "kvq_hip.h"
-
-// what common.cpp provides inside the library
-static thread_local char g_err[512] = "";
-namespace kvq {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-}  // namespace kvq
-extern "C" const char* kvq_last_error(void) { return g_err; }
+#include "jpeg_hostcheck_common.hpp"      // set_error / kvq_last_error (g_err), read_file, read_rgb_planar
 
 static int fail(const char* file, const char* what, long k, int rc) {
   fprintf(stderr, "FAIL %s: %s (prefix %ld, status %d, message '%s')\n", file, what, k, rc, g_err);
@@ -37,12 +24,8 @@ static int fail(const char* file, const char* what, long k, int rc) {
 }
 
 static int check_file(const char* path) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return fail(path, "cannot open", -1, 0);
   std::vector<uint8_t> data;
-  uint8_t chunk[4096];
-  for (size_t n; (n = fread(chunk, 1, sizeof(chunk), f)) > 0;) data.insert(data.end(), chunk, chunk + n);
-  fclose(f);
+  if (!read_file(path, data)) return fail(path, "cannot open", -1, 0);
   KvqJpegInfo info;
   const int rc = kvq_jpeg_probe(data.data(), data.size(), &info);
   uint16_t qt[192];
