@@ -134,6 +134,10 @@ int kvq_swin3d_plan_create(const KvqSwinCfg* cfg, int B, int T, int H, int W, in
                            KvqSwinPlan** out);
 void kvq_swin3d_plan_destroy(KvqSwinPlan* plan);
 size_t kvq_swin3d_workspace_bytes(const KvqSwinPlan* plan);
+/* Read-only view of how the forward carves the workspace: out12[2r] = byte offset, out12[2r + 1] = bytes the region was sized
+ * for (before its round-up to 256), r = x0, x1 (the fp32 / fp16 residual streams), ln (16-bit LayerNorm rows), big (im2col rows,
+ * q | k | v, MLP hidden), o (attention output), sk (split-K scratch).  For tests of the layout; no launch reads it. */
+int kvq_swin3d_workspace_regions(const KvqSwinPlan* plan, uint64_t out12[12]);
 /* Output geometry: C_out, D, H', W' of the (B, C_out, D, H', W') feature map. */
 int kvq_swin3d_out_dims(const KvqSwinPlan* plan, int32_t out4[4]);
 
@@ -1078,6 +1082,29 @@ void kvq_convnet_destroy(KvqConvNet* net);
  * (SlowFast_features.py writes per-clip .npy files the reference computes at batch 1) switches it off. */
 int kvq_convnet_splitk(KvqConvNet* net, int enable);
 size_t kvq_convnet_workspace_bytes(const KvqConvNet* net);
+/* Read-only view of the plan's workspace layout and lane ordering, for tests that check them against an independent restatement.
+ * Slots are the caller's tensor table followed by the plan's internal ones (the packed input of STEM8 / STEM_MFMA).
+ * Call with slots = ops = NULL for the counts in *info, then with arrays of that capacity. */
+typedef struct {
+  uint64_t off, bytes;    /* byte range inside the workspace (bytes rounded up to 256) */
+  int32_t in_workspace;   /* 0: a caller's input pointer, or a slot no op writes */
+  int32_t reserved;
+} KvqNetSlotLayout;
+typedef struct {
+  int32_t lane;
+  int32_t wait_op;        /* index of the other lane's op whose event this op's stream waits for before it runs, or -1 */
+  int32_t n_reads, n_writes;
+  int32_t reads[4], writes[4];   /* the slots the lane ordering takes the op to read / write */
+  int32_t uses_scratch;   /* the op may cut K: it gets its lane's split-K scratch */
+  int32_t reserved;
+} KvqNetOpLayout;
+typedef struct {
+  int32_t n_slots, n_ops, n_lanes, reserved;
+  uint64_t ws_bytes;      /* = kvq_convnet_workspace_bytes */
+  uint64_t sk_off, sk_stride, sk_bytes;   /* lane l's split-K scratch: sk_bytes at sk_off + l * sk_stride */
+} KvqNetLayoutInfo;
+int kvq_convnet_layout(const KvqConvNet* net, KvqNetLayoutInfo* info, KvqNetSlotLayout* slots, int slot_capacity, KvqNetOpLayout* ops,
+                       int op_capacity);
 /* inputs[n_inputs]: device pointers of the input slots; outputs[n_outputs]: fp32 device buffers of the MEAN_STD ops */
 int kvq_convnet_forward(const KvqConvNet* net, const void* const* inputs, float* const* outputs, void* workspace,
                         size_t workspace_bytes, void* stream);

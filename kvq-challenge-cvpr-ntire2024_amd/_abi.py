@@ -191,6 +191,20 @@ class KvqHeadTrainArgs(C.Structure):
                 ("score", p_void), ("dscore", p_void), ("grads", p_void)]
 
 
+class KvqNetSlotLayout(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("bytes", C.c_uint64), ("in_workspace", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KvqNetOpLayout(C.Structure):
+    _fields_ = [("lane", C.c_int32), ("wait_op", C.c_int32), ("n_reads", C.c_int32), ("n_writes", C.c_int32), ("reads", C.c_int32 * 4),
+                ("writes", C.c_int32 * 4), ("uses_scratch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KvqNetLayoutInfo(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("n_ops", C.c_int32), ("n_lanes", C.c_int32), ("reserved", C.c_int32), ("ws_bytes", C.c_uint64),
+                ("sk_off", C.c_uint64), ("sk_stride", C.c_uint64), ("sk_bytes", C.c_uint64)]
+
+
 class KvqProfRecord(C.Structure):
     _fields_ = [("kind", C.c_int32), ("variant", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -205,6 +219,7 @@ SYMBOLS = {
     "kvq_swin3d_plan_create": (i32, [C.POINTER(KvqSwinCfg), i32, i32, i32, i32, i32, C.POINTER(p_void)]),
     "kvq_swin3d_plan_destroy": (None, [p_void]),
     "kvq_swin3d_workspace_bytes": (sz, [p_void]),
+    "kvq_swin3d_workspace_regions": (i32, [p_void, C.POINTER(C.c_uint64 * 12)]),
     "kvq_swin3d_out_dims": (i32, [p_void, C.POINTER(i32 * 4)]),
     "kvq_vit_embed_ln": (i32, [p_void, p_void, p_void, p_void, p_void, i32, i32, i32, f32, p_void, p_void]),
     "kvq_mha_small": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void]),
@@ -224,6 +239,7 @@ SYMBOLS = {
     "kvq_convnet_destroy": (None, [p_void]),
     "kvq_convnet_splitk": (i32, [p_void, i32]),
     "kvq_convnet_workspace_bytes": (sz, [p_void]),
+    "kvq_convnet_layout": (i32, [p_void, C.POINTER(KvqNetLayoutInfo), C.POINTER(KvqNetSlotLayout), i32, C.POINTER(KvqNetOpLayout), i32]),
     "kvq_convnet_forward": (i32, [p_void, C.POINTER(p_void), C.POINTER(p_void), p_void, sz, p_void]),
     "kvq_qkv_fill_pad": (i32, [p_void, p_void, p_void, i32, i32, i32, i32, C.c_float, i32, p_void]),
     "kvq_fast_bottleneck_pack_bytes": (sz, [i32, i32, i32, i32, i32]),

@@ -136,6 +136,50 @@ extern "C" int kvq_convnet_profile_read(const KvqConvNet* net, float* ms, int ca
 
 extern "C" size_t kvq_convnet_workspace_bytes(const KvqConvNet* net) { return net ? net->ws_bytes : 0; }
 
+namespace kvq {
+// the slots an op reads and writes, as the lane ordering of kvq_convnet_create and kvq_convnet_layout see them
+static void slots_of(const NetOpState& o, int* rd, int& nr, int* wr, int& nw) {
+  nr = nw = 0;
+  rd[nr++] = o.op.src;
+  if (o.op.kind == KVQ_NET_CONV && o.op.src2 >= 0) rd[nr++] = o.op.src2;
+  if (o.tmp >= 0) { rd[nr++] = o.tmp; wr[nw++] = o.tmp; }
+  if (o.op.kind != KVQ_NET_MEAN_STD) wr[nw++] = o.op.dst;
+  if (o.op.kind == KVQ_NET_CONV && o.op.dst32 >= 0) wr[nw++] = o.op.dst32;
+}
+}  // namespace kvq
+
+extern "C" int kvq_convnet_layout(const KvqConvNet* net, KvqNetLayoutInfo* info, KvqNetSlotLayout* slots, int slot_capacity,
+                                  KvqNetOpLayout* ops, int op_capacity) {
+  using namespace kvq;
+  KVQ_REQUIRE(net && info, KVQ_ERR_NULL, "kvq_convnet_layout: NULL pointer");
+  const int n_slots = (int)net->tensors.size(), n_ops = (int)net->ops.size();
+  *info = KvqNetLayoutInfo{};
+  info->n_slots = n_slots; info->n_ops = n_ops; info->n_lanes = net->lane1 ? 2 : 1;
+  info->ws_bytes = net->ws_bytes; info->sk_off = net->sk_off; info->sk_stride = net->sk_stride; info->sk_bytes = net->sk_bytes;
+  if (!slots && !ops) return KVQ_OK;
+  KVQ_REQUIRE(slots && ops && slot_capacity >= n_slots && op_capacity >= n_ops, KVQ_ERR_SHAPE,
+              "kvq_convnet_layout: room for %d slots and %d ops, the plan has %d and %d", slot_capacity, op_capacity, n_slots, n_ops);
+  for (int s = 0; s < n_slots; ++s) {
+    const NetTensorState& t = net->tensors[s];
+    slots[s] = KvqNetSlotLayout{};
+    slots[s].in_workspace = s >= net->n_inputs && t.placed ? 1 : 0;
+    if (slots[s].in_workspace) { slots[s].off = t.off; slots[s].bytes = t.bytes; }
+  }
+  for (int i = 0; i < n_ops; ++i) {
+    const NetOpState& o = net->ops[i];
+    KvqNetOpLayout& l = ops[i];
+    l = KvqNetOpLayout{};
+    l.lane = o.op.lane;
+    l.wait_op = -1;
+    // what the forward does: it waits for sync[wait_ev], which is recorded behind the op whose signal_ev that is
+    for (int j = 0; j < n_ops && o.wait_ev >= 0; ++j)
+      if (net->ops[j].signal_ev == o.wait_ev) l.wait_op = j;
+    slots_of(o, l.reads, l.n_reads, l.writes, l.n_writes);
+    l.uses_scratch = o.op.kind == KVQ_NET_CONV && net->sk_on && net->sk_bytes ? 1 : 0;
+  }
+  return KVQ_OK;
+}
+
 extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTensor* tensors, int n_tensors, int n_inputs,
                                   int n_outputs, int dtype, KvqConvNet** out) {
   using namespace kvq;
@@ -308,14 +352,6 @@ extern "C" int kvq_convnet_create(const KvqNetOp* ops, int n_ops, const KvqNetTe
 #undef NET_REQUIRE
   // ---- which lanes touch which slot ----
   bool two_lanes = false;
-  auto slots_of = [&](const NetOpState& o, int* rd, int& nr, int* wr, int& nw) {
-    nr = nw = 0;
-    rd[nr++] = o.op.src;
-    if (o.op.kind == KVQ_NET_CONV && o.op.src2 >= 0) rd[nr++] = o.op.src2;
-    if (o.tmp >= 0) { rd[nr++] = o.tmp; wr[nw++] = o.tmp; }
-    if (o.op.kind != KVQ_NET_MEAN_STD) wr[nw++] = o.op.dst;
-    if (o.op.kind == KVQ_NET_CONV && o.op.dst32 >= 0) wr[nw++] = o.op.dst32;
-  };
   for (const NetOpState& o : net->ops) {
     int rd[4], wr[4], nr, nw;
     slots_of(o, rd, nr, wr, nw);

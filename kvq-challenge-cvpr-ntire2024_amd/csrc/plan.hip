@@ -73,6 +73,7 @@ struct KvqSwinPlan {
   std::vector<void*> owned;      // device allocations to free
   size_t ws_bytes;
   size_t off_x0, off_x1, off_ln, off_big, off_o, off_sk, sk_bytes;   // off_sk: split-K scratch of the un-fused GEMMs
+  size_t region_bytes[6];        // what x0 | x1 | ln | big | o | sk were sized for, before the 256-byte round-up (kvq_swin3d_workspace_regions)
   unsigned char* run_ws;         // workspace of the forward in progress (for the GEMM helper)
   int table_len, center;
   std::vector<float*> taps;      // feats[i] destinations (kvq_swin3d_set_taps), empty = none
@@ -290,6 +291,8 @@ extern "C" int kvq_swin3d_plan_create(const KvqSwinCfg* cfg, int B, int T, int H
     const size_t BL = (size_t)B * g.L, BLp = (size_t)B * g.Lp;
     max_x = std::max(max_x, BL * g.C);
     max_ln = std::max(max_ln, std::max(BLp * g.C, BL * g.C));
+    // the un-fused merge's LayerNorm writes Ln rows of 4C here: 4 Ln > L when H or W is odd, and Lp == L gives no slack
+    if (i < cfg->num_stages - 1) max_ln = std::max(max_ln, (size_t)B * g.Dn * g.Hn * g.Wn * 4 * g.C);
     max_big = std::max(max_big, std::max(BLp * 3 * g.C, BL * (size_t)cfg->mlp_ratio * g.C));
     max_o = std::max(max_o, BLp * g.C);
     {   // GEMM shapes of this stage that may run split-K (long K, few tiles: stage 3 of the trunk)
@@ -310,6 +313,8 @@ extern "C" int kvq_swin3d_plan_create(const KvqSwinCfg* cfg, int B, int T, int H
   pl->off_o = off; off += align_up(max_o * 2);
   pl->off_sk = off; off += align_up(max_sk);
   pl->sk_bytes = max_sk;
+  const size_t sized[6] = {max_x * 4, max_x * 4, max_ln * 2, max_big * 2, max_o * 2, max_sk};
+  memcpy(pl->region_bytes, sized, sizeof(sized));
   pl->run_ws = nullptr;
   pl->ws_bytes = off;
   *out = pl;
@@ -324,6 +329,13 @@ extern "C" void kvq_swin3d_plan_destroy(KvqSwinPlan* pl) {
 }
 
 extern "C" size_t kvq_swin3d_workspace_bytes(const KvqSwinPlan* pl) { return pl ? pl->ws_bytes : 0; }
+
+extern "C" int kvq_swin3d_workspace_regions(const KvqSwinPlan* pl, uint64_t out12[12]) {
+  KVQ_REQUIRE(pl && out12, KVQ_ERR_NULL, "kvq_swin3d_workspace_regions: NULL");
+  const size_t offs[6] = {pl->off_x0, pl->off_x1, pl->off_ln, pl->off_big, pl->off_o, pl->off_sk};
+  for (int r = 0; r < 6; ++r) { out12[2 * r] = offs[r]; out12[2 * r + 1] = pl->region_bytes[r]; }
+  return KVQ_OK;
+}
 
 extern "C" int kvq_swin3d_out_dims(const KvqSwinPlan* pl, int32_t out4[4]) {
   using namespace kvq;

@@ -52,8 +52,8 @@ class _Alloc:
 
 
 class Registry:
-    def __init__(self, device_type, empty, payload=PAYLOAD_BYTE):
-        self.device_type, self._empty, self.payload = device_type, empty, payload
+    def __init__(self, device_type, empty, payload=PAYLOAD_BYTE, max_guard=None):
+        self.device_type, self._empty, self.payload, self.max_guard = device_type, empty, payload, max_guard
         self.allocs = []
 
     # ---------------------------------------------------------------------------------------------------------- allocation
@@ -67,6 +67,8 @@ class Registry:
         padded = -(-nbytes // 16) * 16
         last = shape[-1] if shape else 1
         guard = -(-max(MIN_GUARD, 32 * last * item) // ALIGN) * ALIGN
+        if self.max_guard is not None:
+            guard = min(guard, -(-max(MIN_GUARD, self.max_guard) // ALIGN) * ALIGN)
         buf = self._empty(ALIGN + guard + padded + guard, dtype=torch.uint8, device=device)
         start = (-buf.data_ptr()) % ALIGN + guard
         buf.fill_(fill)
@@ -116,11 +118,13 @@ class Registry:
 
 
 @contextlib.contextmanager
-def guarded(device_type="cuda", payload=PAYLOAD_BYTE):
+def guarded(device_type="cuda", payload=PAYLOAD_BYTE, max_guard=None):
     """patch ``torch.empty`` / ``torch.empty_like`` for ``device_type`` tensors; yields the registry.  Calls for another device
-    type, or with keywords other than ``dtype`` / ``device``, go straight to the originals, which are put back on exit."""
+    type, or with keywords other than ``dtype`` / ``device``, go straight to the originals, which are put back on exit.
+    ``max_guard``: an upper limit in bytes for a guard (whole-model forwards allocate flat byte buffers of many megabytes — workspaces,
+    weight images — whose "32 rows" would be 32 times the buffer)."""
     orig_empty, orig_empty_like = torch.empty, torch.empty_like
-    G = Registry(device_type, orig_empty, payload)
+    G = Registry(device_type, orig_empty, payload, max_guard)
 
     def _device_type(device):
         if device is None:
