@@ -11,7 +11,9 @@ Differences that are deliberate: frames come through the package's frame reader 
 [T,H,W,3] stacks otherwise — no codec ships in this image; ``--fps`` or a ``<video>.fps`` file gives a stack's frame rate);
 the network weights are a pytorchvideo hub download in the reference (:140): pass ``--weights <state_dict.pth>`` (pytorchvideo
 key names under ``feature_extraction.``), else seeded random weights; ``--synthetic N`` writes N seeded random clips instead of
-reading videos (smoke runs).  The SlowFast-R50 network runs as HIP kernels (``slowfast_model.py``); there is no CPU path."""
+reading videos (smoke runs); ``--transform device`` resizes and normalises the frames on the device instead of with PIL on the host
+(``kvq_amd/datasets/slowfast_clips.py::device_clips``: the same clips, bit for bit; ``.y4m`` and Motion-JPEG files never become RGB
+on the host), in the main process.  The SlowFast-R50 network runs as HIP kernels (``slowfast_model.py``); there is no CPU path."""
 import argparse
 import os
 import sys
@@ -21,7 +23,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kvq_amd  # noqa: E402,F401
-from kvq_amd.datasets.slowfast_clips import VideoDataset_NR_SlowFast_feature, extract_video, pil_transform  # noqa: E402
+from kvq_amd.datasets.slowfast_clips import (VideoDataset_NR_SlowFast_feature, device_clips, extract_video, pil_transform,  # noqa: E402
+                                             read_video_names)
 from kvq_amd.models.backbones.slowfast_model import pack_pathway_output, slowfast  # noqa: E402,F401
 
 
@@ -37,6 +40,11 @@ def main(config, video_root, videos_csv):
         g = np.random.Generator(np.random.PCG64(config.seed))
         items = [([torch.from_numpy(g.standard_normal((32, 3, config.resize, config.resize)).astype(np.float32))
                    for _ in range(config.synthetic)], config.video_name)]
+    elif config.transform == "device":
+        from kvq_amd.datasets.fusion_datasets import open_video
+        print("--transform device: the frames are prepared in the main process, --num_workers is ignored", file=sys.stderr)
+        paths = [(os.path.join(video_root, name), name) for name in read_video_names(videos_csv)]
+        items = ((device_clips(open_video(path), path, config.resize, device, config.fps), name) for path, name in paths)
     else:
         trainset = VideoDataset_NR_SlowFast_feature(config, pil_transform(config.resize), video_root, videos_csv)
         items = torch.utils.data.DataLoader(trainset, batch_size=None, shuffle=False, num_workers=config.num_workers)
@@ -66,6 +74,9 @@ if __name__ == "__main__":
     parser.add_argument("--small_grid_mean", action="store_true",
                         help="reduced-size smoke runs: a final grid under the head's AvgPool3d kernel (--resize < 224) gets the global "
                              "mean instead of the error the reference raises there")
+    parser.add_argument("--transform", choices=("host", "device"), default="host",
+                        help="where the frames are resized and normalised: host = PIL in the DataLoader workers (the reference); device = "
+                             "kvq_resize_pil, bit-equal, in the main process")
     config = parser.parse_args()
     if not config.synthetic and (config.video_root is None or config.video_csv is None):
         parser.error("--video_root and --video_csv are required (or --synthetic N)")

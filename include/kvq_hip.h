@@ -879,6 +879,32 @@ int kvq_resize_bilinear_aa(const void* video, int src_is_u8, int C, int T, int H
  * start[out], size[out] and the normalised weights[out][*kmax] (zero past size). */
 int kvq_resize_aa_taps(int in_size, int out_size, int32_t* kmax, int32_t* start, int32_t* size, float* weights);
 
+/* Pillow's Image.resize((ow, oh), BILINEAR) on uint8 RGB frames, to the bit: the frame transform of the motion-feature extractor
+ * (SlowFast_features.py: Resize([r, r]) on a PIL image + ToTensor + Normalize).  A fixed-point two-pass triangle filter — per axis
+ * in -> out, in double: scale = in / out, fs = support = max(scale, 1); output index i: center = (i + 0.5) scale, window
+ * [max(int(center - support + 0.5), 0), min(int(center + support + 0.5), in)), w_j = max(0, 1 - |(j + xmin - center + 0.5) / fs|)
+ * normalised by their sum, k_j = (int)(w_j 2^22 + 0.5); one pass = clip8((sum px_j k_j + 2^21) >> 22); the width pass first, its result
+ * a uint8 image, the height pass on that image (an axis that keeps its size has coefficients {2^22, 0}: its pass changes nothing).
+ *   frames      src_format KVQ_SRC_U8: uint8 frame-major INTERLEAVED (T, H, W, 3) (not the planar (C, T, H, W) of the other entries);
+ *               a KVQ_SRC_I420_* value: T I420 frames, converted where they are loaded (bit-equal to kvq_yuv420_to_rgb + the uint8 path)
+ *   x / y tables  kvq_resize_pil_taps(W, ow) / (H, oh) on the device: start[out], size[out], coef[out][kmax], int32
+ *   lut256      256 fp32 on the device: every resized byte b is written as lut256[b] (0..255 gives the bytes back)
+ *   out         fp32, frame t channel c at out + t frame_stride + c chan_stride (elements), oh x ow contiguous; the strides must
+ *               keep the 3 T planes apart (KVQ_ERR_SHAPE)
+ * One launch, no workspace, no atomics, no host synchronisation.  T in 1..65535, sides <= KVQ_RESIZE_PIL_MAX_AXIS, H W < 2^29; tables,
+ * lut256 and out 4-byte aligned (frames: any address), else KVQ_ERR_SHAPE.  KVQ_ERR_UNSUPPORTED before any launch for a source row wider
+ * than the 16 KiB stage (W > 5456) or a geometry whose tables and one-row band do not fit the LDS; kvq_resize_pil_supported (host
+ * only, 1 / 0) answers the same question.  The windows of the tables are clamped to the axis on the device: a table of another
+ * geometry gives wrong pixels, not a fault.
+ * kvq_resize_pil_taps (host only, no HIP): *kmax = the tap capacity per output index; when start / size / coef are given they receive
+ * start[out], size[out] and coef[out][*kmax] (zero past size). */
+#define KVQ_RESIZE_PIL_MAX_AXIS 65535
+int kvq_resize_pil_taps(int in_size, int out_size, int32_t* kmax, int32_t* start, int32_t* size, int32_t* coef);
+int kvq_resize_pil_supported(int src_format, int T, int H, int W, int oh, int ow);
+int kvq_resize_pil(const void* frames, int src_format, int T, int H, int W, int oh, int ow, const int32_t* xstart,
+                   const int32_t* xsize, const int32_t* xcoef, const int32_t* ystart, const int32_t* ysize, const int32_t* ycoef,
+                   const float* lut256, float* out, int64_t frame_stride, int64_t chan_stride, void* stream);
+
 /* get_spatial_fragments' fallback for sources smaller than the canvas (fusion_datasets.py:43-50): F.interpolate(video / 255.0,
  * scale_factor = s, mode = "bilinear") * 255.0 cast back to the frame type (uint8: truncation), with ATen's CPU arithmetic to the
  * bit.  video u8|fp32 (C,T,H,W) -> out of the same type (C,T,floor(H*s),floor(W*s)) — kvq_upsample_frames_out_dims gives the size. */

@@ -315,6 +315,10 @@ SYMBOLS = {
     "kvq_resize_bilinear_aa": (i32, [p_void, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32),
                                      C.POINTER(f32), p_void, p_void]),
     "kvq_resize_aa_taps": (i32, [i32, i32, C.POINTER(i32), p_void, p_void, p_void]),
+    "kvq_resize_pil_taps": (i32, [i32, i32, C.POINTER(i32), p_void, p_void, p_void]),
+    "kvq_resize_pil_supported": (i32, [i32] * 6),
+    "kvq_resize_pil": (i32, [p_void, i32, i32, i32, i32, i32, i32, p_void, p_void, p_void, p_void, p_void, p_void, p_void, p_void, i64, i64,
+                             p_void]),
     "kvq_upsample_frames_out_dims": (i32, [i32, i32, C.c_double, C.POINTER(i32 * 2)]),
     "kvq_upsample_frames": (i32, [p_void, i32, i32, i32, i32, i32, C.c_double, p_void, p_void]),
     "kvq_im2col_nd": (i32, [p_void, i32, i32, C.POINTER(i64 * 5), C.POINTER(i32 * 5), C.POINTER(i32 * 3),

@@ -1090,12 +1090,12 @@ class MjpegWriter:
         self._file.close()
 
 
-def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601", jpeg_entropy=None):
+def _sampled_clips(path, samplers, is_train, device, yuv_matrix="bt601", jpeg_entropy=None, vr=None):
     """Reference ``spatial_temporal_view_decomposition`` (:376-397), decode half: one reader, every frame fetched once and
     sent to the device once, as uint8; per view a uint8 (3, T, H, W) device tensor (frame gather + layout change in HBM) +
     the sampled indices.  I420 frames (a ``.y4m`` file): per view a ``kernels.I420Frames`` — a gather of whole frames, no
-    layout change and no conversion here."""
-    vr = open_video(path, yuv_matrix)
+    layout change and no conversion here.  ``vr``: the video already opened (a caller that reads it for more than the views)."""
+    vr = open_video(path, yuv_matrix) if vr is None else vr
     frame_inds = {k: s(len(vr), is_train) for k, s in samplers.items()}
     uniq = np.unique(np.concatenate(list(frame_inds.values()), 0))
     frames = _frames_to_device(vr, uniq, device, jpeg_entropy)                 # (n, H, W, 3) uint8
@@ -1130,7 +1130,17 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
     """Reference class of the same name (fusion_datasets.py:786-927): csv ``filename,label`` with a header row, per
     video the ``simpleVQA`` view (resize 520 -> centre crop 448, normalised with the ImageNet constants on 0-255
     pixels — reproduced as-is) and ``feat`` = 8 rows of SlowFast features from
-    ``data_prefix_3D/<video_name>/feature_{i}_{slow,fast}_feature.npy``.  Same dict keys."""
+    ``data_prefix_3D/<video_name>/feature_{i}_{slow,fast}_feature.npy``.  Same dict keys.
+
+    Not in the reference — ``motion_features: {source: files | inline, weights: <state_dict.pth> | null, resize: 224, fps: null,
+    small_grid_mean: false}``: absent or ``source: files`` is the behaviour above.  ``inline``: ``data_prefix_3D`` may be absent and
+    ``feat`` is computed from the video itself, which is opened once per item for the view and for the features: the clips of
+    ``slowfast_clips.device_clips`` (frames resized on the device as Pillow resizes them) through one SlowFast-R50 that the dataset
+    builds lazily on its device, the first 8 clips' features as an fp32 DEVICE tensor [8, 2304 | 2048 | 256].  ``weights`` loads as
+    ``SlowFast_features.py --weights`` does; null = that tool's seeded random weights, with a warning on stderr."""
+
+    MOTION_SOURCES = ("files", "inline")
+    MOTION_KEYS = ("source", "weights", "resize", "fps", "small_grid_mean")
 
     def __init__(self, opt, namelist=None, device=None):
         import csv
@@ -1139,7 +1149,16 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
         self.opt, self.namelist, self.device = opt, namelist, _default_device(device)
         if opt.get("jpeg_entropy") is not None:          # yml data.<split>.args.jpeg_entropy: refused here, not at the first item
             jpeg_entropy_mode(opt["jpeg_entropy"])
-        self.ann_file, self.data_prefix, self.data_prefix_3D = opt["anno_file"], opt["data_prefix"], opt["data_prefix_3D"]
+        mf = opt.get("motion_features") or {}
+        if not isinstance(mf, dict) or set(mf) - set(self.MOTION_KEYS):
+            raise ValueError(f"motion_features: expected a mapping with the keys {', '.join(self.MOTION_KEYS)}, got {mf!r}")
+        self.motion = dict(source=mf.get("source", "files"), weights=mf.get("weights"), resize=int(mf.get("resize", 224)), fps=mf.get("fps"),
+                           small_grid_mean=bool(mf.get("small_grid_mean", False)))
+        if self.motion["source"] not in self.MOTION_SOURCES:
+            raise ValueError(f"motion_features.source must be one of {', '.join(self.MOTION_SOURCES)}, got {self.motion['source']!r}")
+        self._motion_model = None
+        self.ann_file, self.data_prefix = opt["anno_file"], opt["data_prefix"]
+        self.data_prefix_3D = opt.get("data_prefix_3D") if self.motion["source"] == "inline" else opt["data_prefix_3D"]
         self.sample_types, self.feature_type, self.phase = opt["sample_types"], opt["feature_type"], opt["phase"]
         self.augment = opt.get("augment", False)
         if self.phase == "train" or self.augment:
@@ -1172,11 +1191,39 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
                                    for p in parts]))
         return torch.stack(rows)
 
+    def motion_model(self):
+        """the SlowFast-R50 of ``motion_features.source: inline`` on the dataset's device, built at its first use"""
+        if self._motion_model is None:
+            import sys
+            from ..models.backbones.slowfast_model import slowfast
+            model = slowfast().to(self.device).eval()
+            if self.motion["small_grid_mean"]:
+                model.head_small_grid = "mean"
+            if self.motion["weights"]:
+                model.load_state_dict(torch.load(self.motion["weights"], map_location="cpu"), strict=False)
+            else:
+                print("motion_features.weights is null: the SlowFast features come from seeded random weights", file=sys.stderr)
+            self._motion_model = model
+        return self._motion_model
+
+    def _features_inline(self, vr, path):
+        """[8, 2304 | 2048 | 256] fp32 on the device: the first 8 clips of the opened video through ``device_clips`` and the network"""
+        from .slowfast_clips import VIDEO_CLIP_MIN, device_clips, extract_features
+        clips = device_clips(vr, path, self.motion["resize"], self.device, self.motion["fps"], self.opt.get("jpeg_entropy"))
+        slow, fast = extract_features(self.motion_model(), clips[:VIDEO_CLIP_MIN], self.device)
+        parts = {"Slow": (slow,), "Fast": (fast,), "SlowFast": (slow, fast)}[self.feature_type]
+        return torch.cat([p.reshape(p.shape[0], -1).float() for p in parts], 1)
+
     def __getitem__(self, index):
         info = self.video_infos[index]
-        feat = self._features(info["video_name"])
+        vr = None
+        if self.motion["source"] == "inline":
+            vr = open_video(info["filename"], self.opt.get("yuv_matrix", "bt601"))
+            feat = self._features_inline(vr, info["filename"])
+        else:
+            feat = self._features(info["video_name"])
         video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"),
-                                            self.opt.get("jpeg_entropy"))
+                                            self.opt.get("jpeg_entropy"), vr)
         data = {}
         for stype, sopt in self.sample_types.items():
             kw = dict(sopt, phase="test")

@@ -4,7 +4,12 @@ at least 8 clips per video (the last one repeated), every frame ``Resize([r, r])
 
 Host-side index logic and the PIL transform (the reference runs them in DataLoader workers); the frames come from the
 package's frame reader (``open_video``: decord when installed, uint8 ``[T, H, W, 3]`` ``.npy`` stacks otherwise).  The
-network itself runs on the device (``models/backbones/slowfast_model.py``)."""
+network itself runs on the device (``models/backbones/slowfast_model.py``).
+
+``device_clips`` is the same clip assembly without the host transform: the used frames go to the device as the reader holds them
+(uint8 RGB, I420 of a ``.y4m`` file, Motion-JPEG through the entropy decode and the IDCT on the device), ``kernels.resize_pil``
+resizes them as Pillow does, to the bit, and writes ToTensor + Normalize through a 256-entry table, and the clips are index
+gathers on the device — bit-equal to ``VideoDataset_NR_SlowFast_feature`` (tests/test_gpu_resize_pil.py)."""
 from __future__ import annotations
 
 import csv
@@ -108,22 +113,83 @@ class VideoDataset_NR_SlowFast_feature(torch.utils.data.Dataset):  # noqa: N801 
         return [torch.stack([done[int(i)] for i in c]) for c in clips], name
 
 
+DEVICE_CHUNK = 64            # frames per staging round of ``device_clips``: 64 x 1080p RGB = 398 MB of pinned memory at most
+_LUT = {}
+
+
+def _transform_lut(device):
+    """``kernels.slowfast_lut()`` on ``device``, made once"""
+    from .. import kernels
+    key = str(device)
+    if key not in _LUT:
+        _LUT[key] = kernels.slowfast_lut().to(device)
+    return _LUT[key]
+
+
+def device_clips(reader, path: str, resize: int, device, fps: Optional[float] = None, jpeg_entropy=None) -> List[torch.Tensor]:
+    """The clips of ``VideoDataset_NR_SlowFast_feature.__getitem__`` for the opened video ``reader`` (``open_video(path)``), made on
+    ``device``: list of (32, 3, resize, resize) fp32 device tensors, bit-equal to the host path.  ``clip_frame_indices`` unchanged;
+    the UNIQUE used frames go up through ``_frames_to_device`` at most ``DEVICE_CHUNK`` at a time (pinned staging stays bounded)
+    and through ``kernels.resize_pil`` into one (n, 3, r, r) tensor; a clip is an index gather of it.  A repeated padding clip is
+    the same tensor object, so ``extract_video`` computes it once.  ``fps``: as ``frame_rate_of``'s default."""
+    from .. import kernels
+    from .fusion_datasets import _frames_to_device
+    device = torch.device(device)
+    rate = frame_rate_of(reader, path, fps)
+    clips = clip_frame_indices(len(reader), rate)
+    uniq = np.unique(np.concatenate(clips))
+    lut = _transform_lut(device)
+    frames = torch.empty(len(uniq), 3, resize, resize, dtype=torch.float32, device=device)
+    for a in range(0, len(uniq), DEVICE_CHUNK):
+        src = _frames_to_device(reader, uniq[a:a + DEVICE_CHUNK], device, jpeg_entropy)
+        kernels.resize_pil(src, resize, resize, lut, out=frames[a:a + DEVICE_CHUNK])
+    made, out = {}, []
+    for c in clips:                       # the padding to 8 clips repeats the same index array: one gather, one tensor
+        if id(c) not in made:
+            made[id(c)] = frames.index_select(0, torch.from_numpy(np.searchsorted(uniq, c).astype(np.int64)).to(device))
+        out.append(made[id(c)])
+    return out
+
+
 def extract_video(model, clips: List[torch.Tensor], device, batch: int = 8):
-    """clips: list of (32, 3, r, r) fp32 -> list of (slow (1,2048,1,1,1), fast (1,256,1,1,1)) numpy pairs, one per clip
+    """clips: list of (32, 3, r, r) fp32, on the host or already on the device (``device_clips``) -> list of (slow (1,2048,1,1,1),
+    fast (1,256,1,1,1)) numpy pairs, one per clip
     (:189-197).  Clips are stacked ``batch`` at a time (the clips are independent; repeated padding clips are computed once)."""
-    uniq, order = [], []
-    for c in clips:                       # the padding to 8 clips repeats the LAST clip: compute it once
-        if uniq and (uniq[-1] is c or torch.equal(uniq[-1], c)):
-            order.append(len(uniq) - 1)
-        else:
-            order.append(len(uniq))
-            uniq.append(c)
-    feats = []
+    uniq, order = _distinct(clips)
+    slow, fast = _forward_unique(model, uniq, device, batch)
+    slow, fast = slow.cpu().numpy(), fast.cpu().numpy()
+    return [(slow[j:j + 1], fast[j:j + 1]) for j in order]
+
+
+def _forward_unique(model, uniq, device, batch):
+    """the network on the distinct clips ``uniq``, ``batch`` at a time -> (slow (n, 2048, 1, 1, 1), fast (n, 256, 1, 1, 1)) on the device"""
+    slows, fasts = [], []
     model.split_k = False           # a clip's features must not depend on which clips share its forward (10 clips run as 8 + 2)
     with torch.no_grad():
         for a in range(0, len(uniq), batch):
             ele = torch.stack(uniq[a:a + batch]).permute(0, 2, 1, 3, 4).contiguous().to(device)      # (b, 3, 32, r, r)   (:193)
             slow, fast = model.forward_clips(ele)
-            slow, fast = slow.cpu().numpy(), fast.cpu().numpy()
-            feats += [(slow[k:k + 1], fast[k:k + 1]) for k in range(slow.shape[0])]
-    return [feats[j] for j in order]
+            slows.append(slow)
+            fasts.append(fast)
+    return torch.cat(slows), torch.cat(fasts)
+
+
+def _distinct(clips):
+    """(distinct clips in order, position of every clip among them): the padding to 8 clips repeats the LAST clip"""
+    uniq, order = [], []
+    for c in clips:
+        # (device clips repeat the tensor object itself; comparing their values would cost a launch and a wait per clip)
+        if uniq and (uniq[-1] is c or (not c.is_cuda and torch.equal(uniq[-1], c))):
+            order.append(len(uniq) - 1)
+        else:
+            order.append(len(uniq))
+            uniq.append(c)
+    return uniq, order
+
+
+def extract_features(model, clips: List[torch.Tensor], device, batch: int = 8):
+    """as ``extract_video`` with the features left on the device: (slow (n, 2048, 1, 1, 1), fast (n, 256, 1, 1, 1)), one row per clip"""
+    uniq, order = _distinct(clips)
+    slow, fast = _forward_unique(model, uniq, device, batch)
+    idx = torch.tensor(order, dtype=torch.int64, device=slow.device)
+    return slow.index_select(0, idx), fast.index_select(0, idx)

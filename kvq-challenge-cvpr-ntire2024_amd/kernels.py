@@ -1370,6 +1370,79 @@ def resize_aa_taps(in_size: int, out_size: int):
     return start, size, w
 
 
+def resize_pil_taps(in_size: int, out_size: int):
+    """The tap tables of one axis of ``resize_pil`` (``kvq_resize_pil_taps``: built on the host in double):
+    (start int32 [out], size int32 [out], coefficients int32 [out, kmax] with 22 fractional bits; zero past size)."""
+    import numpy as np
+    k = C.c_int32()
+    check(lib().kvq_resize_pil_taps(in_size, out_size, C.byref(k), None, None, None), "kvq_resize_pil_taps")
+    start, size = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
+    coef = np.zeros((out_size, k.value), np.int32)
+    check(lib().kvq_resize_pil_taps(in_size, out_size, C.byref(k), start.ctypes.data, size.ctypes.data, coef.ctypes.data),
+          "kvq_resize_pil_taps")
+    return start, size, coef
+
+
+_PIL_TAPS = {}          # (in, out, device) -> (start, size, coef) on the device
+
+
+def _resize_pil_taps_on(in_size: int, out_size: int, device):
+    """the tables of an axis on ``device``: built and uploaded once per (in, out)"""
+    key = (int(in_size), int(out_size), str(device))
+    if key not in _PIL_TAPS:
+        _PIL_TAPS[key] = tuple(torch.from_numpy(a).to(device) for a in resize_pil_taps(in_size, out_size))
+    return _PIL_TAPS[key]
+
+
+def slowfast_lut() -> torch.Tensor:
+    """The 256-entry table of the motion-feature transform (``datasets/slowfast_clips.py::pil_transform``): ToTensor + Normalize(.45,
+    .225) of every byte value, by the torch expression the host path applies, on the CPU — so the device never restates ATen's scalar
+    arithmetic (a CPU ``div`` by a scalar multiplies by the reciprocal) and equals the host path by construction."""
+    t = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    return (t - 0.45) / 0.225
+
+
+def identity_lut() -> torch.Tensor:
+    """0..255 as fp32: ``resize_pil`` gives the resized bytes back"""
+    return torch.arange(256, dtype=torch.float32)
+
+
+def resize_pil_supported(frames, oh: int, ow: int) -> bool:
+    i420 = isinstance(frames, I420Frames)
+    T, H, W = (frames.shape[1], frames.H, frames.W) if i420 else frames.shape[:3]
+    return bool(lib().kvq_resize_pil_supported(frames.format if i420 else _abi.SRC_U8, T, H, W, oh, ow))
+
+
+def resize_pil(frames, oh: int, ow: int, lut: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pillow's ``Image.resize((ow, oh), BILINEAR)`` of every frame, to the bit, each resized byte written as ``lut[byte]``
+    (``kvq_resize_pil``, one launch).  ``frames``: uint8 (T, H, W, 3) interleaved on the device, or ``I420Frames`` (converted where
+    the launch loads them).  ``lut``: fp32 (256,) on the device (``slowfast_lut()``, ``identity_lut()``).  -> fp32 (T, 3, oh, ow);
+    ``out``: an fp32 (T, 3, oh, ow) view to write instead, with any frame and channel strides and contiguous oh x ow planes."""
+    i420 = isinstance(frames, I420Frames)
+    if i420:
+        src, fmt, T, H, W = frames.data, frames.format, frames.shape[1], frames.H, frames.W
+    else:
+        src, fmt = frames, _abi.SRC_U8
+        if not (torch.is_tensor(src) and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()):
+            raise ValueError("resize_pil: expected contiguous uint8 (T, H, W, 3) frames or I420Frames, got "
+                             f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+        T, H, W = src.shape[:3]
+    _need_gpu(src, lut, out)
+    oh, ow = int(oh), int(ow)
+    if not (lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous() and lut.device == src.device):
+        raise ValueError("resize_pil: lut must be 256 contiguous fp32 values on the frames' device")
+    if out is None:
+        out = torch.empty(T, 3, oh, ow, dtype=torch.float32, device=src.device)
+    elif not (out.dtype == torch.float32 and tuple(out.shape) == (T, 3, oh, ow) and out.device == src.device
+              and (out.stride(3) == 1 or ow == 1) and (out.stride(2) == ow or oh == 1)):
+        raise ValueError(f"resize_pil: out must be an fp32 ({T}, 3, {oh}, {ow}) view with contiguous planes on the frames' device")
+    xs, xn, xk = _resize_pil_taps_on(W, ow, src.device)
+    ys, yn, yk = _resize_pil_taps_on(H, oh, src.device)
+    check(lib().kvq_resize_pil(ptr(src), fmt, T, H, W, oh, ow, ptr(xs), ptr(xn), ptr(xk), ptr(ys), ptr(yn), ptr(yk), ptr(lut), ptr(out),
+                               out.stride(0) if T > 1 else 3 * max(out.stride(1), oh * ow), out.stride(1), stream_of(src)), "kvq_resize_pil")
+    return out
+
+
 def upsample_frames(video: torch.Tensor, scale_factor: float):
     """get_spatial_fragments' small-source fallback (fusion_datasets.py:43-50): F.interpolate(video / 255.0, scale_factor,
     mode="bilinear") * 255.0 cast back to the frame type, ATen-CPU-exact.  video u8|fp32 (C,T,H,W) -> same type, upsampled."""
