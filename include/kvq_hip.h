@@ -1220,6 +1220,25 @@ int kvq_headtrain_loss(const float* score, const float* label, int B, float rank
 int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float wd,
                         int step, void* stream);
 
+/* ---- simpleVQAHead training step on features of a frozen trunk (csrc/simple_headtrain.hip): the reference's head
+ * (head.py:10-31: Linear(C -> 128), Linear(128 -> 1) per frame, mean over the frames; no activation, no dropout) and the gradients of its
+ * four parameters.  The loss and the optimiser are the kvq_headtrain_loss and kvq_headtrain_adamw entries above.  All fp32, no atomics:
+ * two runs are bit-equal.  The entries take KvqHeadTrainArgs with
+ *
+ *   feat     fp32 [B][T][C], dense, 16-byte aligned; L carries T, the frames of a video
+ *   params   W1 [128][C] | b1 [128] | w2 [128] | b2 [1], 16-byte aligned; grads has the same layout and is written in full
+ *   p_drop   0 (the head has no dropout); seed and step are not read
+ *
+ * Shapes: hidden == 128, C a multiple of 64, p_drop == 0, 16-byte alignment: otherwise KVQ_ERR_UNSUPPORTED.  2 <= B <= 1024, T >= 1,
+ * B * T <= 2^24: otherwise KVQ_ERR_SHAPE.  A workspace below the workspace_bytes entry's answer (0 for a shape that is not built):
+ * KVQ_ERR_WORKSPACE.  NULL: KVQ_ERR_NULL.  All of it is checked on the host before the first launch.  The backward reads feat, params
+ * and dscore only: it needs no forward before it, and the two calls may share one workspace.
+ * Workspace, in floats: 2 C + ceil4(B T nseg) + nchunks C, with nseg = ceil(C / 1024), chunk = max(32, ceil8(ceil(B T / 32))),
+ * nchunks = ceil(B T / chunk). */
+size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int hidden);
+int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* host_args, void* stream);
+int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* host_args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -367,6 +367,9 @@ SYMBOLS = {
     "kvq_headtrain_mask": (i32, [C.c_uint32, C.c_uint32, i32, f32, i64, p_void, p_void]),
     "kvq_headtrain_loss": (i32, [p_void, p_void, i32, f32, p_void, p_void, p_void]),
     "kvq_headtrain_adamw": (i32, [p_void, p_void, p_void, p_void, p_void, i64, f32, f32, i32, p_void]),
+    "kvq_simple_headtrain_workspace_bytes": (sz, [i32] * 4),
+    "kvq_simple_headtrain_forward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
+    "kvq_simple_headtrain_backward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
 }
 
 _lib: Optional[C.CDLL] = None

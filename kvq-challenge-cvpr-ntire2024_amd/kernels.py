@@ -1748,3 +1748,53 @@ def headtrain_adamw(params, grads, exp_avg, exp_avg_sq, ema, lr, wd, step):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
     check(lib().kvq_headtrain_adamw(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), ptr(ema), n, float(lr), float(wd), int(step),
                                     stream_of(params)), "kvq_headtrain_adamw")
+
+
+# ---- simpleVQAHead training step (csrc/simple_headtrain.hip): thin wrappers; kvq_amd/finetune.py drives them; the loss and the optimiser
+# are headtrain_loss and headtrain_adamw above ---------------------------------------------------------------------------------------------
+def simple_headtrain_param_count(C_in: int, hidden: int = 128) -> int:
+    """length of the flat parameter vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]"""
+    return hidden * C_in + 2 * hidden + 1
+
+
+def simple_headtrain_workspace(B: int, T: int, C_in: int, hidden: int = 128, device=None) -> torch.Tensor:
+    """the workspace the forward and the backward of one (B, T, C) share; raises for a shape that is not built"""
+    n = int(lib().kvq_simple_headtrain_workspace_bytes(B, T, C_in, hidden))
+    if n == 0:
+        raise _abi.KvqError(f"kvq_simple_headtrain: shape B={B} T={T} C={C_in} hidden={hidden} is not built "
+                            "(2 <= B <= 1024, C a multiple of 64, hidden 128)")
+    return torch.empty(n // 4, dtype=torch.float32, device=device if device is not None else "cuda")
+
+
+def _simple_headtrain_args(feat, params, ws, score=None, dscore=None, grads=None, hidden=128):
+    _need_gpu(feat, params, ws, score, dscore, grads)
+    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous(), "features: dense fp32 [B][T][C]"
+    B, T, Cc = feat.shape
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == simple_headtrain_param_count(Cc, hidden)
+    a = _abi.KvqHeadTrainArgs()
+    a.feat, a.B, a.L, a.C, a.hidden, a.params = ptr(feat), B, T, Cc, hidden, ptr(params)
+    a.p_drop, a.seed, a.step = 0.0, 0, 0
+    a.workspace, a.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
+    a.score, a.dscore, a.grads = ptr(score), ptr(dscore), ptr(grads)
+    return a
+
+
+def simple_headtrain_forward(feat, params, ws, score=None):
+    """scores fp32 [B] of features [B][T][C] under the flat parameters: the mean over the T frames of the two Linears"""
+    if score is None:
+        score = torch.empty(feat.shape[0], dtype=torch.float32, device=feat.device)
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == feat.shape[0]
+    a = _simple_headtrain_args(feat, params, ws, score=score)
+    check(lib().kvq_simple_headtrain_forward(C.byref(a), stream_of(feat)), "kvq_simple_headtrain_forward")
+    return score
+
+
+def simple_headtrain_backward(feat, params, ws, dscore, grads=None):
+    """the flat gradient (layout of ``params``, written in full) from ``dscore`` [B]; needs no forward before it"""
+    if grads is None:
+        grads = torch.empty_like(params)
+    assert dscore.dtype == torch.float32 and dscore.is_contiguous() and dscore.numel() == feat.shape[0]
+    assert grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == params.numel()
+    a = _simple_headtrain_args(feat, params, ws, dscore=dscore, grads=grads)
+    check(lib().kvq_simple_headtrain_backward(C.byref(a), stream_of(feat)), "kvq_simple_headtrain_backward")
+    return grads

@@ -2,7 +2,8 @@
 :10-31).  Parameter names/shapes are the reference's; forward calls libkvq_hip.so.
 ``forward`` is the eval-mode head: dropout is the identity (``model.eval()`` in ``trainer.py:257,303``).  The train-mode head
 (dropout on the features and behind the GELU), its losses and its optimiser step live in ``kvq_amd/finetune.py``
-(``HeadFinetuner``, csrc/headtrain.hip), which works on a ``VQAHead``'s parameters and writes the trained ones back into them."""
+(``HeadFinetuner``, csrc/headtrain.hip), which works on a ``VQAHead``'s parameters and writes the trained ones back into them;
+``SimpleHeadFinetuner`` (csrc/simple_headtrain.hip) does the same for a ``simpleVQAHead``."""
 from __future__ import annotations
 
 import torch

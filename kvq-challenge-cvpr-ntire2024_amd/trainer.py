@@ -7,8 +7,9 @@ Differences that are deliberate:
   * one process per GPU (``torch.distributed.run``) instead of ``nn.DataParallel``: videos are sharded
     ``videos[rank::world]`` and ONE all-gather of the score vector runs at the end;
   * scores stay on the device until the end (no per-video ``.item()`` sync, ``trainer.py:329``).
-Training: ``finetune_head()`` fits the ``VQAHead`` on features of the frozen trunk (kvq_amd/finetune.py: the reference's losses, AdamW,
-schedule, EMA and best-checkpoint rule); gradients into a backbone are out of scope.
+Training: ``finetune_head()`` fits the head (a ``VQAHead``, or the ``simpleVQAHead`` of model key ``simpleVQA``) on features of the
+frozen trunk (kvq_amd/finetune.py: the reference's losses, AdamW, schedule, EMA and best-checkpoint rule); gradients into a backbone
+are out of scope.
 """
 from __future__ import annotations
 
@@ -536,12 +537,12 @@ class Trainer:
 
     # ---- head fine-tuning on the frozen trunk (the reference's train.py / train_eval_all_epoches for the head's parameters) ----------
     def finetune_head(self):
-        """The reference's yml schema: ``num_epochs``, ``l_num_epochs``, ``warmup_epochs``, ``batch_size`` (clips per batch), ``ema``,
+        """The reference's yml schema: ``num_epochs``, ``l_num_epochs``, ``warmup_epochs``, ``batch_size`` (samples per batch: clips of a ``VQAHead`` model, videos of ``simpleVQA``), ``ema``,
         ``save_model``, ``optimizer.{lr, wd, backbone_lr_mult}``, ``data.train`` (sampled deterministically, ``phase: test``) and
         ``data.val``.  After every epoch the trained head and the EMA head are scored on ``data.val`` with the ``inferece_val``
         metrics and kept by the rule of trainer.py:223-230 in ``{resume}/{name}_head_{test_set}_{n|s}_finetuned.pth``.
         -> (best of the trained head, best of the EMA head), each (SRCC, PLCC, KRCC, RMSE)."""
-        from .finetune import HeadFinetuner
+        from .finetune import finetuner_for
         cfg, opt = self.config, self.config["optimizer"]
         if opt.get("backbone_lr_mult", 0) != 0:
             raise NotImplementedError(f"optimizer.backbone_lr_mult = {opt['backbone_lr_mult']}: this engine trains the head on a frozen "
@@ -549,17 +550,18 @@ class Trainer:
         if self.world > 1:
             raise NotImplementedError("finetune_head() runs on one rank")
         key = self.key_list[0]
+        Finetuner = finetuner_for(getattr(self.model, key + "_head", None))       # VQAHead: HeadFinetuner; simpleVQAHead: its own
         tcfg = cfg["data"]["train"]
         train_ds = getattr(_datasets, tcfg["type"])(dict(tcfg["args"], phase="test"), None, device=self.device)
         use_ema = bool(cfg.get("ema", True))
-        ft = HeadFinetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=use_ema, seed=int(cfg.get("seed", 0)),
+        ft = Finetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=use_ema, seed=int(cfg.get("seed", 0)),
                            rank_weight=float(cfg.get("rank_weight", 0.0)))
         ft.cache_features(train_ds, self)
         n = sum(f.shape[0] for f in ft.feats)
         bs = int(cfg["batch_size"])
         per_epoch = n // bs + (1 if n % bs >= 3 else 0)
         ft.set_schedule(int(cfg["warmup_epochs"] * per_epoch), int((cfg["num_epochs"] + cfg["l_num_epochs"]) * per_epoch))
-        val = HeadFinetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=False)       # the cache of data.val's features
+        val = Finetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=False)       # the cache of data.val's features
         val.cache_features(self.val_dataset, self)
         resume, test_set = getattr(self.args, "resume", "./checkpoint/"), getattr(self.args, "test_set", "val")
         save = bool(cfg.get("save_model", True))

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Drop-in for the reference's ``train.py`` (:21-76): same flags (-o/--opt, -t/--train_set, -t1/--test_set, -r/--resume, --gpu_id), same
-yml schema, same checkpoint files and metric lines.  What trains is the ``VQAHead`` on features of the frozen trunk
-(``Trainer.finetune_head``): ``optimizer.backbone_lr_mult`` must be 0.
+yml schema, same checkpoint files and metric lines.  What trains is the head (``VQAHead``, or ``simpleVQAHead`` for model key
+``simpleVQA``) on features of the frozen trunk (``Trainer.finetune_head``): ``optimizer.backbone_lr_mult`` must be 0.
 
     python train.py -o config/kwai_swin_grpb_synthetic_finetune.yml -r ./checkpoint/ --gpu_id 0
+    python train.py -o config/kwai_simpleVQA_synthetic_finetune.yml -r ./checkpoint/ --gpu_id 0
 """
 import argparse
 import os
