@@ -241,7 +241,7 @@ enum {
 };
 typedef struct {
   int32_t kind;     /* KVQ_K_*                                                                    */
-  int32_t variant;  /* kernel instantiation: GEMM (MI*100+BK)*10+epilogue; attention 2*gated+mask */
+  int32_t variant;  /* kernel instantiation: GEMM kvq_gemm_kernel_choice*10+epilogue; attention 2*gated+mask */
   float ms;         /* hipEventElapsedTime around the launch, on the launch stream                */
   double flops;     /* algorithmic flops of the launch (2MNK; attention 4*rows*N*C)               */
   double bytes;     /* algorithmic HBM bytes of the launch (operands read once, result written once) */
@@ -323,11 +323,21 @@ int kvq_gemm_bf16(const KvqGemmArgs* host_args, void* stream);
  * subnormal).  host_args as for KVQ_EPI_RESID_F32 — `epilogue` must be KVQ_EPI_RESID_F32 or KVQ_EPI_RESID_SCALE_F32, the scatter map
  * and split-K apply as there; with col_scale == 1 the result is bit-equal to KVQ_EPI_RESID_F32.  KvqGemmArgs is unchanged. */
 int kvq_gemm_resid_scaled(const KvqGemmArgs* host_args, const float* col_scale, void* stream);
-/* Which main loop kvq_gemm_bf16 / kvq_conv_implicit take (process-wide; returns the previous mode): -1 = by shape (default; the
- * 256 x 256 x 64 eight-phase kernel of csrc/gemm256.hip when the tile grid fills the chip, else the 128 x 128 x 32 ring kernel),
- * 0 = never the wide tile, 1 = the wide tile whenever the shape is eligible (K % 64 == 0, K >= 128).  Any other value only reads.
- * Initial value: environment KVQ_GEMM8P.  Used by the parity tests to run every epilogue through both kernels. */
+/* Whether kvq_gemm_bf16 may take the 256 x 256 x 64 eight-phase kernel of csrc/gemm256.hip (process-wide; returns the previous
+ * mode): -1 = by shape (default: where the tile grid fills the chip), 0 = never the wide tile, 1 = the wide tile whenever the
+ * shape is eligible (K % 64 == 0, K >= 128).  Any other value only reads.  Initial value: environment KVQ_GEMM8P.  Everything else
+ * goes to the ring kernel of csrc/gemm.hip, whose tile follows the shape alone.  The parity tests of tests/test_gpu_kernels.py run
+ * every epilogue on the 64 x 64 x 32 ring tile (-1) and on the wide tile (1); tests/test_gpu_gemm_variants.py reaches each other
+ * form with modes -1 and 0 and shapes that tests/test_gemm_choice_cpu.py pins to their forms through kvq_gemm_kernel_choice. */
 int kvq_gemm_tile_mode(int mode);
+/* Host only: the main loop kvq_gemm_bf16 (conv = 0) or kvq_conv_implicit (conv != 0; M = B*Do*Ho*Wo, K = Kpad, epilogue unused)
+ * launches for this shape and epilogue under the current tile mode; the launchers switch on this very value.
+ *   MI*1000 + NI*100 + BK   ring kernel, tile 64 MI x 64 NI, BK-deep slices: 1132, 2132, 2232, 2264, 3264, 2464
+ *   22264                   ring kernel, 128 x 128 x 64 on a 2-slice ring (KVQ_EPI_QKV_BF16 only)
+ *   4464                    the 256 x 256 x 64 eight-phase kernel
+ * A split-K launch (kvq_gemm_splitk_factor > 1 and a scratch buffer) runs the same main loop with the fp32 store, then the
+ * reduce launch.  0: a shape the launch refuses (M, N, K <= 0, N % 8, K % 32).  KvqProfRecord.variant carries code * 10 + epilogue. */
+int kvq_gemm_kernel_choice(int M, int N, int K, int epilogue, int conv);
 /* Diagnostic: while dev_buf != NULL every GEMM block b < max_blocks writes uint64 stamps
  * dev_buf[8*b + {0:start, 1:first slice landed, 2:K loop done, 3:epilogue done}] (shader clock) and
  * [4] = XCC id << 32 | HW_ID.  Pass NULL to switch it off. */

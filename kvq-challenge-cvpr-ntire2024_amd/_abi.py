@@ -271,6 +271,7 @@ SYMBOLS = {
     "kvq_gemm_splitk_bytes": (sz, [i32, i32, i32]),
     "kvq_debug_gemm_trace": (i32, [p_void, i32]),
     "kvq_gemm_tile_mode": (i32, [i32]),
+    "kvq_gemm_kernel_choice": (i32, [i32, i32, i32, i32, i32]),
     "kvq_patch_embed_supported": (i32, [i32] * 8),
     "kvq_patch_embed_fragments_supported": (i32, [C.POINTER(KvqFragmentSource), i32, i32, i32, i32, i32, i32]),
     "kvq_patch_embed_pack_bytes": (sz, [i32, i32]),

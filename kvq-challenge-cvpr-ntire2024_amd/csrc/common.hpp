@@ -203,9 +203,13 @@ __device__ __forceinline__ uint32_t gelu_pack2<Fp16>(float lo, float hi) {
 extern unsigned long long* g_trace;
 extern int g_trace_blocks;
 
-// tile variant the GEMM dispatcher picks for a shape: (MI==NI) * 100 + BK  (gemm.hip)
-int gemm_variant(int M, int N, int K);
-// true: kvq_gemm_bf16 takes the 256 x 256 x 64 eight-phase kernel for this shape (gemm256.hip); profile records carry tile code 4464
+// The main loop kvq_gemm_bf16 (conv = false) / kvq_conv_implicit (conv = true) launch for a shape and epilogue under the current
+// tile mode (gemm.hip): MI * 1000 + NI * 100 + BK of the ring kernel's 64 MI x 64 NI x BK tile, or one of the two codes below.
+// The launchers switch on this value, kvq_gemm_kernel_choice exports it and the profile records carry it.
+constexpr int kGemmChoice8p = 4464;          // the 256 x 256 x 64 eight-phase kernel (gemm256.hip)
+constexpr int kGemmChoiceQkvRing2 = 22264;   // 128 x 128 x 64 on a 2-slice ring: the QKV epilogue only
+int gemm_choice(int M, int N, int K, int epilogue, bool conv);
+// true: a plain GEMM of this shape takes the eight-phase kernel (gemm256.hip)
 bool gemm8p_wanted(int M, int N, int K);
 
 // f(Fp16{}) or f(Bf16{}) for a dtype that passed KVQ_REQUIRE_OPERAND: a launch site names its kernel once, as kernel<decltype(e), ...>

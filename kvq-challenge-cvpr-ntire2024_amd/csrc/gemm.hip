@@ -401,8 +401,8 @@ static int splitk_factor(long tiles, int nk, int bk) {
   return S < 1 ? 1 : S;
 }
 
-// tile (MI, NI) for a shape, encoded (10*MI + NI)*100 + BK
-int gemm_variant(int M, int N, int K) {
+// ring tile (MI, NI) for a shape, encoded (10*MI + NI)*100 + BK
+static int gemm_variant(int M, int N, int K) {
   // Measured per shape of the trunk (B = 4 clips, us: 128x128 / 128x64 / 64x64): fc2 stage 2 (K = 1536) 36.7 / 41.4 /
   // 44.3 although 128x128 makes only 294 workgroups; qkv stage 3 25.6 / 31.0 / 35.1 (450 workgroups); proj stage 2
   // (K = 384, epilogue-dominated) 25.0 / 21.3 / 20.2; merge stage 0 (N = 192 = 1.5 tiles of 128) 28.0 / 24.7 / 28.1.
@@ -427,15 +427,22 @@ int gemm_variant(int M, int N, int K) {
   return ((rem != 0 && rem <= 64) ? 21 : 22) * 100 + 32;
 }
 
-// the tile grid and slice count of the variant launch_gemm / launch_conv would pick
+// The one place that names the launch (common.hpp).  The implicit-GEMM convolution has the 32-deep ring tiles only (a slice =
+// 4 chunks = at most 4 taps): a shape the plain GEMM would give a 64-deep tile takes 128 x 128 x 32.
+// 128 x 128 with 64-deep slices and a 2-slice ring (64 KB, 2 workgroups per CU; whole 128-B lines per DMA row), QKV only:
+// measured per epilogue on the trunk's shapes - qkv stage 2: 28 -> 26 us, stage 3: 25 -> 22; fc1 equal; fc2 +2 us
+int gemm_choice(int M, int N, int K, int epilogue, bool conv) {
+  const int var = gemm_variant(M, N, K);
+  if (conv) return var % 100 == 64 ? 2232 : var;
+  if (gemm8p_wanted(M, N, K)) return kGemmChoice8p;
+  if (epilogue == KVQ_EPI_QKV_BF16 && var == 2232 && K % 64 == 0) return kGemmChoiceQkvRing2;
+  return var;
+}
+
+// the ring tile grid and slice count split-K is sized by: those of the tile launch_gemm / launch_conv would pick by shape
 static void variant_tiles(int M, int N, int K, bool conv, long* tiles, int* nk, int* bk_out) {
-  int var = gemm_variant(M, N, K);
-  int bk = var % 100, mi = var / 1000, ni = (var / 100) % 10;
-  if (conv) {
-    const int v = var / 100;
-    if (v != 22 && v != 21 && v != 12 && v != 11) { mi = 2; ni = 2; }
-    bk = 32;
-  }
+  const int var = conv ? gemm_choice(M, N, K, KVQ_EPI_STORE_F32, true) : gemm_variant(M, N, K);
+  const int bk = var % 100, mi = var / 1000, ni = (var / 100) % 10;
   *tiles = (long)ceil_div(M, 64 * mi) * ceil_div(N, 64 * ni);
   *nk = K / bk;
   *bk_out = bk;
@@ -447,26 +454,27 @@ static int finish_splitk(const GemmParams& p, const float* partial, int S, hipSt
   return launch("splitk_reduce_kernel", splitk_reduce_kernel<E>, grid_1d(chunks), dim3(256), 0, st, p, partial, S, (int)EPI);
 }
 
+static int unknown_choice(const char* who, int choice) {
+  set_error("%s: no kernel for main-loop code %d", who, choice);
+  return KVQ_ERR_UNSUPPORTED;
+}
+
 template <typename E, int EPI>
 static int launch_gemm_variant(const GemmParams& p, hipStream_t st) {
-  if (gemm8p_wanted(p.M, p.N, p.K)) return launch_gemm8p<E, EPI>(p, st);
-  const int var = gemm_variant(p.M, p.N, p.K);
-  // 128x128 with 64-deep slices and a 2-slice ring (64 KB, 2 workgroups per CU; whole 128-B lines per DMA row):
-  // measured per epilogue on the trunk's shapes — qkv stage 2: 28 -> 26 us, stage 3: 25 -> 22; fc1 equal; fc2 +2 us
-  if (EPI == KVQ_EPI_QKV_BF16 && var == 2232 && p.K % 64 == 0) return launch_one<E, 2, 2, 64, EPI, 2>(p, st);
-  if (var % 100 == 64) {
-    switch (var / 100) {
-      case 22: return launch_one<E, 2, 2, 64, EPI>(p, st);
-      case 32: return launch_one<E, 3, 2, 64, EPI>(p, st);
-      default: return launch_one<E, 2, 4, 64, EPI>(p, st);
-    }
+  const int choice = gemm_choice(p.M, p.N, p.K, EPI, false);
+  switch (choice) {
+    case kGemmChoice8p: return launch_gemm8p<E, EPI>(p, st);
+    case kGemmChoiceQkvRing2:
+      if constexpr (EPI == KVQ_EPI_QKV_BF16) return launch_one<E, 2, 2, 64, EPI, 2>(p, st);
+      break;
+    case 2264: return launch_one<E, 2, 2, 64, EPI>(p, st);
+    case 3264: return launch_one<E, 3, 2, 64, EPI>(p, st);
+    case 2464: return launch_one<E, 2, 4, 64, EPI>(p, st);
+    case 2232: return launch_one<E, 2, 2, 32, EPI>(p, st);
+    case 2132: return launch_one<E, 2, 1, 32, EPI>(p, st);
+    case 1132: return launch_one<E, 1, 1, 32, EPI>(p, st);
   }
-  switch (var / 100) {
-    case 22: return launch_one<E, 2, 2, 32, EPI>(p, st);
-    case 21: return launch_one<E, 2, 1, 32, EPI>(p, st);
-    case 12: return launch_one<E, 1, 2, 32, EPI>(p, st);
-    default: return launch_one<E, 1, 1, 32, EPI>(p, st);
-  }
+  return unknown_choice("kvq_gemm_bf16", choice);
 }
 
 // split-K around a variant launcher: partial tiles (STORE_F32 instantiation of the same variant) + the reduce / epilogue launch
@@ -476,25 +484,24 @@ static int launch_maybe_split(const GemmParams& p, hipStream_t st);
 template <typename E, int EPI>
 static int launch_gemm(const GemmParams& p, hipStream_t st) { return launch_maybe_split<E, EPI, false>(p, st); }
 
-// implicit-GEMM convolution: the 32-deep variants only (a slice = 4 chunks = at most 4 taps)
+// implicit-GEMM convolution: the 32-deep tiles, each as a tap walk and as a tap-table kernel
 template <typename E, int EPI>
 static int launch_conv_variant(const GemmParams& p, hipStream_t st) {
-  int var = gemm_variant(p.M, p.N, p.K) / 100;
-  if (var != 22 && var != 21 && var != 12 && var != 11) var = 22;
+  const int choice = gemm_choice(p.M, p.N, p.K, EPI, true);
   if (!p.taps) {                // C % 32 == 0, full tap set: the kernel walks the taps with wave-uniform counters
-    switch (var) {
-      case 22: return launch_one<E, 2, 2, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
-      case 21: return launch_one<E, 2, 1, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
-      case 12: return launch_one<E, 1, 2, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
-      default: return launch_one<E, 1, 1, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
+    switch (choice) {
+      case 2232: return launch_one<E, 2, 2, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
+      case 2132: return launch_one<E, 2, 1, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
+      case 1132: return launch_one<E, 1, 1, 32, EPI, KVQ_GEMM_NST, true, true>(p, st);
     }
+    return unknown_choice("kvq_conv_implicit", choice);
   }
-  switch (var) {
-    case 22: return launch_one<E, 2, 2, 32, EPI, KVQ_GEMM_NST, true>(p, st);
-    case 21: return launch_one<E, 2, 1, 32, EPI, KVQ_GEMM_NST, true>(p, st);
-    case 12: return launch_one<E, 1, 2, 32, EPI, KVQ_GEMM_NST, true>(p, st);
-    default: return launch_one<E, 1, 1, 32, EPI, KVQ_GEMM_NST, true>(p, st);
+  switch (choice) {
+    case 2232: return launch_one<E, 2, 2, 32, EPI, KVQ_GEMM_NST, true>(p, st);
+    case 2132: return launch_one<E, 2, 1, 32, EPI, KVQ_GEMM_NST, true>(p, st);
+    case 1132: return launch_one<E, 1, 1, 32, EPI, KVQ_GEMM_NST, true>(p, st);
   }
+  return unknown_choice("kvq_conv_implicit", choice);
 }
 
 template <typename E, int EPI>
@@ -545,6 +552,11 @@ extern "C" int kvq_gemm_splitk_factor(int M, int N, int K) {
   return kvq::splitk_factor(tiles, nk, bk);
 }
 
+extern "C" int kvq_gemm_kernel_choice(int M, int N, int K, int epilogue, int conv) {
+  if (M <= 0 || N <= 0 || K <= 0 || N % 8 || K % 32) return 0;
+  return kvq::gemm_choice(M, N, K, epilogue, conv != 0);
+}
+
 extern "C" size_t kvq_gemm_splitk_bytes(int M, int N, int K) {
   // the conv front end may pick a different tile for the same (M, N, K): size for the larger factor of the two
   if (M <= 0 || N <= 0 || K <= 0 || K % 32) return 0;
@@ -590,7 +602,8 @@ int kvq::gemm_launch(const KvqGemmArgs* a, RangeFlag range, hipStream_t stream, 
               "kvq_gemm_bf16: a_gather needs M = n_batch * a_rows, a_phys_rows >= a_rows, no split-K");
   KVQ_REQUIRE(a->ldc != 0 || a->col_off == 0, KVQ_ERR_SHAPE, "kvq_gemm_bf16: col_off = %d without ldc (the epilogue would write outside the row)",
               a->col_off);
-  KVQ_REQUIRE(a->ldc == 0 || (a->epilogue != KVQ_EPI_QKV_BF16 && a->epilogue != KVQ_EPI_RESID_F32 && a->epilogue != KVQ_EPI_STORE_F32 &&
+  KVQ_REQUIRE(a->ldc == 0 || (a->epilogue != KVQ_EPI_QKV_BF16 && a->epilogue != KVQ_EPI_RESID_F32 && a->epilogue != KVQ_EPI_RESID_SCALE_F32 &&
+                              a->epilogue != KVQ_EPI_STORE_F32 &&
                               a->ldc % 8 == 0 && a->col_off % 8 == 0 && a->col_off >= 0 && a->col_off + a->N <= a->ldc),
               KVQ_ERR_SHAPE, "kvq_gemm_bf16: ldc / col_off need a 16-bit row-major epilogue, multiples of 8, col_off + N <= ldc");
   hipStream_t st = (hipStream_t)stream;

@@ -449,7 +449,7 @@ static int gemm(KvqSwinPlan* pl, hipStream_t st, int kind, const uint16_t* A, co
   // and the trunk's only long-K / few-tile shape (fc2 of stage 3) gains nothing from it (43.6 vs 43.8 us).
   // algorithmic bytes: A + W once, output once (fp32 residual epilogues read-modify-write)
   const double out_b = (epi == KVQ_EPI_RESID_F32) ? 8.0 : (epi == KVQ_EPI_STORE_F32 ? 4.0 : 2.0);
-  Bracket br(pl, st, kind, (gemm8p_wanted(M, N, K) ? 4464 : gemm_variant(M, N, K)) * 10 + epi, 2.0 * M * N * K,
+  Bracket br(pl, st, kind, gemm_choice(M, N, K, epi, false) * 10 + epi, 2.0 * M * N * K,
              2.0 * ((double)M * K + (double)N * K) + out_b * M * N);
   return gemm_launch(&a, range, st);
 }
@@ -721,7 +721,7 @@ static int swin_run(const KvqSwinPlan* cpl, const KvqSwinWeights* w, const float
       KvqGemmArgs pa{};
       pa.A = bo; pa.W = bw.proj_w; pa.bias = bw.proj_b; pa.M = ML; pa.N = C; pa.K = C; pa.epilogue = KVQ_EPI_RESID_F32; pa.out_f32 = cur;
       pa.dtype = pl->dtype; pa.a_gather = g.d_dst[t.par]; pa.a_rows = g.L; pa.a_phys_rows = g.Lp;
-      Bracket br(pl, st, KVQ_K_GEMM_PROJ, gemm_variant(ML, C, C) * 10 + KVQ_EPI_RESID_F32, 2.0 * M * C * C,
+      Bracket br(pl, st, KVQ_K_GEMM_PROJ, gemm_choice(ML, C, C, KVQ_EPI_RESID_F32, false) * 10 + KVQ_EPI_RESID_F32, 2.0 * M * C * C,
                  2.0 * ((double)ML * C + (double)C * C) + 8.0 * ML * C);
       KVQ_TRY(kvq_gemm_bf16(&pa, st));
     } else {

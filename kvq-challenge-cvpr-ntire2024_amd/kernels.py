@@ -60,9 +60,19 @@ def _splitk_scratch(a, M: int, N: int, K: int, device):
     return ws
 
 
+def _concat_dest(out, M: int, ldc: int, col_off: int):
+    """(ldc, col_off) of a launch that writes into a wider 16-bit destination: ``out`` must then be a contiguous [M, ldc] tensor.
+    Which epilogues take them, and which values, is the library's decision (it refuses the rest)."""
+    if ldc and out is not None:
+        assert out.is_contiguous() and out.numel() == M * ldc, "ldc: pass out= as a contiguous [M, ldc] tensor"
+    return int(ldc), int(col_off)
+
+
 def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], epilogue: int, *, out=None,
-         num_heads=0, q_scale=1.0, scatter_map=None, map_rows=0, out_rows=0, a_gather=None, a_rows=0, rows=None, col_scale=None):
+         num_heads=0, q_scale=1.0, scatter_map=None, map_rows=0, out_rows=0, a_gather=None, a_rows=0, rows=None, col_scale=None, ldc=0, col_off=0):
     """A [M,K], W [N,K], both fp16 or both bf16.  Returns the output tensor (allocated unless given).
+    ``ldc`` / ``col_off`` (16-bit row-major epilogues, ``out`` given as [M, ldc]): the N columns land at columns col_off ..
+    col_off+N-1 of rows of ldc elements; the library refuses them for the other epilogues.
     ``col_scale`` (fp32 [N], residual epilogue only): out += col_scale * (A W^T + bias) — ``kvq_gemm_resid_scaled``.
     ``a_gather`` (+ ``a_rows``, ``rows`` = GEMM rows): row m reads A row (m // a_rows) * (A rows per batch) + a_gather[m % a_rows].
     QKV epilogue with ``scatter_map``: GEMM row m lands in row (m // map_rows) * out_rows + scatter_map[m % map_rows] of a buffer
@@ -99,6 +109,7 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], epilogu
     a.num_heads, a.q_scale = num_heads, q_scale
     a.scatter_map, a.map_rows, a.out_rows = ptr(scatter_map), map_rows, out_rows
     a.a_gather, a.a_rows, a.a_phys_rows = ptr(a_gather), a_rows, a_phys
+    a.ldc, a.col_off = _concat_dest(out if out.dtype in HALF_TYPES else None, M, ldc, col_off)
     a.dtype = dtype_code(A.dtype)
     _ws = _splitk_scratch(a, a.M, a.N, a.K, A.device) if (a.epilogue != _abi.EPI_QKV_BF16 and a_gather is None) else None   # noqa: F841
     if col_scale is not None:
@@ -172,6 +183,16 @@ def grn(hid: torch.Tensor, shape, gamma, beta, *, over="th", out=None):
 def gemm_tile_mode(mode: int) -> int:
     """-1: main loop by shape (default), 0: never the 256 x 256 eight-phase tile, 1: whenever eligible.  Returns the previous mode."""
     return lib().kvq_gemm_tile_mode(mode)
+
+
+GEMM_8P, GEMM_QKV_RING2 = 4464, 22264      # kvq_gemm_kernel_choice: the eight-phase kernel; 128 x 128 x 64 on the 2-slice QKV ring
+
+
+def gemm_kernel_choice(M: int, N: int, K: int, epilogue: int = _abi.EPI_BIAS_BF16, conv: bool = False) -> int:
+    """The main loop ``gemm`` / ``conv_gemm`` (conv=False) or ``conv_implicit`` (conv=True, K = the weight's padded K) launch for
+    this shape under the current tile mode: MI*1000 + NI*100 + BK of the ring kernel's 64 MI x 64 NI x BK tile, ``GEMM_QKV_RING2``
+    or ``GEMM_8P``; 0 for a shape the launch refuses.  Host only (no GPU needed)."""
+    return lib().kvq_gemm_kernel_choice(M, N, K, epilogue, int(conv))
 
 
 def qkv_fill_pad(qkv: torch.Tensor, qkv_bias: torch.Tensor, pad_rows: torch.Tensor, n_batch: int, q_scale: float):
@@ -1090,19 +1111,24 @@ def mean_std_pool(x: torch.Tensor, out: torch.Tensor, mean_off: int, std_off: in
     return out
 
 
-def conv_gemm(A: torch.Tensor, W: torch.Tensor, bias, relu: bool, resid=None, resid_f32=None, want_f32=False):
+def conv_gemm(A: torch.Tensor, W: torch.Tensor, bias, relu: bool, resid=None, resid_f32=None, want_f32=False, out=None, ldc=0,
+              col_off=0):
     """out[M,N] = (relu)(A @ W^T + bias (+ resid)), 16-bit operands.  ``resid`` 16-bit / ``resid_f32`` fp32
     identity branch (ReLU epilogue only).  Returns the 16-bit output, or (16-bit, fp32 copy) when
-    ``want_f32`` — the fp32 copy keeps a residual stream un-rounded between blocks."""
-    _need_gpu(A, W, bias, resid, resid_f32)
+    ``want_f32`` — the fp32 copy keeps a residual stream un-rounded between blocks.  ``out`` [M, ldc] with ``ldc`` / ``col_off``:
+    the N columns land at columns col_off .. col_off+N-1 of it (a channel concatenation)."""
+    _need_gpu(A, W, bias, resid, resid_f32, out)
     M, N = A.shape[0], W.shape[0]
-    out = torch.empty(M, N, dtype=A.dtype, device=A.device)
+    if out is None:
+        out = torch.empty(M, N, dtype=A.dtype, device=A.device)
+    assert out.dtype == A.dtype and out.is_contiguous() and out.numel() >= M * N
     out32 = torch.empty(M, N, dtype=torch.float32, device=A.device) if want_f32 else None
     a = _abi.KvqGemmArgs()
     a.A, a.W, a.bias, a.M, a.N, a.K = ptr(A), ptr(W), ptr(bias), M, N, A.shape[1]
     a.epilogue = _abi.EPI_RELU_BF16 if relu else _abi.EPI_BIAS_BF16
     assert relu or (resid is None and resid_f32 is None and not want_f32), "identity add / fp32 copy: ReLU epilogue only"
     a.out_bf16, a.out_f32, a.resid_bf16, a.resid_f32 = ptr(out), ptr(out32), ptr(resid), ptr(resid_f32)
+    a.ldc, a.col_off = _concat_dest(out, M, ldc, col_off)
     a.dtype = dtype_code(A.dtype)
     _ws = _splitk_scratch(a, a.M, a.N, a.K, A.device) if a.epilogue != _abi.EPI_QKV_BF16 else None   # noqa: F841
     check(lib().kvq_gemm_bf16(C.byref(a), current_stream()), "kvq_gemm_bf16")
@@ -1303,12 +1329,14 @@ TAP_TABLE = False      # test hook: True = always hand kvq_conv_implicit a tap t
 
 
 def conv_implicit(x: torch.Tensor, W: torch.Tensor, bias, kernel, stride, pad, relu: bool, resid=None, resid_f32=None,
-                  want_f32=False, store_f32=False, live=None):
+                  want_f32=False, store_f32=False, live=None, out=None, ldc=0, col_off=0):
     """Conv (+ folded BN, + identity, + ReLU) on a channels-last 16-bit activation x (B, D, H, W, C), C % 8 == 0, without a
     patch matrix: W [N][Kpad] with the (kd,kh,kw,c) column order of ``im2col_nd``.  Returns the (B, Do, Ho, Wo, N) 16-bit
     output, or (output, fp32 copy [M][N]) when ``want_f32``; ``store_f32``: only the fp32 [M][N] result (no ReLU).
-    ``live`` (``live_taps``): W holds the columns of those taps only (``prune_conv_weight``)."""
-    _need_gpu(x, W, bias, resid, resid_f32)
+    ``live`` (``live_taps``): W holds the columns of those taps only (``prune_conv_weight``).
+    ``out`` [M, ldc] with ``ldc`` / ``col_off``: the N channels land at channels col_off .. col_off+N-1 of it, and ``out`` is
+    returned as it was given."""
+    _need_gpu(x, W, bias, resid, resid_f32, out)
     assert x.dtype in HALF_TYPES and x.is_contiguous() and x.dim() == 5 and W.dtype == x.dtype and W.is_contiguous()
     B, D, H, Wd, Cc = x.shape
     if Cc % 8:
@@ -1316,7 +1344,10 @@ def conv_implicit(x: torch.Tensor, W: torch.Tensor, bias, kernel, stride, pad, r
     Do, Ho, Wo = conv_out_dims((D, H, Wd), kernel, stride, pad)
     N, k_pad = W.shape
     M = B * Do * Ho * Wo
-    out = None if store_f32 else torch.empty(M, N, dtype=x.dtype, device=x.device)
+    given = out is not None
+    if not given and not store_f32:
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    assert out is None or (out.dtype == x.dtype and out.is_contiguous() and out.numel() >= M * N)
     out32 = torch.empty(M, N, dtype=torch.float32, device=x.device) if (want_f32 or store_f32) else None
     assert relu or (resid is None and resid_f32 is None and not want_f32), "identity add / fp32 copy: ReLU epilogue only"
     a = _abi.KvqConvArgs()
@@ -1330,11 +1361,13 @@ def conv_implicit(x: torch.Tensor, W: torch.Tensor, bias, kernel, stride, pad, r
     a.epilogue = _abi.EPI_STORE_F32 if store_f32 else (_abi.EPI_RELU_BF16 if relu else _abi.EPI_BIAS_BF16)
     a.dtype = dtype_code(x.dtype)
     a.out_bf16, a.out_f32, a.resid_bf16, a.resid_f32 = ptr(out), ptr(out32), ptr(resid), ptr(resid_f32)
+    a.ldc, a.col_off = _concat_dest(out, M, ldc, col_off)
     _ws = _splitk_scratch(a, x.shape[0] * Do * Ho * Wo, N, k_pad, x.device)   # noqa: F841
     check(lib().kvq_conv_implicit(C.byref(a), current_stream()), "kvq_conv_implicit")
     if store_f32:
         return out32
-    out = out.reshape(B, Do, Ho, Wo, N)
+    if not given:
+        out = out.reshape(B, Do, Ho, Wo, N)
     return (out, out32) if want_f32 else out
 
 

@@ -580,6 +580,8 @@ class SwinTransformer3D(nn.Module):
                 sym = f"gemm_kernel<{ename}, {mn // 10}, {mn % 10}, {bk}, {epi}>"
                 if tile == 4464:            # the 256 x 256 x 64 eight-phase kernel (csrc/gemm256.hip)
                     sym = f"gemm8p_kernel<{ename}, {epi}>"
+                elif tile == 22264:         # 128 x 128 x 64 on the 2-slice ring of the QKV epilogue (kvq_gemm_kernel_choice)
+                    sym = f"gemm_kernel<{ename}, 2, 2, 64, {epi}, 2>"
             elif kind == "attn" and r.variant >= 4:
                 sym = f"window_attention32_kernel<{ename}>"
             elif kind == "attn":

@@ -11,17 +11,23 @@ makes (outputs, split-K scratch, weight packs, workspaces) guarded as well.  Ass
       (byte outputs, where 255 is a value: a third run with a 0x00 payload must give the same bytes)
   (d) rows / columns an entry point documents it leaves alone still hold the payload
 
-The shapes are the smallest ragged ones of the value tests (tests/test_gpu_kernels.py and friends); values are random, no reference
-is needed here.  Integer tables are wrapped with ZERO guards (tests/guarded.py: the blind spot), so an over-read of an index table is
+The shapes are the smallest ragged ones of the value tests (tests/test_gpu_kernels.py and friends) and, for the GEMM and the
+implicit-GEMM convolution, one ragged shape per big main loop of tests/gemm_forms.py (each case asserts the form its shape reaches)
+with the ldc / col_off store; values are random, no reference is needed here.  Integer tables are wrapped with ZERO guards (tests/guarded.py: the blind spot), so an over-read of an index table is
 not detected.  The end-to-end forwards allocate through the plan's workspaces and are out of scope.
 
 Skipped cases: none.
 """
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
 import kvq_amd  # noqa: F401
+from gemm_forms import BY_NAME, conv_rows
+from gemm_forms import CONV as CONV_FORMS
+from gemm_forms import QKV as QKV_FORMS
 from guarded import guarded
 from kvq_amd import _abi, kernels
 from kvq_amd.utils import synth
@@ -262,6 +268,85 @@ def test_qkv_fill_pad(half):
     inputs = dict(qkv=Out(3, nH, B * Lp, 32, dtype=half), b=f32(g, 3 * C), pad=i32(np.nonzero(pad)[0]))
     check(inputs, lambda t: kernels.qkv_fill_pad(t["qkv"], t["b"], t["pad"], B, 32 ** -0.5),
           [Keep(0, row_mask((3, nH, B * Lp, 32), 2, np.tile(~pad, B)))])
+
+
+@contextlib.contextmanager
+def form(c):
+    """a row of tests/gemm_forms.py: its tile mode set and restored, its main loop asserted before anything is launched"""
+    prev = kernels.gemm_tile_mode(getattr(c, "mode", -1))
+    try:
+        if hasattr(c, "shape"):
+            assert kernels.gemm_kernel_choice(conv_rows(c), c.Cout, c.Kpad, _abi.EPI_RELU_BF16, True) == c.code
+        else:
+            assert kernels.gemm_kernel_choice(c.M, c.N, c.K, _abi.EPI_QKV_BF16 if c.nH else _abi.EPI_BIAS_BF16) == c.code
+            assert (_abi.lib().kvq_gemm_splitk_factor(c.M, c.N, c.K) > 1) == c.split
+        yield
+    finally:
+        kernels.gemm_tile_mode(prev)
+
+
+BIG_FORMS = ["128x128x64", "128x128x32-mode0", "128x64x32", "192x128x64", "128x256x64", "splitk-128x128x32", "splitk-128x64x32"]
+
+
+@pytest.mark.parametrize("name", BIG_FORMS)
+def test_gemm_epilogues_on_the_big_ring_tiles(name, half):
+    """one ragged shape per big ring tile (the 192-row tile over M = 3000, the 256-column tile over N = 2520, the shape mode 0 takes
+    off the wide tile) and split-K around the two big 32-deep tiles: the last row and column tiles of every epilogue"""
+    c = BY_NAME[name]
+    M, N, K = c.M, c.N, c.K
+    g = gen(M + N + K)
+    inputs = dict(A=f32(g, M, K).to(half), W=f32(g, N, K, sc=K ** -0.5).to(half), b=f32(g, N), x=f32(g, M, N), r16=f32(g, M, N).to(half))
+
+    def call(t):
+        outs = [kernels.gemm(t["A"], t["W"], t["b"], e) for e in (_abi.EPI_STORE_F32, _abi.EPI_BIAS_BF16, _abi.EPI_GELU_BF16)]
+        outs.append(kernels.conv_gemm(t["A"], t["W"], t["b"], True, resid=t["r16"]))
+        outs.append(kernels.gemm(t["A"], t["W"], t["b"], _abi.EPI_RESID_F32, out=t["x"]))
+        return outs
+    with form(c):
+        check(inputs, call)
+
+
+@pytest.mark.parametrize("name", [c.name for c in QKV_FORMS])
+def test_gemm_qkv_epilogue_on_the_big_ring_tiles(name, half):
+    """the head-major store from the 256-column tile (N = 96 nH = 12 tiles), the 128 x 64 tile and the 2-slice ring; with the scatter
+    map the rows no token lands in keep the payload"""
+    c = BY_NAME[name]
+    M, N, K, nH = c.M, c.N, c.K, c.nH
+    g = gen(M + N + K)
+    B = 2
+    L = M // B
+    Lp = L + 100
+    inv = np.sort(g.permutation(Lp)[:L])
+    hit = np.zeros(Lp, bool)
+    hit[inv] = True
+    inputs = dict(A=f32(g, M, K).to(half), W=f32(g, N, K, sc=K ** -0.5).to(half), b=f32(g, N), inv=i32(inv), qkv=Out(3, nH, B * Lp, 32, dtype=half))
+
+    def call(t):
+        kernels.gemm(t["A"], t["W"], t["b"], _abi.EPI_QKV_BF16, num_heads=nH, q_scale=32 ** -0.5, out=t["qkv"], scatter_map=t["inv"], map_rows=L,
+                     out_rows=Lp)
+        return [t["qkv"], kernels.gemm(t["A"], t["W"], t["b"], _abi.EPI_QKV_BF16, num_heads=nH, q_scale=32 ** -0.5)]
+    with form(c):
+        check(inputs, call, [Keep(0, row_mask((3, nH, B * Lp, 32), 2, np.tile(~hit, B)))])
+
+
+@pytest.mark.parametrize("name", ["64x64x32", "192x128x64", "256x256x64", "splitk-128x128x32"])
+def test_gemm_channel_concatenation_leaves_the_other_columns_alone(name, half):
+    """ldc / col_off: the N columns land inside rows of ldc elements; the columns in front of and behind them keep the payload"""
+    c = BY_NAME[name]
+    M, N, K = c.M, c.N, c.K
+    g = gen(M + N + K + 2)
+    ldc, off = N + 40, 16
+    inputs = dict(A=f32(g, M, K).to(half), W=f32(g, N, K, sc=K ** -0.5).to(half), b=f32(g, N), r16=f32(g, M, N).to(half),
+                  o1=Out(M, ldc, dtype=half), o2=Out(M, ldc, dtype=half))
+    cols = np.ones(ldc, bool)
+    cols[off:off + N] = False
+
+    def call(t):
+        kernels.gemm(t["A"], t["W"], t["b"], _abi.EPI_GELU_BF16, out=t["o1"], ldc=ldc, col_off=off)
+        kernels.conv_gemm(t["A"], t["W"], t["b"], True, resid=t["r16"], out=t["o2"], ldc=ldc, col_off=off)
+        return [t["o1"], t["o2"]]
+    with form(c):
+        check(inputs, call, [Keep(0, row_mask((M, ldc), 1, cols)), Keep(1, row_mask((M, ldc), 1, cols))])
 
 
 # -------------------------------------------------------------------------------------------------------------- LayerNorm
@@ -598,6 +683,37 @@ def test_conv_implicit_and_im2col(shape, Cout, k, stride, pad, half):
         return [cols, y16, y32, kernels.conv_implicit(t["x"], t["w"], t["b"], k, stride, pad, False),
                 kernels.conv_implicit(t["x"], t["w"], t["b"], k, stride, pad, False, store_f32=True)]
     check(inputs, call)
+
+
+@pytest.mark.parametrize("name", [c.name for c in CONV_FORMS if c.code != 1132])
+def test_conv_implicit_on_the_big_ring_tiles(name, half):
+    """the 128 x 128 and 128 x 64 implicit-GEMM tiles (walked taps, and the tap table: the only form of C % 32 != 0), split-K around
+    the 128 x 128 one, and the channel-concatenation store with the other channels keeping the payload"""
+    c = BY_NAME[name]
+    g = gen(sum(c.shape) + c.Cout)
+    N, M, Cc = c.Cout, conv_rows(c), c.shape[-1]
+    K = c.kernel[0] * c.kernel[1] * c.kernel[2] * Cc
+    wk = torch.zeros(N, c.Kpad)
+    wk[:, :K] = f32(g, N, K, sc=K ** -0.5)
+    ldc, off = N + 24, 8
+    inputs = dict(x=f32(g, *c.shape).to(half), w=wk.to(half), b=f32(g, N), r=f32(g, M, N), o=Out(M, ldc, dtype=half))
+    cols = np.ones(ldc, bool)
+    cols[off:off + N] = False
+    k, s1, pad = c.kernel, (1, 1, 1), c.pad
+
+    def call(t):
+        y16, y32 = kernels.conv_implicit(t["x"], t["w"], t["b"], k, s1, pad, True, resid_f32=t["r"], want_f32=True)
+        kernels.conv_implicit(t["x"], t["w"], t["b"], k, s1, pad, True, out=t["o"], ldc=ldc, col_off=off)
+        outs = [t["o"], y16, y32, kernels.conv_implicit(t["x"], t["w"], t["b"], k, s1, pad, False, store_f32=True)]
+        if Cc % 32 == 0:
+            kernels.TAP_TABLE = True
+            try:
+                outs.append(kernels.conv_implicit(t["x"], t["w"], t["b"], k, s1, pad, True))
+            finally:
+                kernels.TAP_TABLE = False
+        return outs
+    with form(c):
+        check(inputs, call, [Keep(0, row_mask((M, ldc), 1, cols))])
 
 
 @pytest.mark.parametrize("C", [40, 6])
