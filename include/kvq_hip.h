@@ -34,7 +34,7 @@ extern "C" {
 /* 16-bit MFMA operand type of every uint16_t buffer below (activations AND weights of one call must
  * agree).  Same MFMA rate and bytes; fp16 (11-bit mantissa, saturating conversions) is the default of
  * the host wrapper because it holds the 1e-3 MOS parity gate where bf16 (8-bit mantissa) does not. */
-typedef enum { KVQ_DT_BF16 = 0, KVQ_DT_FP16 = 1 } KvqDtype;
+typedef enum { KVQ_DT_BF16 = 0, KVQ_DT_FP16 = 1, KVQ_DT_FP32 = 2 /* the rows of a KvqFeatureBank only: no operand type */ } KvqDtype;
 
 typedef enum {
   KVQ_OK = 0,
@@ -1248,6 +1248,54 @@ int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float
 size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int hidden);
 int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* host_args, void* stream);
 int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* host_args, void* stream);
+
+/* ---- feature bank (csrc/featbank.hip): the cached features of a frozen trunk, stored once — several train-phase draws
+ * per video, in fp32, fp16 or bf16 — and read in place by the two training steps through an index vector.
+ *
+ *   rows     [n_rows][L][C], dense, 16-byte aligned, elements of type dtype (KVQ_DT_FP32 | KVQ_DT_FP16 | KVQ_DT_BF16)
+ *   L, C     a row's tokens (VQAHead: the clip's feature map; simpleVQAHead: the frames T) and channels, C a multiple of 4
+ *
+ * Widening a 16-bit row to fp32 is exact, and the bank entries below run the launches of the dense entries with the rows widened in
+ * registers: a bank step is bit-equal to the dense step on kvq_feature_bank_rows of the same index. */
+typedef struct KvqFeatureBank {
+  void* rows;
+  int32_t dtype;
+  int32_t L, C;
+  int64_t n_rows;
+} KvqFeatureBank;
+/* Writes n samples of fp32 features into the rows first_row .. first_row + n - 1: feat[i * stride_n + l * stride_l + c] (strides in
+ * elements, multiples of 4; channel stride 1; feat 16-byte aligned) — the trunk's channels-last storage behind its (B, C, D, H, W) view,
+ * or simpleVQA's (rows, T, C).  Rounds to nearest even.  A value past +-65504 goes into an fp16 bank as +-65504, and a NaN stays a NaN in
+ * every bank; either sets *flag = 1 (a plain store of the same value from every lane that sees one; flag may be NULL, and is never
+ * cleared here).  n >= 1, 0 <= first_row, first_row + n <= n_rows: otherwise KVQ_ERR_SHAPE. */
+int kvq_feature_bank_store(const float* feat, int64_t n, int64_t stride_n, int64_t stride_l, const KvqFeatureBank* bank, int64_t first_row,
+                           int32_t* flag, void* stream);
+/* out fp32 [B][L][C] (dense, 16-byte aligned) = the rows index[0 .. B) (device pointer), widened.  Every index value is clamped into
+ * [0, n_rows) on the device: a defined result, never a read outside the bank. */
+int kvq_feature_bank_rows(const KvqFeatureBank* bank, const int32_t* index, int64_t B, float* out, void* stream);
+
+/* The two training steps on bank rows: KvqHeadTrainArgs with feat replaced by (bank, index) — sample b of the batch is the bank row
+ * index[b] (device pointer to B values, clamped as above), bank.L == L and bank.C == C.  The dropout masks stay indexed by the batch
+ * position [b][l][c], the workspace is the one of the dense entry for (B, L, C, hidden), and every result equals the dense entry's on the
+ * widened rows bit for bit.  Host checks as the dense entries, plus the bank's: NULL rows or index: KVQ_ERR_NULL; alignment (rows 16,
+ * index 4 bytes) or dtype code: KVQ_ERR_UNSUPPORTED; n_rows < 1 or L, C that differ from the bank's: KVQ_ERR_SHAPE. */
+typedef struct KvqHeadTrainBankArgs {
+  KvqFeatureBank bank;
+  const int32_t* index;
+  int32_t B, L, C, hidden;
+  const float* params;
+  float p_drop;
+  uint32_t seed, step;
+  void* workspace;
+  size_t workspace_bytes;
+  float* score;
+  const float* dscore;
+  float* grads;
+} KvqHeadTrainBankArgs;
+int kvq_headtrain_bank_forward(const KvqHeadTrainBankArgs* host_args, void* stream);
+int kvq_headtrain_bank_backward(const KvqHeadTrainBankArgs* host_args, void* stream);
+int kvq_simple_headtrain_bank_forward(const KvqHeadTrainBankArgs* host_args, void* stream);
+int kvq_simple_headtrain_bank_backward(const KvqHeadTrainBankArgs* host_args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,26 @@ def torch_dtype(code: int):
     import torch
     return torch.float16 if code == DT_FP16 else torch.bfloat16
 
+
+DT_FP32 = 2      # the rows of a KvqFeatureBank only: no 16-bit operand type, dtype_code() refuses it
+
+
+def bank_dtype_code(dt) -> int:
+    """torch dtype / name of a feature bank's rows -> KvqDtype: fp32 or one of the two 16-bit types"""
+    import torch
+    is_int = isinstance(dt, int) and not isinstance(dt, bool)
+    if (is_int and dt == DT_FP32) or (not is_int and dt in (torch.float32, "fp32", "float32")):
+        return DT_FP32
+    try:
+        return dtype_code(dt)
+    except ValueError:
+        raise ValueError(f"feature bank dtype must be fp32, fp16 or bf16, got {dt!r}") from None
+
+
+def bank_torch_dtype(code: int):
+    import torch
+    return torch.float32 if code == DT_FP32 else torch_dtype(code)
+
 p_void = C.c_void_p
 
 
@@ -189,6 +209,16 @@ class KvqHeadTrainArgs(C.Structure):
     _fields_ = [("feat", p_void), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32), ("params", p_void),
                 ("p_drop", C.c_float), ("seed", C.c_uint32), ("step", C.c_uint32), ("workspace", p_void), ("workspace_bytes", C.c_size_t),
                 ("score", p_void), ("dscore", p_void), ("grads", p_void)]
+
+
+class KvqFeatureBank(C.Structure):
+    _fields_ = [("rows", p_void), ("dtype", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("n_rows", C.c_int64)]
+
+
+class KvqHeadTrainBankArgs(C.Structure):
+    _fields_ = [("bank", KvqFeatureBank), ("index", p_void), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32),
+                ("params", p_void), ("p_drop", C.c_float), ("seed", C.c_uint32), ("step", C.c_uint32), ("workspace", p_void),
+                ("workspace_bytes", C.c_size_t), ("score", p_void), ("dscore", p_void), ("grads", p_void)]
 
 
 class KvqNetSlotLayout(C.Structure):
@@ -371,6 +401,12 @@ SYMBOLS = {
     "kvq_simple_headtrain_workspace_bytes": (sz, [i32] * 4),
     "kvq_simple_headtrain_forward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
     "kvq_simple_headtrain_backward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
+    "kvq_feature_bank_store": (i32, [p_void, i64, i64, i64, C.POINTER(KvqFeatureBank), i64, p_void, p_void]),
+    "kvq_feature_bank_rows": (i32, [C.POINTER(KvqFeatureBank), p_void, i64, p_void, p_void]),
+    "kvq_headtrain_bank_forward": (i32, [C.POINTER(KvqHeadTrainBankArgs), p_void]),
+    "kvq_headtrain_bank_backward": (i32, [C.POINTER(KvqHeadTrainBankArgs), p_void]),
+    "kvq_simple_headtrain_bank_forward": (i32, [C.POINTER(KvqHeadTrainBankArgs), p_void]),
+    "kvq_simple_headtrain_bank_backward": (i32, [C.POINTER(KvqHeadTrainBankArgs), p_void]),
 }
 
 _lib: Optional[C.CDLL] = None

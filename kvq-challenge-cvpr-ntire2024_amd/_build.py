@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 TAG = os.environ.get("KVQ_BUILD_TAG", "")
 LIB = os.path.join(PKG, f"libkvq_hip_{TAG}.so" if TAG else "libkvq_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "kvq_hip.h")
-SOURCES = ["common.cpp", "gemm.hip", "gemm256.hip", "ln.hip", "dwconv.hip", "grn.hip", "attn.hip", "attn32.hip", "misc.hip", "yuv.hip", "jpeg.cpp", "jpeg.hip", "jpeg_entropy.hip", "jpeg_enc.cpp", "jpeg_enc.hip", "jpeg_enc_entropy.hip", "qmap.hip", "resize_aa.hip", "resize_pil.cpp", "resize_pil.hip", "plan.hip", "conv.hip", "tail.hip", "tailmm.hip", "embed.hip", "merge.hip", "vit.hip", "convnet.hip", "bottleneck.hip", "slowneck.hip", "headtrain.hip", "simple_headtrain.hip"]
+SOURCES = ["common.cpp", "gemm.hip", "gemm256.hip", "ln.hip", "dwconv.hip", "grn.hip", "attn.hip", "attn32.hip", "misc.hip", "yuv.hip", "jpeg.cpp", "jpeg.hip", "jpeg_entropy.hip", "jpeg_enc.cpp", "jpeg_enc.hip", "jpeg_enc_entropy.hip", "qmap.hip", "resize_aa.hip", "resize_pil.cpp", "resize_pil.hip", "plan.hip", "conv.hip", "tail.hip", "tailmm.hip", "embed.hip", "merge.hip", "vit.hip", "convnet.hip", "bottleneck.hip", "slowneck.hip", "headtrain.hip", "simple_headtrain.hip", "featbank.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable"]
 # attn.hip is VALU-bound: SLP packing of adjacent f32 ops into v_pk_* costs more v_mov than it saves, and

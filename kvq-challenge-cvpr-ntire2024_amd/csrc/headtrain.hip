@@ -1,7 +1,10 @@
 // One optimisation step of VQAHead on features of a frozen trunk (gfx950): the reference's train-mode head (head.py:60-68), its losses
 // (trainer.py:337-354), the gradients of the four head parameters and torch's AdamW with the EMA copy (trainer.py:163-172).
 //
-//   features  fp32 channels-last [B][L][C], C % 64 == 0, hidden == 64, one class, no pre-pool, B >= 2
+//   features  fp32 channels-last [B][L][C], C % 64 == 0, hidden == 64, one class, no pre-pool, B >= 2; or (the bank entries) B rows of a
+//             feature bank [n_rows][L][C] in fp32, fp16 or bf16, picked by a device index and widened to fp32 in registers
+//             (featbank.hpp): the two launches that read features are templates over the element type and over whether an index is
+//             given, the dense entries are their (float, no index) form
 //   params    one flat fp32 vector: W1 [64][C] | b1 [64] | w2 [64] | b2 [1]; the gradients and the AdamW state have the same layout
 //   score[b]  = mean_l( w2 . (m2 * gelu(W1 (m1 * f) + b1)) ) + b2,   m1, m2 the scaled dropout masks of headtrain.hpp
 //
@@ -19,6 +22,7 @@
 //   headtrain_bwd_sum    dW1: adds the chunk partials in ascending order into the flat gradient; db2 = sum_b dscore
 //   headtrain_adamw      elementwise AdamW + EMA over the flat vector
 #include "common.hpp"
+#include "featbank.hpp"
 #include "headtrain.hpp"
 
 namespace kvq {
@@ -41,8 +45,11 @@ __global__ __launch_bounds__(256) void headtrain_mask_kernel(uint32_t key, uint3
   if (i < n) out[i] = ht_bits(key, (uint32_t)i) >= thr ? 1 : 0;
 }
 
-// grid ceil(B*L / 16), 256 threads.  vqa_head_mfma_kernel with the two masks and the pre-activations kept.
-__global__ __launch_bounds__(256) void headtrain_fwd_kernel(const float* __restrict__ feat, long total, int C, const float* __restrict__ w1,
+// grid ceil(B*L / 16), 256 threads.  vqa_head_mfma_kernel with the two masks and the pre-activations kept.  Token tk = (b, l) reads
+// row bank_row(b) of feat (IDX = false: row b, the dense batch); the masks are indexed by the batch position tk either way.
+template <typename E, bool IDX>
+__global__ __launch_bounds__(256) void headtrain_fwd_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
+                                                            int L, long total, int C, const float* __restrict__ w1,
                                                             const float* __restrict__ b1, const float* __restrict__ w2, uint32_t key1,
                                                             uint32_t key2, uint32_t thr, float scale, float* __restrict__ z,
                                                             float* __restrict__ tok_score) {
@@ -52,20 +59,25 @@ __global__ __launch_bounds__(256) void headtrain_fwd_kernel(const float* __restr
   const int tok = lane & 15, kq = lane >> 4;
   const long tk = min((long)blockIdx.x * 16 + tok, total - 1);
   const int cw = C / 4, c0 = wave * cw;
-  const float* xr = feat + (size_t)tk * C + c0 + 4 * kq;
+  long tsrc = tk;                                                // the token's place in feat, in tokens
+  if constexpr (IDX) {
+    const long b = tk / L;
+    tsrc = bank_row<IDX>(index, n_rows, b) * L + (tk - b * L);
+  }
+  const E* xr = feat + (size_t)tsrc * C + c0 + 4 * kq;
   const uint32_t e0 = (uint32_t)((size_t)tk * C) + (uint32_t)(c0 + 4 * kq);      // element index of xr[0]
   const float* wr = w1 + (size_t)tok * C + c0 + 4 * kq;          // + 16 hb rows
   const size_t hbs = (size_t)16 * C;
   f32x4 acc[4];
 #pragma unroll
   for (int hb = 0; hb < 4; ++hb) acc[hb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  f32x4 xv = *reinterpret_cast<const f32x4*>(xr), wv[4];
+  f32x4 xv = bank_load4(xr), wv[4];
 #pragma unroll
   for (int hb = 0; hb < 4; ++hb) wv[hb] = *reinterpret_cast<const f32x4*>(wr + hb * hbs);
   for (int c = 0; c < cw; c += 16) {
     f32x4 xn = xv, wn[4] = {wv[0], wv[1], wv[2], wv[3]};
     if (c + 16 < cw) {                                             // the next macro-step's operands, under this one's MFMAs
-      xn = *reinterpret_cast<const f32x4*>(xr + c + 16);
+      xn = bank_load4(xr + c + 16);
 #pragma unroll
       for (int hb = 0; hb < 4; ++hb) wn[hb] = *reinterpret_cast<const f32x4*>(wr + hb * hbs + c + 16);
     }
@@ -333,9 +345,11 @@ __global__ __launch_bounds__(1024) void headtrain_bwd_sum_small_kernel(const flo
 // (hb, s) takes element s of every lane's quad, so its 16 output columns are the channels c0 + 4 j + s and a lane's four tiles s = 0 .. 3
 // hold four consecutive channels again.  The four waves take the k-steps in turn (wave w: steps w, w + 4, ...) and meet in LDS, added as
 // (w0 + w1) + (w2 + w3); wave w then stores the hidden units 16 w .. 16 w + 15.
-__global__ __launch_bounds__(256) void headtrain_bwd_w1_kernel(const float* __restrict__ feat, const float* __restrict__ dz, long total, int C,
-                                                               int chunk, uint32_t key1, uint32_t thr, float scale,
-                                                               float* __restrict__ part) {
+// Token t = (b, l) reads row bank_row(b) of feat, as in the forward; dz and the mask are indexed by t.
+template <typename E, bool IDX>
+__global__ __launch_bounds__(256) void headtrain_bwd_w1_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
+                                                               int L, const float* __restrict__ dz, long total, int C, int chunk,
+                                                               uint32_t key1, uint32_t thr, float scale, float* __restrict__ part) {
   __shared__ float red[4][3][16][64];                      // [owner hb][source slot][s * 4 + r][lane]: 48 KiB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
@@ -359,7 +373,12 @@ __global__ __launch_bounds__(256) void headtrain_bwd_w1_kernel(const float* __re
     const long t = ts + kq;
     o.in = t < t1;
     const long tc = o.in ? t : t1 - 1;
-    o.x = *reinterpret_cast<const f32x4*>(feat + (size_t)tc * C + c0 + 4 * j);
+    long tsrc = tc;
+    if constexpr (IDX) {
+      const long b = tc / L;
+      tsrc = bank_row<IDX>(index, n_rows, b) * L + (tc - b * L);
+    }
+    o.x = bank_load4(feat + (size_t)tsrc * C + c0 + 4 * j);
     o.e0 = (uint32_t)((size_t)tc * C) + (uint32_t)(c0 + 4 * j);
 #pragma unroll
     for (int hb = 0; hb < 4; ++hb) o.d[hb] = dz[(size_t)tc * HT_HID + 16 * hb + j];
@@ -464,15 +483,15 @@ __global__ __launch_bounds__(256) void headtrain_adamw_kernel(float* __restrict_
   if (ema) ema[i] = fmaf(0.001f, pi, ema[i] * 0.999f);
 }
 
-static int headtrain_check(const KvqHeadTrainArgs* a, const char* who, HeadTrainPlan* plan) {
-  KVQ_REQUIRE(a && a->feat && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
+static int headtrain_check(const HeadTrainCall* a, const char* who, HeadTrainPlan* plan) {
+  KVQ_REQUIRE(a->feat.rows && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
   KVQ_REQUIRE(a->hidden == HT_HID, KVQ_ERR_UNSUPPORTED, "%s: hidden %d (64 is built)", who, a->hidden);
   KVQ_REQUIRE(a->C >= 64 && a->C % 64 == 0, KVQ_ERR_UNSUPPORTED, "%s: C %d is not a multiple of 64", who, a->C);
   KVQ_REQUIRE(a->p_drop >= 0.f && a->p_drop < 1.f, KVQ_ERR_UNSUPPORTED, "%s: dropout probability %g outside [0, 1)", who, (double)a->p_drop);
   KVQ_REQUIRE(a->B >= 2 && a->L >= 1, KVQ_ERR_SHAPE, "%s: B %d (at least 2 clips: the loss of one is constant), L %d", who, a->B, a->L);
   KVQ_REQUIRE((double)a->B * a->L * a->C < 4294967296.0, KVQ_ERR_SHAPE, "%s: B*L*C = %g elements exceed the 32-bit mask index", who,
               (double)a->B * a->L * a->C);
-  KVQ_REQUIRE((((uintptr_t)a->feat | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
+  KVQ_REQUIRE((((uintptr_t)a->feat.rows | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
               "%s: feat, params and workspace must be 16-byte aligned", who);
   *plan = headtrain_plan(a->B, a->L, a->C, a->hidden);
   KVQ_REQUIRE(a->workspace_bytes >= plan->total * sizeof(float), KVQ_ERR_WORKSPACE, "%s: workspace %zu bytes, %zu needed", who,
@@ -496,21 +515,72 @@ extern "C" int kvq_headtrain_mask(uint32_t seed, uint32_t step, int which, float
                 ht_threshold(p), (long)n, out);
 }
 
-extern "C" int kvq_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
+namespace kvq {
+
+static int headtrain_forward_call(const HeadTrainCall* a, const char* who, void* stream) {
   HeadTrainPlan pl;
-  if (int rc = headtrain_check(a, "kvq_headtrain_forward", &pl)) return rc;
-  KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "kvq_headtrain_forward: NULL pointer");
+  if (int rc = headtrain_check(a, who, &pl)) return rc;
+  KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "%s: NULL pointer", who);
   float* ws = static_cast<float*>(a->workspace);
   const float* w1 = a->params;
   const float* b1 = w1 + (size_t)HT_HID * a->C;
   const float* w2 = b1 + HT_HID;
   const float* b2 = w2 + HT_HID;
   const uint32_t thr = ht_threshold(a->p_drop);
-  if (int rc = launch("headtrain_fwd_kernel", headtrain_fwd_kernel, grid_1d(pl.T, 16), dim3(256), 0, stream, a->feat, pl.T, a->C, w1, b1, w2,
-                      ht_key(a->seed, a->step, 0), ht_key(a->seed, a->step, 1), thr, ht_scale(a->p_drop), ws + pl.z, ws + pl.tok))
+  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+        using E = decltype(e);
+        return launch("headtrain_fwd_kernel", headtrain_fwd_kernel<E, decltype(idx)::value>, grid_1d(pl.T, 16), dim3(256), 0, stream,
+                      static_cast<const E*>(a->feat.rows), a->feat.index, a->feat.n_rows, a->L, pl.T, a->C, w1, b1, w2,
+                      ht_key(a->seed, a->step, 0), ht_key(a->seed, a->step, 1), thr, ht_scale(a->p_drop), ws + pl.z, ws + pl.tok);
+      }))
     return rc;
   return launch("headtrain_score_kernel", headtrain_score_kernel, dim3((unsigned)a->B), dim3(256), 0, stream, ws + pl.tok, a->L, b2, a->score);
+}
+
+static int headtrain_backward_call(const HeadTrainCall* a, const char* who, void* stream) {
+  HeadTrainPlan pl;
+  if (int rc = headtrain_check(a, who, &pl)) return rc;
+  KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "%s: NULL pointer", who);
+  float* ws = static_cast<float*>(a->workspace);
+  const float* w2 = a->params + (size_t)HT_HID * a->C + HT_HID;
+  const uint32_t thr = ht_threshold(a->p_drop);
+  const float scale = ht_scale(a->p_drop);
+  KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "%s: grads must be 16-byte aligned", who);
+  const size_t nw1 = (size_t)HT_HID * a->C;
+  if (int rc = launch("headtrain_bwd_hidden_kernel", headtrain_bwd_hidden_kernel, dim3((unsigned)pl.hsub, (unsigned)pl.nchunks), dim3(256), 0,
+                      stream, ws + pl.z, a->dscore, w2, pl.T, a->L, pl.chunk, ht_key(a->seed, a->step, 1), thr, scale, ws + pl.dz,
+                      ws + pl.part_b1, ws + pl.part_w2))
+    return rc;
+  if (int rc = launch("headtrain_bwd_sum_small_kernel", headtrain_bwd_sum_small_kernel, dim3(1), dim3(1024), 0, stream, ws + pl.part_b1,
+                      ws + pl.part_w2, pl.nsub, a->grads + nw1))
+    return rc;
+  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+        using E = decltype(e);
+        return launch("headtrain_bwd_w1_kernel", headtrain_bwd_w1_kernel<E, decltype(idx)::value>,
+                      dim3((unsigned)(a->C / 64), (unsigned)pl.nchunks), dim3(256), 0, stream, static_cast<const E*>(a->feat.rows),
+                      a->feat.index, a->feat.n_rows, a->L, ws + pl.dz, pl.T, a->C, pl.chunk, ht_key(a->seed, a->step, 0), thr, scale,
+                      ws + pl.part_w1);
+      }))
+    return rc;
+  const long quads = (long)nw1 / 4;
+  return launch("headtrain_bwd_sum_kernel", headtrain_bwd_sum_kernel, dim3((unsigned)((quads + 255) / 256 + 1)), dim3(256), 0, stream,
+                ws + pl.part_w1, a->dscore, a->B, a->C, pl.nchunks, a->grads);
+}
+
+}  // namespace kvq
+
+extern "C" int kvq_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_headtrain_forward: NULL pointer");
+  const HeadTrainCall c = headtrain_call(a);
+  return headtrain_forward_call(&c, "kvq_headtrain_forward", stream);
+}
+
+extern "C" int kvq_headtrain_bank_forward(const KvqHeadTrainBankArgs* a, void* stream) {
+  using namespace kvq;
+  if (int rc = headtrain_bank_check(a, "kvq_headtrain_bank_forward")) return rc;
+  const HeadTrainCall c = headtrain_call(a);
+  return headtrain_forward_call(&c, "kvq_headtrain_bank_forward", stream);
 }
 
 extern "C" int kvq_headtrain_loss(const float* score, const float* label, int B, float rank_weight, float* out3, float* dscore,
@@ -523,28 +593,16 @@ extern "C" int kvq_headtrain_loss(const float* score, const float* label, int B,
 
 extern "C" int kvq_headtrain_backward(const KvqHeadTrainArgs* a, void* stream) {
   using namespace kvq;
-  HeadTrainPlan pl;
-  if (int rc = headtrain_check(a, "kvq_headtrain_backward", &pl)) return rc;
-  KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "kvq_headtrain_backward: NULL pointer");
-  float* ws = static_cast<float*>(a->workspace);
-  const float* w2 = a->params + (size_t)HT_HID * a->C + HT_HID;
-  const uint32_t thr = ht_threshold(a->p_drop);
-  const float scale = ht_scale(a->p_drop);
-  KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "kvq_headtrain_backward: grads must be 16-byte aligned");
-  const size_t nw1 = (size_t)HT_HID * a->C;
-  if (int rc = launch("headtrain_bwd_hidden_kernel", headtrain_bwd_hidden_kernel, dim3((unsigned)pl.hsub, (unsigned)pl.nchunks), dim3(256), 0,
-                      stream, ws + pl.z, a->dscore, w2, pl.T, a->L, pl.chunk, ht_key(a->seed, a->step, 1), thr, scale, ws + pl.dz,
-                      ws + pl.part_b1, ws + pl.part_w2))
-    return rc;
-  if (int rc = launch("headtrain_bwd_sum_small_kernel", headtrain_bwd_sum_small_kernel, dim3(1), dim3(1024), 0, stream, ws + pl.part_b1,
-                      ws + pl.part_w2, pl.nsub, a->grads + nw1))
-    return rc;
-  if (int rc = launch("headtrain_bwd_w1_kernel", headtrain_bwd_w1_kernel, dim3((unsigned)(a->C / 64), (unsigned)pl.nchunks), dim3(256), 0, stream,
-                      a->feat, ws + pl.dz, pl.T, a->C, pl.chunk, ht_key(a->seed, a->step, 0), thr, scale, ws + pl.part_w1))
-    return rc;
-  const long quads = (long)nw1 / 4;
-  return launch("headtrain_bwd_sum_kernel", headtrain_bwd_sum_kernel, dim3((unsigned)((quads + 255) / 256 + 1)), dim3(256), 0, stream,
-                ws + pl.part_w1, a->dscore, a->B, a->C, pl.nchunks, a->grads);
+  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_headtrain_backward: NULL pointer");
+  const HeadTrainCall c = headtrain_call(a);
+  return headtrain_backward_call(&c, "kvq_headtrain_backward", stream);
+}
+
+extern "C" int kvq_headtrain_bank_backward(const KvqHeadTrainBankArgs* a, void* stream) {
+  using namespace kvq;
+  if (int rc = headtrain_bank_check(a, "kvq_headtrain_bank_backward")) return rc;
+  const HeadTrainCall c = headtrain_call(a);
+  return headtrain_backward_call(&c, "kvq_headtrain_bank_backward", stream);
 }
 
 extern "C" int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,

@@ -2,7 +2,10 @@
 // Linear(128 -> 1) per frame, no activation, no dropout, then the mean over the frames), the gradients of its four parameters; the losses
 // and AdamW + EMA are the launches of headtrain.hip, unchanged.
 //
-//   features  fp32 [B][T][C], C % 64 == 0, hidden == 128, 2 <= B <= 1024
+//   features  fp32 [B][T][C], C % 64 == 0, hidden == 128, 2 <= B <= 1024; or (the bank entries) B rows of a feature bank [n_rows][T][C] in
+//             fp32, fp16 or bf16, picked by a device index and widened to fp32 in registers (featbank.hpp): simple_fwd_rows and
+//             simple_bwd_g are templates over the element type and over whether an index is given, the dense entries their
+//             (float, no index) form
 //   params    one flat fp32 vector: W1 [128][C] | b1 [128] | w2 [128] | b2 [1]; the gradients and the AdamW state have the same layout
 //
 // The head is linear, so both directions collapse:
@@ -25,6 +28,7 @@
 //   simple_bwd_small  per hidden unit j: dw2[j] = W1[j,:] . g + b1[j] S, db1[j], and (j == 0) db2
 //   headtrain_adamw   (headtrain.hip)
 #include "common.hpp"
+#include "featbank.hpp"
 #include "simple_headtrain.hpp"
 
 namespace kvq {
@@ -79,21 +83,29 @@ __global__ __launch_bounds__(256) void simple_fwd_u_kernel(const float* __restri
 
 // grid ceil(N * nseg / 4), 256 threads: wave = one (row n, segment sg) of the [N][nseg] partials.  A lane multiplies up to four channel
 // quads (c = 1024 sg + 256 k + 4 lane) into four running sums, adds them as (0 + 1) + (2 + 3); the lanes meet in a butterfly.
-__global__ __launch_bounds__(256) void simple_fwd_rows_kernel(const float* __restrict__ feat, const float* __restrict__ u, long N, int C,
-                                                              int nseg, float* __restrict__ part) {
+// Row n = (b, t) reads row bank_row(b) of feat (IDX = false: row b, the dense batch).
+template <typename E, bool IDX>
+__global__ __launch_bounds__(256) void simple_fwd_rows_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
+                                                              int T, const float* __restrict__ u, long N, int C, int nseg,
+                                                              float* __restrict__ part) {
   const int lane = threadIdx.x & 63;
   const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= N * nseg) return;                                   // a whole wave; no barrier follows
   const long n = item / nseg;
   const int sg = (int)(item % nseg);
-  const float* xr = feat + (size_t)n * C;
+  long nsrc = n;
+  if constexpr (IDX) {
+    const long b = n / T;
+    nsrc = bank_row<IDX>(index, n_rows, b) * T + (n - b * T);
+  }
+  const E* xr = feat + (size_t)nsrc * C;
   f32x4 x[4], w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = sg * SH_SEG + 256 * k + 4 * lane;
     x[k] = w[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (c < C) {                                                   // c % 4 == 0 and C % 4 == 0: the quad is inside the row
-      x[k] = *reinterpret_cast<const f32x4*>(xr + c);
+      x[k] = bank_load4(xr + c);
       w[k] = *reinterpret_cast<const f32x4*>(u + c);
     }
   }
@@ -120,8 +132,11 @@ __global__ __launch_bounds__(64) void simple_fwd_score_kernel(const float* __res
 // grid (ceil(C / 128), nchunks), 256 threads: thread = (channel quad tid & 31, row phase tid >> 5).  The run's partial
 // g[c] = sum_n dscore[n / T] / T * X[n][c]: a thread adds its rows r0 + ph, r0 + ph + 8, ... in ascending order, the eight phases meet in
 // LDS as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).
-__global__ __launch_bounds__(256) void simple_bwd_g_kernel(const float* __restrict__ feat, const float* __restrict__ dscore, long N, int T,
-                                                           int C, int chunk, float* __restrict__ gpart) {
+// Row r = (b, t) reads row bank_row(b) of feat, as in the forward.
+template <typename E, bool IDX>
+__global__ __launch_bounds__(256) void simple_bwd_g_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
+                                                           const float* __restrict__ dscore, long N, int T, int C, int chunk,
+                                                           float* __restrict__ gpart) {
   __shared__ f32x4 red[8][32];
   const int q = threadIdx.x & 31, ph = threadIdx.x >> 5;
   const int c = blockIdx.x * 128 + 4 * q;
@@ -131,8 +146,10 @@ __global__ __launch_bounds__(256) void simple_bwd_g_kernel(const float* __restri
   if (in) {
 #pragma unroll 4
     for (long r = r0 + ph; r < r1; r += 8) {
-      const float d = dscore[r / T] / (float)T;
-      acc = sh_fma4(d, *reinterpret_cast<const f32x4*>(feat + (size_t)r * C + c), acc);
+      const long b = r / T;
+      const float d = dscore[b] / (float)T;
+      const long rsrc = IDX ? bank_row<IDX>(index, n_rows, b) * T + (r - b * T) : r;
+      acc = sh_fma4(d, bank_load4(feat + (size_t)rsrc * C + c), acc);
     }
   }
   red[ph][q] = acc;
@@ -200,14 +217,14 @@ __global__ __launch_bounds__(256) void simple_bwd_small_kernel(const float* __re
   }
 }
 
-static int simple_headtrain_check(const KvqHeadTrainArgs* a, const char* who, SimpleHeadTrainPlan* plan) {
-  KVQ_REQUIRE(a && a->feat && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
+static int simple_headtrain_check(const HeadTrainCall* a, const char* who, SimpleHeadTrainPlan* plan) {
+  KVQ_REQUIRE(a->feat.rows && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
   KVQ_REQUIRE(a->B >= 2 && a->B <= 1024 && a->L >= 1, KVQ_ERR_SHAPE, "%s: B %d outside 2 .. 1024 or T %d below 1", who, a->B, a->L);
   KVQ_REQUIRE((long)a->B * a->L <= (1L << 24), KVQ_ERR_SHAPE, "%s: B*T = %ld rows exceed 2^24", who, (long)a->B * a->L);
   KVQ_REQUIRE(a->hidden == SH_HID, KVQ_ERR_UNSUPPORTED, "%s: hidden %d (128 is built)", who, a->hidden);
   KVQ_REQUIRE(a->C >= 64 && a->C % 64 == 0, KVQ_ERR_UNSUPPORTED, "%s: C %d is not a multiple of 64", who, a->C);
   KVQ_REQUIRE(a->p_drop == 0.f, KVQ_ERR_UNSUPPORTED, "%s: p_drop %g (simpleVQAHead has no dropout: 0)", who, (double)a->p_drop);
-  KVQ_REQUIRE((((uintptr_t)a->feat | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
+  KVQ_REQUIRE((((uintptr_t)a->feat.rows | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
               "%s: feat, params and workspace must be 16-byte aligned", who);
   *plan = simple_headtrain_plan(a->B, a->L, a->C);
   KVQ_REQUIRE(a->workspace_bytes >= plan->total * sizeof(float), KVQ_ERR_WORKSPACE, "%s: workspace %zu bytes, %zu needed", who,
@@ -222,11 +239,12 @@ extern "C" size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int 
   return kvq::simple_headtrain_plan(B, T, C).total * sizeof(float);
 }
 
-extern "C" int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
+namespace kvq {
+
+static int simple_headtrain_forward_call(const HeadTrainCall* a, const char* who, void* stream) {
   SimpleHeadTrainPlan pl;
-  if (int rc = simple_headtrain_check(a, "kvq_simple_headtrain_forward", &pl)) return rc;
-  KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "kvq_simple_headtrain_forward: NULL pointer");
+  if (int rc = simple_headtrain_check(a, who, &pl)) return rc;
+  KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "%s: NULL pointer", who);
   float* ws = static_cast<float*>(a->workspace);
   const float* w1 = a->params;
   const float* b1 = w1 + (size_t)SH_HID * a->C;
@@ -234,29 +252,66 @@ extern "C" int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* a, void* str
   const float* b2 = w2 + SH_HID;
   if (int rc = launch("simple_fwd_u_kernel", simple_fwd_u_kernel, dim3((unsigned)(a->C / 64)), dim3(256), 0, stream, w1, w2, a->C, ws + pl.u))
     return rc;
-  if (int rc = launch("simple_fwd_rows_kernel", simple_fwd_rows_kernel, grid_1d(pl.N * pl.nseg, 4), dim3(256), 0, stream, a->feat, ws + pl.u,
-                      pl.N, a->C, pl.nseg, ws + pl.part))
+  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+        using E = decltype(e);
+        return launch("simple_fwd_rows_kernel", simple_fwd_rows_kernel<E, decltype(idx)::value>, grid_1d(pl.N * pl.nseg, 4), dim3(256), 0,
+                      stream, static_cast<const E*>(a->feat.rows), a->feat.index, a->feat.n_rows, a->L, ws + pl.u, pl.N, a->C, pl.nseg,
+                      ws + pl.part);
+      }))
     return rc;
   return launch("simple_fwd_score_kernel", simple_fwd_score_kernel, dim3((unsigned)a->B), dim3(64), 0, stream, ws + pl.part, a->L * pl.nseg,
                 a->L, b1, w2, b2, a->score);
 }
 
-extern "C" int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
+static int simple_headtrain_backward_call(const HeadTrainCall* a, const char* who, void* stream) {
   SimpleHeadTrainPlan pl;
-  if (int rc = simple_headtrain_check(a, "kvq_simple_headtrain_backward", &pl)) return rc;
-  KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "kvq_simple_headtrain_backward: NULL pointer");
-  KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "kvq_simple_headtrain_backward: grads must be 16-byte aligned");
+  if (int rc = simple_headtrain_check(a, who, &pl)) return rc;
+  KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "%s: NULL pointer", who);
+  KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "%s: grads must be 16-byte aligned", who);
   float* ws = static_cast<float*>(a->workspace);
   const float* w1 = a->params;
   const float* b1 = w1 + (size_t)SH_HID * a->C;
   const float* w2 = b1 + SH_HID;
-  if (int rc = launch("simple_bwd_g_kernel", simple_bwd_g_kernel, dim3((unsigned)((a->C + 127) / 128), (unsigned)pl.nchunks), dim3(256), 0, stream,
-                      a->feat, a->dscore, pl.N, a->L, a->C, pl.chunk, ws + pl.gpart))
+  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+        using E = decltype(e);
+        return launch("simple_bwd_g_kernel", simple_bwd_g_kernel<E, decltype(idx)::value>,
+                      dim3((unsigned)((a->C + 127) / 128), (unsigned)pl.nchunks), dim3(256), 0, stream, static_cast<const E*>(a->feat.rows),
+                      a->feat.index, a->feat.n_rows, a->dscore, pl.N, a->L, a->C, pl.chunk, ws + pl.gpart);
+      }))
     return rc;
   if (int rc = launch("simple_bwd_w1_kernel", simple_bwd_w1_kernel, dim3((unsigned)((a->C + 255) / 256), 8u), dim3(256), 0, stream, ws + pl.gpart,
                       w2, a->C, pl.nchunks, ws + pl.g, a->grads))
     return rc;
   return launch("simple_bwd_small_kernel", simple_bwd_small_kernel, dim3((unsigned)SH_HID), dim3(256), 0, stream, w1, b1, w2, ws + pl.g, a->dscore,
                 a->B, a->C, a->grads + (size_t)SH_HID * a->C);
+}
+
+}  // namespace kvq
+
+extern "C" int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_simple_headtrain_forward: NULL pointer");
+  const HeadTrainCall c = headtrain_call(a);
+  return simple_headtrain_forward_call(&c, "kvq_simple_headtrain_forward", stream);
+}
+
+extern "C" int kvq_simple_headtrain_bank_forward(const KvqHeadTrainBankArgs* a, void* stream) {
+  using namespace kvq;
+  if (int rc = headtrain_bank_check(a, "kvq_simple_headtrain_bank_forward")) return rc;
+  const HeadTrainCall c = headtrain_call(a);
+  return simple_headtrain_forward_call(&c, "kvq_simple_headtrain_bank_forward", stream);
+}
+
+extern "C" int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* a, void* stream) {
+  using namespace kvq;
+  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_simple_headtrain_backward: NULL pointer");
+  const HeadTrainCall c = headtrain_call(a);
+  return simple_headtrain_backward_call(&c, "kvq_simple_headtrain_backward", stream);
+}
+
+extern "C" int kvq_simple_headtrain_bank_backward(const KvqHeadTrainBankArgs* a, void* stream) {
+  using namespace kvq;
+  if (int rc = headtrain_bank_check(a, "kvq_simple_headtrain_bank_backward")) return rc;
+  const HeadTrainCall c = headtrain_call(a);
+  return simple_headtrain_backward_call(&c, "kvq_simple_headtrain_bank_backward", stream);
 }

@@ -107,15 +107,44 @@ def get_resized_video(video, size_h=224, size_w=224, random_crop=False, arp=Fals
     return kernels.resize_bilinear(_rgb_frames(video).contiguous(), size_h, size_w, mean=mean, std=std, antialias=antialias)
 
 
+def train_crop_offsets(resize: int, crop: int):
+    """the reference's train-phase crop of the (resize, resize) frames (:308-312): ``rnd_h`` then ``rnd_w``, each
+    ``random.randrange(resize - crop)`` of Python's global ``random``.  Host integers only.  ``resize == crop`` (or less) raises
+    ValueError, as the reference's ``randrange(0)`` does."""
+    if resize - crop <= 0:
+        raise ValueError(f"train-phase crop of {crop} out of {resize}: the reference draws random.randrange({resize - crop}), an empty range")
+    rnd_h = _pyrandom.randrange(resize - crop)
+    rnd_w = _pyrandom.randrange(resize - crop)
+    return rnd_h, rnd_w
+
+
 def get_resizecrop_video(video, resize=520, crop=448, phase="test", mean=None, std=None, antialias=False, **kwargs):
-    """Reference ``get_resizecrop_video`` (:299-316), test phase: resize to (resize,resize) then the centre
-    crop [r//2-crop//2 : r//2+crop//2] — fused with the normalisation in one kernel."""
+    """Reference ``get_resizecrop_video`` (:299-316): resize to (resize,resize), then the centre crop
+    [r//2-crop//2 : r//2+crop//2] (test phase) or the random crop of ``train_crop_offsets`` (train phase) — fused with the
+    normalisation in one kernel: only the crop's pixels are computed."""
     if phase == "train":
-        raise NotImplementedError("random crop is a training augmentation")
-    o = resize // 2 - crop // 2
-    n = (resize // 2 + crop // 2) - o
-    return kernels.resize_bilinear(_rgb_frames(video).contiguous(), resize, resize, crop=(o, o, n, n), mean=mean, std=std,
+        oy, ox = train_crop_offsets(resize, crop)
+        n = crop
+    else:
+        oy = ox = resize // 2 - crop // 2
+        n = (resize // 2 + crop // 2) - oy
+    return kernels.resize_bilinear(_rgb_frames(video).contiguous(), resize, resize, crop=(oy, ox, n, n), mean=mean, std=std,
                                    antialias=antialias)
+
+
+DRAW_SEED_STRIDE = 1000003
+
+
+def _item_seed(index: int, draw: int) -> int:
+    """the per-item seed of ``seed_per_item`` for train-phase draw ``draw`` (``set_draw``): draw 0 is 1234 + index"""
+    return 1234 + index + DRAW_SEED_STRIDE * draw
+
+
+def _seed_item(index: int, draw: int):
+    s = _item_seed(index, draw)
+    np.random.seed(s)
+    _pyrandom.seed(s)
+    torch.manual_seed(s)
 
 
 def get_single_view(video, sample_type="aesthetic", antialias=False, **kwargs):
@@ -152,9 +181,14 @@ class SyntheticSimpleVQADataset(torch.utils.data.Dataset):
         self.slowfast = opt.get("compute_feat")
         g = np.random.Generator(np.random.PCG64(4321))
         self.labels = list(opt.get("labels") or g.uniform(1.0, 5.0, self.n))
+        self.phase, self.draw = opt.get("phase", "test"), 0     # 'train': the view takes the reference's random train-phase crop
 
     def __len__(self):
         return self.n
+
+    def set_draw(self, k: int):
+        """train-phase draw ``k`` of every item (see ``SyntheticKVQDataset.set_draw``)"""
+        self.draw = int(k)
 
     def _feat(self, i, frames_u8):
         import os
@@ -180,9 +214,11 @@ class SyntheticSimpleVQADataset(torch.utils.data.Dataset):
     def __getitem__(self, i):
         from ..utils import synth
         frames = torch.from_numpy(synth.synth_video_u8(1234 + i, self.frames, self.h, self.w))
+        if self.opt.get("seed_per_item"):
+            _seed_item(i, self.draw)
         inds = self.sampler(self.frames)
         clip = frames[:, torch.from_numpy(inds.astype(np.int64))].to(self.device)
-        view = get_resizecrop_video(clip, self.sopt["resize"], self.sopt["crop"], "test", mean=SIMPLEVQA_MEAN,
+        view = get_resizecrop_video(clip, self.sopt["resize"], self.sopt["crop"], "train" if self.phase == "train" else "test", mean=SIMPLEVQA_MEAN,
                                     std=SIMPLEVQA_STD, antialias=bool(self.sopt.get("antialias", False)))
         return {"simpleVQA": view, "feat": self._feat(i, frames).unsqueeze(0), "num_clips": {"simpleVQA": self.sopt["num_clips"]},
                 "frame_inds": inds, "label": float(self.labels[i]), "name": f"synthetic_{i:05d}",
@@ -234,9 +270,15 @@ class SyntheticKVQDataset(torch.utils.data.Dataset):
                                        for s in (self.sopt, self.aopt))
         g = np.random.Generator(np.random.PCG64(4321))
         self.labels = list(opt.get("labels") or g.uniform(1.0, 5.0, self.n))
+        self.draw = 0
 
     def __len__(self):
         return self.n
+
+    def set_draw(self, k: int):
+        """train-phase draw ``k`` of every item: with ``seed_per_item`` the item's seed moves by ``DRAW_SEED_STRIDE * k`` (draw 0: the
+        items as they always were); without it the global RNGs simply move on, as in the reference"""
+        self.draw = int(k)
 
     def __getitem__(self, i):
         from ..utils import synth
@@ -245,9 +287,7 @@ class SyntheticKVQDataset(torch.utils.data.Dataset):
         if self.opt.get("seed_per_item"):
             # the samplers draw from the process-global RNGs like the reference's (a1 / a2): seeding them per item makes item i
             # the same whatever rank builds it and whatever was built before (the 1-rank vs N-rank rehearsal of C4)
-            np.random.seed(1234 + i)
-            _pyrandom.seed(1234 + i)
-            torch.manual_seed(1234 + i)
+            _seed_item(i, self.draw)
         item = {"num_clips": {}}
         if s is not None:
             inds = self.sampler(self.frames)
@@ -1161,8 +1201,10 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
         self.data_prefix_3D = opt.get("data_prefix_3D") if self.motion["source"] == "inline" else opt["data_prefix_3D"]
         self.sample_types, self.feature_type, self.phase = opt["sample_types"], opt["feature_type"], opt["phase"]
         self.augment = opt.get("augment", False)
-        if self.phase == "train" or self.augment:
-            raise NotImplementedError("training-phase sampling / augmentation: this is an inference engine")
+        if self.augment:
+            raise NotImplementedError("augment: the training augmentations (RandomResizedCrop, flips) are not built; phase 'train' "
+                                      "without them samples as the reference does")
+        self.draw = 0
         self.samplers = _build_samplers(self.sample_types, self.phase)
         if isinstance(self.ann_file, list):
             self.video_infos = self.ann_file
@@ -1180,6 +1222,10 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
 
     def __len__(self):
         return len(self.video_infos)
+
+    def set_draw(self, k: int):
+        """train-phase draw ``k`` of every item (see ``SyntheticKVQDataset.set_draw``)"""
+        self.draw = int(k)
 
     def _features(self, video_name):
         import os
@@ -1216,17 +1262,19 @@ class ViewDecompositionDataset_add_forSimpleVQA(torch.utils.data.Dataset):  # no
 
     def __getitem__(self, index):
         info = self.video_infos[index]
+        if self.opt.get("seed_per_item"):
+            _seed_item(index, self.draw)
         vr = None
         if self.motion["source"] == "inline":
             vr = open_video(info["filename"], self.opt.get("yuv_matrix", "bt601"))
             feat = self._features_inline(vr, info["filename"])
         else:
             feat = self._features(info["video_name"])
-        video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"),
-                                            self.opt.get("jpeg_entropy"), vr)
+        video, frame_inds = _sampled_clips(info["filename"], self.samplers, self.phase == "train", self.device,
+                                            self.opt.get("yuv_matrix", "bt601"), self.opt.get("jpeg_entropy"), vr)
         data = {}
         for stype, sopt in self.sample_types.items():
-            kw = dict(sopt, phase="test")
+            kw = dict(sopt, phase=self.phase)
             data[stype] = get_single_view(video[stype], stype, mean=SIMPLEVQA_MEAN, std=SIMPLEVQA_STD, **kw)
         data["num_clips"] = {k: s["num_clips"] for k, s in self.sample_types.items()}
         data["clip_len"] = {k: s["clip_len"] for k, s in self.sample_types.items()}
@@ -1257,7 +1305,12 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
         self.sample_types, self.phase = opt["sample_types"], opt["phase"]
         self.augment = opt.get("augment", False)
         if self.phase == "train" or self.augment:
-            raise NotImplementedError("training-phase sampling / augmentation: this is an inference engine")
+            # the reference's train phase draws this class's views (fragments, resized frames, frame indices) exactly as its test phase
+            # does — get_spatial_fragments and UnifiedFrameSampler ignore the flag — so 'train' without augment would add nothing:
+            # phase 'test' with set_draw(k) gives the train-phase draws
+            raise NotImplementedError("training-phase sampling / augmentation: this is an inference engine (phase 'test' with "
+                                      "set_draw(k) draws what the reference's train phase draws; its augmentations are not built)")
+        self.draw = 0
         self.samplers = _build_samplers(self.sample_types, self.phase)
         if isinstance(self.ann_file, list):
             self.video_infos = self.ann_file
@@ -1277,14 +1330,16 @@ class ViewDecompositionDataset_KVQ(torch.utils.data.Dataset):  # noqa: N801  (re
     def __len__(self):
         return len(self.video_infos)
 
+    def set_draw(self, k: int):
+        """train-phase draw ``k`` of every item (see ``SyntheticKVQDataset.set_draw``)"""
+        self.draw = int(k)
+
     def __getitem__(self, index):
         info = self.video_infos[index]
         if self.opt.get("seed_per_item"):
             # as SyntheticKVQDataset: the samplers draw from the process-global RNGs; seeded per item, item i is the same whatever
             # was built before it (two runs over two trees of the same videos then draw the same frames and offsets)
-            np.random.seed(1234 + index)
-            _pyrandom.seed(1234 + index)
-            torch.manual_seed(1234 + index)
+            _seed_item(index, self.draw)
         video, frame_inds = _sampled_clips(info["filename"], self.samplers, False, self.device, self.opt.get("yuv_matrix", "bt601"),
                                             self.opt.get("jpeg_entropy"))
         data, k = {}, None

@@ -3,13 +3,19 @@ on cached features of the frozen backbone.  Forward, loss, backward, AdamW and t
 (``kernels.headtrain_*``); nothing here goes through autograd, and no gradient reaches a backbone.
 
     ft = HeadFinetuner(model, "swin_tiny_grpb", lr=1e-3, wd=0.05, warmup_iters=10, max_iters=100)
-    ft.cache_features(dataset, trainer)          # one frozen forward per video
+    ft.cache_features(dataset, trainer)          # one frozen forward per video, into the feature bank
     ft.fit(epochs=5, batch_size=16)
     ft.write_back()                              # the VQAHead's nn.Parameters now hold the trained weights
 
 The dropout masks are this project's counter-based hash of (seed, step, which, element) (csrc/headtrain.hpp): torch's random stream
 cannot be reproduced, and a hash needs no mask tensor.  Built: ``VQAHead`` with one class, hidden 64, no pre-pool, channels a multiple
 of 64, batches of 2 .. 1024 clips.
+
+The cached features live in one **feature bank** (``kernels.FeatureBank``, csrc/featbank.hip): ``[draws * samples][L][C]`` in fp32, fp16
+or bf16, written by the store launch straight from the trunk's output.  ``cache_features(..., draws=K)`` samples every video K times
+(``dataset.set_draw(k)``: the reference re-samples every video in every epoch); epoch ``e`` trains on draw ``e % K``.  A batch is an int32
+index vector into the bank: the step's launches read the rows where they lie and widen 16-bit rows in registers, which is exact, so a
+step on a bank equals the dense fp32 step on the widened rows bit for bit.
 
 ``SimpleHeadFinetuner`` is the same for the 1.2 M parameters of a ``simpleVQAHead`` (model key ``simpleVQA``): two Linears per frame and
 the mean over the frames, no dropout (csrc/simple_headtrain.hip, ``kernels.simple_headtrain_*``); a sample is one video's (T, C) feature
@@ -21,7 +27,7 @@ import math
 
 import torch
 
-from . import kernels
+from . import _abi, kernels
 from .models.head import VQAHead, simpleVQAHead
 
 HIDDEN = 64
@@ -35,11 +41,20 @@ def lr_factor(it: int, warmup_iters: int, max_iters: int) -> float:
     return 0.5 * (1 + math.cos(math.pi * (it - warmup_iters) / max_iters))
 
 
+def _widened(feats):
+    """dense fp32 [B][L][C] of features on the device: 16-bit rows (a bank's) are widened by the gather launch, exactly"""
+    if feats.dtype in kernels.HALF_TYPES:
+        bank = kernels.FeatureBank.of(feats.contiguous())
+        return kernels.feature_bank_rows(bank, torch.arange(bank.n_rows, dtype=torch.int32, device=feats.device))
+    return feats.to(torch.float32).contiguous()
+
+
 class _Finetuner:
     """What the finetuners of the two head types share: the flat parameter vector with its AdamW state and EMA copy, the schedule, the
     feature cache, the step around the head's own launches, the epochs and the write-back.  A subclass sets ``hidden`` and gives
     ``_check_head`` (refusals; -> in_channels), ``_head_params`` (the head's four nn.Parameters in flat order), ``_clip_features``
-    (the backbone's output of one video -> [samples][L][C]), ``_forward`` / ``_backward`` (the launches) and ``predict``."""
+    (the backbone's output of one video -> [samples][L][C]), ``_forward`` / ``_backward`` (the launches on a dense batch),
+    ``_bank_forward`` / ``_bank_backward`` (the same on bank rows) and ``predict``."""
     hidden = None
 
     def __init__(self, model, key, lr, wd, warmup_iters, max_iters, ema=True, seed=0, rank_weight=0.0):
@@ -59,6 +74,7 @@ class _Finetuner:
         self.grads = torch.empty_like(self.params)
         self.it = 0                                  # iterations done = the scheduler's counter = the mask hash's step
         self.feats, self.labels, self.names = [], [], []
+        self.bank, self.n, self.draws, self.epoch = None, 0, 1, 0    # epoch: passes fit() has made, kept across calls: it picks the draw
         self._trainer = None
         self._ws = {}
         self._perm = torch.Generator().manual_seed(self.seed)
@@ -72,32 +88,75 @@ class _Finetuner:
         self.warmup_iters, self.max_iters = int(warmup_iters), int(max_iters)
 
     # ---- features of the frozen trunk ---------------------------------------------------------------------------------------------
-    def cache_features(self, dataset, trainer):
-        """one eval-mode forward of the frozen model per video: keeps every sample's fp32 features on the device, [samples][L][C]
-        (VQAHead: a clip's feature map, channels-last; simpleVQAHead: a video's T feature rows), with the video's label"""
+    def cache_features(self, dataset, trainer, draws=1, dtype=torch.float32):
+        """``draws`` eval-mode forwards of the frozen model per video (draw k after ``dataset.set_draw(k)``, if the dataset has it), each
+        stored by one launch from the model's output into the feature bank: ``bank.tensor`` [draws * n][L][C] of ``dtype`` (fp32, fp16
+        or bf16), row = draw * n + sample, n = videos * samples per video (VQAHead: a clip's feature map, channels-last; simpleVQAHead:
+        a video's T feature rows).  ``feats`` is the list of per-video views of draw 0, with the video's label in ``labels``.
+        An fp16 bank that would have to saturate a value, or any bank that met a NaN, raises ValueError."""
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError(f"draws = {draws}: at least one draw per video")
+        code = _abi.bank_dtype_code(dtype)
+        tdtype = _abi.bank_torch_dtype(code)
         self._trainer = trainer
         self.model.eval()
-        self.feats, self.labels, self.names = [], [], []
-        for i in range(len(dataset)):
-            item = dataset[i]
-            with torch.no_grad():
-                out = self.model(inputs=trainer._model_inputs(item), return_pooled_feats=True, reduce_scores=True)
-            feat = out[1][self.key]                  # (scores, feats[, contrastive loss]); KSVQE's (features, loss) is split by the model
-            if isinstance(feat, (tuple, list)):
-                feat = feat[0]
-            self.feats.append(self._clip_features(feat))
-            self.labels.append(float(item["label"]))
-            self.names.append(item.get("video_name", str(i)) if isinstance(item, dict) else str(i))
+        self.feats, self.labels, self.names, self.bank = [], [], [], None
+        videos = len(dataset)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        per = None
+        try:
+            for k in range(draws):
+                if hasattr(dataset, "set_draw"):
+                    dataset.set_draw(k)
+                for i in range(videos):
+                    item = dataset[i]
+                    with torch.no_grad():
+                        out = self.model(inputs=trainer._model_inputs(item), return_pooled_feats=True, reduce_scores=True)
+                    feat = out[1][self.key]          # (scores, feats[, contrastive loss]); KSVQE's (features, loss) is split by the model
+                    if isinstance(feat, (tuple, list)):
+                        feat = feat[0]
+                    view = self._clip_features(feat)             # fp32 [samples][L][C], channel stride 1: a view where the layout allows
+                    if self.bank is None:
+                        per = tuple(view.shape)
+                        rows = draws * videos * per[0]
+                        need = rows * per[1] * per[2] * torch.empty(0, dtype=tdtype).element_size()
+                        free = torch.cuda.mem_get_info(self.device)[0]
+                        if need > free:
+                            raise ValueError(f"a feature bank of {rows} rows x {per[1]} x {per[2]} takes {need} bytes with draws = {draws}, dtype = "
+                                             f"{tdtype}: the device has {free} bytes free (fewer draws, or a 16-bit dtype)")
+                        self.bank = kernels.FeatureBank(rows, per[1], per[2], tdtype, device=self.device)
+                    elif tuple(view.shape) != per:
+                        raise NotImplementedError("the cached videos have feature maps of different sizes: one batch needs one (L, C)")
+                    kernels.feature_bank_store(view, self.bank, (k * videos + i) * per[0], flag)
+                    if k == 0:
+                        self.labels.append(float(item["label"]))
+                        self.names.append(item.get("video_name", str(i)) if isinstance(item, dict) else str(i))
+        finally:
+            if hasattr(dataset, "set_draw"):
+                dataset.set_draw(0)
+        if videos and int(flag.item()):                          # the one synchronisation of caching
+            self.bank = None
+            raise ValueError(f"the features do not fit a {tdtype} bank: a value past +-65504 (fp16 would store it saturated) or a NaN was met; "
+                             "use dtype bf16 or fp32")
+        self.draws, self.epoch = draws, 0
+        self.n = videos * per[0] if videos else 0
+        self.feats = [self.bank.tensor[i * per[0]:(i + 1) * per[0]] for i in range(videos)]
         return len(self.feats)
 
+    def sample_labels(self):
+        """the label of every sample of one draw, [n] on the device: every cached clip carries its video's label"""
+        return torch.tensor([l for f, l in zip(self.feats, self.labels) for _ in range(f.shape[0])], dtype=torch.float32, device=self.device)
+
     def clip_samples(self):
-        """every cached clip as one sample carrying its video's label -> (feats [N][L][C], labels [N])"""
+        """every cached clip of draw 0 as one sample carrying its video's label -> (feats fp32 [N][L][C], labels [N]); an fp32 bank
+        gives a view of its rows, a 16-bit bank a widened copy"""
         if not self.feats:
             raise RuntimeError("no cached features: call cache_features(dataset, trainer) first")
-        if len({f.shape[1:] for f in self.feats}) != 1:
-            raise NotImplementedError("the cached videos have feature maps of different sizes: one batch needs one (L, C)")
-        labels = torch.tensor([l for f, l in zip(self.feats, self.labels) for _ in range(f.shape[0])], dtype=torch.float32, device=self.device)
-        return torch.cat(self.feats), labels
+        feats = self.bank.tensor[:self.n]
+        if feats.dtype != torch.float32:
+            feats = kernels.feature_bank_rows(self.bank, torch.arange(self.n, dtype=torch.int32, device=self.device))
+        return feats, self.sample_labels()
 
     # ---- one optimisation step -----------------------------------------------------------------------------------------------------
     def _workspace(self, B, L):
@@ -127,19 +186,45 @@ class _Finetuner:
         loss, plcc, rank = out3.tolist()
         return {"loss": loss, "plcc_loss": plcc, "rank_loss": rank, "lr": lr}
 
+    def step_indexed(self, index, labels):
+        """``step`` on the bank rows ``index`` (int32 on the device, or a CPU tensor, which is checked against the bank and uploaded),
+        read in place: equal to ``step(feature_bank_rows(bank, index), labels)`` bit for bit, without the gathered copy"""
+        if self.bank is None:
+            raise RuntimeError("no feature bank: call cache_features(dataset, trainer) first")
+        index = kernels.bank_index(index, self.bank)
+        labels = torch.as_tensor(labels, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
+        B = index.numel()
+        if self.bank.C != self.C or labels.numel() != B:
+            raise ValueError(f"step_indexed(): {B} rows of a bank {tuple(self.bank.tensor.shape)} / {labels.numel()} labels do not fit a "
+                             f"{self.C}-channel head")
+        ws = self._workspace(B, self.bank.L)
+        score = self._bank_forward(index, ws)
+        out3, dscore = kernels.headtrain_loss(score, labels, self.rank_weight)
+        self._bank_backward(index, ws, dscore)
+        lr = self.current_lr()
+        kernels.headtrain_adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.ema, lr, self.wd, self.it + 1)
+        self.it += 1
+        loss, plcc, rank = out3.tolist()
+        return {"loss": loss, "plcc_loss": plcc, "rank_loss": rank, "lr": lr}
+
     def fit(self, epochs, batch_size):
-        """``epochs`` passes over the cached clips: a seeded permutation cut into batches of ``batch_size``; a last batch shorter than 3
-        is dropped (with two samples the PLCC loss is constant).  -> the list of step() results"""
-        feats, labels = self.clip_samples()
-        n, log = feats.shape[0], []
+        """``epochs`` passes over the cached samples: pass e (counted across calls) trains on draw ``e % draws``; a seeded permutation of
+        the n samples is cut into batches of ``batch_size``, each an index vector ``draw * n + order[s:s + batch_size]`` into the bank; a
+        last batch shorter than 3 is dropped (with two samples the PLCC loss is constant).  -> the list of step results"""
+        if not self.feats:
+            raise RuntimeError("no cached features: call cache_features(dataset, trainer) first")
+        labels = self.sample_labels()
+        n, log = self.n, []
         for _ in range(int(epochs)):
+            draw = self.epoch % self.draws
+            self.epoch += 1
             order = torch.randperm(n, generator=self._perm)
             for s in range(0, n, int(batch_size)):
                 idx = order[s:s + int(batch_size)]
                 if idx.numel() < 3:
                     continue
                 idx = idx.to(self.device)
-                log.append(self.step(feats.index_select(0, idx), labels.index_select(0, idx)))
+                log.append(self.step_indexed((idx + draw * n).to(torch.int32), labels.index_select(0, idx)))
         return log
 
     # ---- the trained head ------------------------------------------------------------------------------------------------------------
@@ -185,7 +270,9 @@ class HeadFinetuner(_Finetuner):
 
     def _clip_features(self, feat):
         B, C = feat.shape[:2]                        # (clips, C, D, H, W) -> channels-last [clips][L][C]
-        return feat.to(torch.float32).reshape(B, C, -1).transpose(1, 2).contiguous()
+        # the trunk stores its output channels-last behind the (B, C, D, H, W) view: the permutation is then dense and the reshape a
+        # view, which the store launch reads in place; any other layout is copied here
+        return feat.to(torch.float32).permute(0, 2, 3, 4, 1).reshape(B, -1, C)
 
     def _new_workspace(self, B, L):
         return kernels.headtrain_workspace(B, L, self.C, HIDDEN, device=self.device)
@@ -196,9 +283,16 @@ class HeadFinetuner(_Finetuner):
     def _backward(self, feats, ws, dscore):
         kernels.headtrain_backward(feats, self.params, self.p_drop, self.seed, self.it, ws, dscore, self.grads)
 
+    def _bank_forward(self, index, ws):
+        return kernels.headtrain_bank_forward(self.bank, index, self.params, self.p_drop, self.seed, self.it, ws)
+
+    def _bank_backward(self, index, ws, dscore):
+        kernels.headtrain_bank_backward(self.bank, index, self.params, self.p_drop, self.seed, self.it, ws, dscore, self.grads)
+
     def predict(self, feats, ema=False):
-        """eval-mode scores [B] of features [B][L][C] with the current weights (``ema``: the EMA copy), by the inference launch"""
-        feats = feats.to(self.device, torch.float32).contiguous()
+        """eval-mode scores [B] of features [B][L][C] (fp32, or the 16-bit rows of a bank, widened here) with the current weights
+        (``ema``: the EMA copy), by the inference launch"""
+        feats = _widened(feats.to(self.device))
         B, L, C = feats.shape
         w1, b1, w2, b2 = self._split(self._weights(ema))
         x = feats.as_strided((B, C, 1, 1, L), (L * C, 1, L * C, L * C, C))
@@ -225,7 +319,7 @@ class SimpleHeadFinetuner(_Finetuner):
         return q[0].weight, q[0].bias, q[1].weight, q[1].bias
 
     def _clip_features(self, feat):
-        return feat.to(torch.float32).contiguous()   # (rows, T, C) as the backbone gives it
+        return feat.to(torch.float32)                # (rows, T, C) as the backbone gives it
 
     def _new_workspace(self, B, L):
         return kernels.simple_headtrain_workspace(B, L, self.C, SIMPLE_HIDDEN, device=self.device)
@@ -236,10 +330,39 @@ class SimpleHeadFinetuner(_Finetuner):
     def _backward(self, feats, ws, dscore):
         kernels.simple_headtrain_backward(feats, self.params, ws, dscore, self.grads)
 
+    def _bank_forward(self, index, ws):
+        return kernels.simple_headtrain_bank_forward(self.bank, index, self.params, ws)
+
+    def _bank_backward(self, index, ws, dscore):
+        kernels.simple_headtrain_bank_backward(self.bank, index, self.params, ws, dscore, self.grads)
+
     def predict(self, feats, ema=False):
         """scores [B] of features [B][T][C] with the current weights (``ema``: the EMA copy), by the inference launch"""
         w1, b1, w2, b2 = self._split(self._weights(ema))
-        return kernels.simple_vqa_head(feats.to(self.device, torch.float32), w1, b1, w2, b2).reshape(-1)
+        return kernels.simple_vqa_head(_widened(feats.to(self.device)), w1, b1, w2, b2).reshape(-1)
+
+
+BANK_KEYS = ("draws", "dtype")
+BANK_DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def feature_bank_options(cfg):
+    """the optional top-level yml key ``feature_bank: {draws: 1, dtype: fp32 | fp16 | bf16}`` -> (draws, torch dtype); absent: (1, fp32),
+    the behaviour without the key.  An unknown key or value raises ValueError naming it."""
+    fb = cfg.get("feature_bank")
+    if fb is None:
+        return 1, torch.float32
+    if not isinstance(fb, dict):
+        raise ValueError(f"feature_bank: expected a mapping with the keys {', '.join(BANK_KEYS)}, got {fb!r}")
+    for k in fb:
+        if k not in BANK_KEYS:
+            raise ValueError(f"feature_bank: unknown key {k!r} (known: {', '.join(BANK_KEYS)})")
+    draws, name = fb.get("draws", 1), fb.get("dtype", "fp32")
+    if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+        raise ValueError(f"feature_bank.draws must be an integer of at least 1, got {draws!r}")
+    if name not in BANK_DTYPES:
+        raise ValueError(f"feature_bank.dtype must be one of {', '.join(BANK_DTYPES)}, got {name!r}")
+    return draws, BANK_DTYPES[name]
 
 
 def finetuner_for(head):

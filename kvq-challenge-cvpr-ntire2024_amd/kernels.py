@@ -1831,3 +1831,117 @@ def simple_headtrain_backward(feat, params, ws, dscore, grads=None):
     a = _simple_headtrain_args(feat, params, ws, dscore=dscore, grads=grads)
     check(lib().kvq_simple_headtrain_backward(C.byref(a), stream_of(feat)), "kvq_simple_headtrain_backward")
     return grads
+
+
+# ---- feature bank (csrc/featbank.hip) and the two training steps on its rows: thin wrappers; kvq_amd/finetune.py drives them ------------
+class FeatureBank:
+    """``[n_rows][L][C]`` cached features of a frozen trunk on the device, fp32, fp16 or bf16: ``tensor`` owns the memory, ``view`` is
+    the ``KvqFeatureBank`` the entries take.  ``tensor``: adopt an existing dense tensor instead of allocating one."""
+
+    def __init__(self, n_rows: int, L: int, C_in: int, dtype=torch.float32, device=None, tensor=None):
+        code = _abi.bank_dtype_code(dtype)
+        if tensor is None:
+            tensor = torch.empty(int(n_rows), int(L), int(C_in), dtype=_abi.bank_torch_dtype(code), device=device if device is not None else "cuda")
+        assert tensor.dim() == 3 and tensor.is_contiguous() and tensor.dtype == _abi.bank_torch_dtype(code), "a bank is dense [n_rows][L][C]"
+        self.tensor, self.dtype = tensor, tensor.dtype
+        self.n_rows, self.L, self.C = (int(v) for v in tensor.shape)
+        self.view = _abi.KvqFeatureBank(ptr(tensor), code, self.L, self.C, self.n_rows)
+
+    @classmethod
+    def of(cls, tensor):
+        return cls(*tensor.shape, dtype=tensor.dtype, tensor=tensor)
+
+    @property
+    def nbytes(self) -> int:
+        return self.tensor.numel() * self.tensor.element_size()
+
+
+def bank_index(index, bank: "FeatureBank") -> torch.Tensor:
+    """the index vector of a bank entry as int32 on the bank's device.  A CPU tensor (or a sequence) is checked here: a value outside
+    ``[0, n_rows)`` raises ValueError naming it; a device tensor is not read back — the launches clamp its values into the bank."""
+    if not isinstance(index, torch.Tensor):
+        index = torch.as_tensor(index, dtype=torch.int64)
+    if not index.is_cuda:
+        index = index.reshape(-1)
+        bad = ((index < 0) | (index >= bank.n_rows)).nonzero()
+        if bad.numel():
+            k = int(bad[0])
+            raise ValueError(f"index[{k}] = {int(index[k])} is outside the bank's rows 0 .. {bank.n_rows - 1}")
+        return index.to(torch.int32).to(bank.tensor.device)
+    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "a device index is a dense int32 vector"
+    return index
+
+
+def feature_bank_store(feat: torch.Tensor, bank: FeatureBank, first_row: int, flag: Optional[torch.Tensor] = None):
+    """rows ``first_row ..`` of the bank = the fp32 features ``feat`` [n][L][C], any sample and token strides (multiples of 4), channel
+    stride 1: read where they lie, rounded to nearest even.  ``flag`` (int32 [1] on the device, never cleared here) becomes 1 when a
+    NaN is stored, or a value past +-65504 into an fp16 bank (stored as +-65504)."""
+    _need_gpu(feat, bank.tensor, flag)
+    assert feat.dtype == torch.float32 and feat.dim() == 3 and tuple(feat.shape[1:]) == (bank.L, bank.C), "features: fp32 [n][L][C] of the bank's (L, C)"
+    assert feat.stride(2) == 1 or bank.C == 1, "the channel stride of the features must be 1"
+    assert flag is None or (flag.dtype == torch.int32 and flag.numel() == 1)
+    check(lib().kvq_feature_bank_store(ptr(feat), feat.shape[0], feat.stride(0), feat.stride(1), C.byref(bank.view), int(first_row),
+                                       ptr(flag), stream_of(feat)), "kvq_feature_bank_store")
+
+
+def feature_bank_rows(bank: FeatureBank, index, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dense fp32 [B][L][C]: the bank's rows ``index`` (``bank_index``), widened"""
+    idx = bank_index(index, bank)
+    _need_gpu(bank.tensor, idx, out)
+    if out is None:
+        out = torch.empty(idx.numel(), bank.L, bank.C, dtype=torch.float32, device=bank.tensor.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (idx.numel(), bank.L, bank.C)
+    check(lib().kvq_feature_bank_rows(C.byref(bank.view), ptr(idx), idx.numel(), ptr(out), stream_of(out)), "kvq_feature_bank_rows")
+    return out
+
+
+def _headtrain_bank_args(bank, index, params, p, seed, step, ws, hidden, count, score=None, dscore=None, grads=None):
+    idx = bank_index(index, bank)
+    _need_gpu(bank.tensor, idx, params, ws, score, dscore, grads)
+    B = idx.numel()
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == count(bank.C, hidden)
+    for t in (score, dscore):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B)
+    assert grads is None or (grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == params.numel())
+    a = _abi.KvqHeadTrainBankArgs()
+    a.bank, a.index, a.B, a.L, a.C, a.hidden, a.params = bank.view, ptr(idx), B, bank.L, bank.C, hidden, ptr(params)
+    a.p_drop, a.seed, a.step = float(p), seed & 0xFFFFFFFF, step & 0xFFFFFFFF
+    a.workspace, a.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
+    a.score, a.dscore, a.grads = ptr(score), ptr(dscore), ptr(grads)
+    return a, idx
+
+
+def headtrain_bank_forward(bank, index, params, p, seed, step, ws, score=None):
+    """``headtrain_forward`` on the bank rows ``index``, read in place: bit-equal to it on ``feature_bank_rows(bank, index)``"""
+    if score is None:
+        score = torch.empty(len(index), dtype=torch.float32, device=bank.tensor.device)
+    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, headtrain_param_count, score=score)
+    check(lib().kvq_headtrain_bank_forward(C.byref(a), stream_of(bank.tensor)), "kvq_headtrain_bank_forward")
+    return score
+
+
+def headtrain_bank_backward(bank, index, params, p, seed, step, ws, dscore, grads=None):
+    """``headtrain_backward`` on the bank rows ``index``, read in place"""
+    if grads is None:
+        grads = torch.empty_like(params)
+    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, headtrain_param_count, dscore=dscore, grads=grads)
+    check(lib().kvq_headtrain_bank_backward(C.byref(a), stream_of(bank.tensor)), "kvq_headtrain_bank_backward")
+    return grads
+
+
+def simple_headtrain_bank_forward(bank, index, params, ws, score=None):
+    """``simple_headtrain_forward`` on the bank rows ``index`` ([n_rows][T][C]), read in place"""
+    if score is None:
+        score = torch.empty(len(index), dtype=torch.float32, device=bank.tensor.device)
+    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, simple_headtrain_param_count, score=score)
+    check(lib().kvq_simple_headtrain_bank_forward(C.byref(a), stream_of(bank.tensor)), "kvq_simple_headtrain_bank_forward")
+    return score
+
+
+def simple_headtrain_bank_backward(bank, index, params, ws, dscore, grads=None):
+    """``simple_headtrain_backward`` on the bank rows ``index``, read in place"""
+    if grads is None:
+        grads = torch.empty_like(params)
+    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, simple_headtrain_param_count, dscore=dscore, grads=grads)
+    check(lib().kvq_simple_headtrain_bank_backward(C.byref(a), stream_of(bank.tensor)), "kvq_simple_headtrain_bank_backward")
+    return grads

@@ -539,10 +539,12 @@ class Trainer:
     def finetune_head(self):
         """The reference's yml schema: ``num_epochs``, ``l_num_epochs``, ``warmup_epochs``, ``batch_size`` (samples per batch: clips of a ``VQAHead`` model, videos of ``simpleVQA``), ``ema``,
         ``save_model``, ``optimizer.{lr, wd, backbone_lr_mult}``, ``data.train`` (sampled deterministically, ``phase: test``) and
-        ``data.val``.  After every epoch the trained head and the EMA head are scored on ``data.val`` with the ``inferece_val``
+        ``data.val``.  Not in the reference — ``feature_bank: {draws: 1, dtype: fp32 | fp16 | bf16}``: the cached train features are
+        ``draws`` samplings of every video (epoch e trains on draw ``e % draws``; with more than one, ``data.train`` keeps its own
+        ``phase``, so ``train`` samples as the reference's training does) stored in ``dtype``; the validation cache stays fp32, one draw.  After every epoch the trained head and the EMA head are scored on ``data.val`` with the ``inferece_val``
         metrics and kept by the rule of trainer.py:223-230 in ``{resume}/{name}_head_{test_set}_{n|s}_finetuned.pth``.
         -> (best of the trained head, best of the EMA head), each (SRCC, PLCC, KRCC, RMSE)."""
-        from .finetune import finetuner_for
+        from .finetune import feature_bank_options, finetuner_for
         cfg, opt = self.config, self.config["optimizer"]
         if opt.get("backbone_lr_mult", 0) != 0:
             raise NotImplementedError(f"optimizer.backbone_lr_mult = {opt['backbone_lr_mult']}: this engine trains the head on a frozen "
@@ -551,13 +553,15 @@ class Trainer:
             raise NotImplementedError("finetune_head() runs on one rank")
         key = self.key_list[0]
         Finetuner = finetuner_for(getattr(self.model, key + "_head", None))       # VQAHead: HeadFinetuner; simpleVQAHead: its own
+        draws, bank_dtype = feature_bank_options(cfg)
         tcfg = cfg["data"]["train"]
-        train_ds = getattr(_datasets, tcfg["type"])(dict(tcfg["args"], phase="test"), None, device=self.device)
+        targs = dict(tcfg["args"]) if draws > 1 else dict(tcfg["args"], phase="test")
+        train_ds = getattr(_datasets, tcfg["type"])(targs, None, device=self.device)
         use_ema = bool(cfg.get("ema", True))
         ft = Finetuner(self.model, key, opt["lr"], opt["wd"], 1, 1, ema=use_ema, seed=int(cfg.get("seed", 0)),
                            rank_weight=float(cfg.get("rank_weight", 0.0)))
-        ft.cache_features(train_ds, self)
-        n = sum(f.shape[0] for f in ft.feats)
+        ft.cache_features(train_ds, self, draws=draws, dtype=bank_dtype)
+        n = sum(f.shape[0] for f in ft.feats)       # the samples of one draw: an epoch is one pass over one draw
         bs = int(cfg["batch_size"])
         per_epoch = n // bs + (1 if n % bs >= 3 else 0)
         ft.set_schedule(int(cfg["warmup_epochs"] * per_epoch), int((cfg["num_epochs"] + cfg["l_num_epochs"]) * per_epoch))

@@ -5,6 +5,9 @@ yml schema, same checkpoint files and metric lines.  What trains is the head (``
 
     python train.py -o config/kwai_swin_grpb_synthetic_finetune.yml -r ./checkpoint/ --gpu_id 0
     python train.py -o config/kwai_simpleVQA_synthetic_finetune.yml -r ./checkpoint/ --gpu_id 0
+
+With the yml key ``feature_bank: {draws, dtype}`` every train video is sampled ``draws`` times in the train phase and cached in a 16-bit
+feature bank (``config/kwai_swin_grpb_synthetic_bank_finetune.yml``, ``config/kwai_simpleVQA_synthetic_bank_finetune.yml``).
 """
 import argparse
 import os
