@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KVQ_ABI_VERSION 31
+#define KVQ_ABI_VERSION 32
 #define KVQ_MAX_STAGES 4
 
 /* 16-bit MFMA operand type of every uint16_t buffer below (activations AND weights of one call must
@@ -1188,75 +1188,14 @@ int kvq_pool_nd_strided(const uint16_t* x, int dtype, const int32_t dims5[5], co
 int kvq_mean_std_pool(const uint16_t* x, int dtype, int rows, int HW, int C, float* out, int64_t out_stride,
                       int mean_off, int std_off, void* stream);
 
-/* ---- VQAHead training step on features of a frozen trunk (csrc/headtrain.hip, DESIGN.md §8): the reference's train-mode head
- * (head.py:60-68), plcc_loss / rank_loss (trainer.py:337-354), the gradients of the four head parameters, torch's AdamW and the EMA copy
- * (trainer.py:163-172).  All fp32 (fp32 MFMA, fp32 sums), no atomics: two runs are bit-equal.
- *
- *   feat     channels-last fp32 [B][L][C], dense, 16-byte aligned
- *   params   one flat fp32 vector, 16-byte aligned: W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]  (hidden * C + 2 hidden + 1
- *            floats); grads, exp_avg, exp_avg_sq and ema have the same layout
- *   p_drop   probability of both dropouts (head.py:63, :65), 0 <= p < 1.  The mask of element idx of dropout `which` (0: the features, idx
- *            in [b][l][c] order; 1: the GELU output, idx in [b][l][hidden] order) at (seed, step) is the counter-based hash of
- *            csrc/headtrain.hpp; kept values are multiplied by 1 / (1 - p); p == 0 is the identity.  No mask tensor is stored.
- *   score    forward: out [B], the train-mode scores;  dscore: backward: in [B], d loss / d score;  grads: backward: out
- *
- * Shapes: hidden == 64, C a multiple of 64, p_drop in [0, 1), 16-byte alignment: otherwise KVQ_ERR_UNSUPPORTED.  B >= 2, L >= 1,
- * B * L * C < 2^32: otherwise KVQ_ERR_SHAPE.  A workspace below kvq_headtrain_workspace_bytes(B, L, C, hidden) (0 for a shape that is
- * not built): KVQ_ERR_WORKSPACE.  NULL: KVQ_ERR_NULL.  All of it is checked on the host before the first launch.  The forward leaves the
- * pre-activations in the workspace; the backward of the same (seed, step, p_drop) reads them, so the two calls share one workspace. */
-typedef struct KvqHeadTrainArgs {
-  const float* feat;
-  int32_t B, L, C, hidden;
-  const float* params;
-  float p_drop;
-  uint32_t seed, step;
-  void* workspace;
-  size_t workspace_bytes;
-  float* score;
-  const float* dscore;
-  float* grads;
-} KvqHeadTrainArgs;
-size_t kvq_headtrain_workspace_bytes(int B, int L, int C, int hidden);
-int kvq_headtrain_forward(const KvqHeadTrainArgs* host_args, void* stream);
-int kvq_headtrain_backward(const KvqHeadTrainArgs* host_args, void* stream);
-/* out[i] = 1 if element i of dropout `which` (0 | 1) is kept at (seed, step) under probability p, else 0; 1 <= n <= 2^32 */
-int kvq_headtrain_mask(uint32_t seed, uint32_t step, int which, float p, int64_t n, uint8_t* out, void* stream);
-/* One launch: out3 = {plcc + rank_weight * rank, plcc, rank} and dscore [B] = d out3[0] / d score, the gradient through the rank loss's
- * 1 + max included.  2 <= B <= 1024 or KVQ_ERR_SHAPE.  Ties of the maximum and scores on the relu kink: deterministic, the first in
- * row-major order carries the maximum and a zero difference has zero gradient. */
-int kvq_headtrain_loss(const float* score, const float* label, int B, float rank_weight, float* out3, float* dscore, void* stream);
-/* torch.optim.AdamW (betas 0.9 / 0.999, eps 1e-8, decoupled decay p *= 1 - lr * wd on every element) on n elements, optimiser step
- * `step` >= 1 (bias corrections computed on the host in double), then ema = 0.999 ema + 0.001 params unless ema is NULL. */
-int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float wd,
-                        int step, void* stream);
-
-/* ---- simpleVQAHead training step on features of a frozen trunk (csrc/simple_headtrain.hip, DESIGN.md §8): the reference's head
- * (head.py:10-31: Linear(C -> 128), Linear(128 -> 1) per frame, mean over the frames; no activation, no dropout) and the gradients of its
- * four parameters.  The loss and the optimiser are the kvq_headtrain_loss and kvq_headtrain_adamw entries above.  All fp32, no atomics:
- * two runs are bit-equal.  The entries take KvqHeadTrainArgs with
- *
- *   feat     fp32 [B][T][C], dense, 16-byte aligned; L carries T, the frames of a video
- *   params   W1 [128][C] | b1 [128] | w2 [128] | b2 [1], 16-byte aligned; grads has the same layout and is written in full
- *   p_drop   0 (the head has no dropout); seed and step are not read
- *
- * Shapes: hidden == 128, C a multiple of 64, p_drop == 0, 16-byte alignment: otherwise KVQ_ERR_UNSUPPORTED.  2 <= B <= 1024, T >= 1,
- * B * T <= 2^24: otherwise KVQ_ERR_SHAPE.  A workspace below the workspace_bytes entry's answer (0 for a shape that is not built):
- * KVQ_ERR_WORKSPACE.  NULL: KVQ_ERR_NULL.  All of it is checked on the host before the first launch.  The backward reads feat, params
- * and dscore only: it needs no forward before it, and the two calls may share one workspace.
- * Workspace, in floats: 2 C + ceil4(B T nseg) + nchunks C, with nseg = ceil(C / 1024), chunk = max(32, ceil8(ceil(B T / 32))),
- * nchunks = ceil(B T / chunk). */
-size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int hidden);
-int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* host_args, void* stream);
-int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* host_args, void* stream);
-
 /* ---- feature bank (csrc/featbank.hip): the cached features of a frozen trunk, stored once — several train-phase draws
- * per video, in fp32, fp16 or bf16 — and read in place by the two training steps through an index vector.
+ * per video, in fp32, fp16 or bf16 — and read in place by the two training steps below through an index vector.
  *
  *   rows     [n_rows][L][C], dense, 16-byte aligned, elements of type dtype (KVQ_DT_FP32 | KVQ_DT_FP16 | KVQ_DT_BF16)
- *   L, C     a row's tokens (VQAHead: the clip's feature map; simpleVQAHead: the frames T) and channels, C a multiple of 4
+ *   L, C     a row's tokens (VQAHead: the clip's feature map, channels-last; simpleVQAHead: the frames T) and channels, C a multiple of 4
  *
- * Widening a 16-bit row to fp32 is exact, and the bank entries below run the launches of the dense entries with the rows widened in
- * registers: a bank step is bit-equal to the dense step on kvq_feature_bank_rows of the same index. */
+ * Widening a 16-bit row to fp32 is exact, and the training steps widen the rows in registers: a step on 16-bit rows is bit-equal to the
+ * step on kvq_feature_bank_rows of the same index. */
 typedef struct KvqFeatureBank {
   void* rows;
   int32_t dtype;
@@ -1274,11 +1213,30 @@ int kvq_feature_bank_store(const float* feat, int64_t n, int64_t stride_n, int64
  * [0, n_rows) on the device: a defined result, never a read outside the bank. */
 int kvq_feature_bank_rows(const KvqFeatureBank* bank, const int32_t* index, int64_t B, float* out, void* stream);
 
-/* The two training steps on bank rows: KvqHeadTrainArgs with feat replaced by (bank, index) — sample b of the batch is the bank row
- * index[b] (device pointer to B values, clamped as above), bank.L == L and bank.C == C.  The dropout masks stay indexed by the batch
- * position [b][l][c], the workspace is the one of the dense entry for (B, L, C, hidden), and every result equals the dense entry's on the
- * widened rows bit for bit.  Host checks as the dense entries, plus the bank's: NULL rows or index: KVQ_ERR_NULL; alignment (rows 16,
- * index 4 bytes) or dtype code: KVQ_ERR_UNSUPPORTED; n_rows < 1 or L, C that differ from the bank's: KVQ_ERR_SHAPE. */
+/* ---- VQAHead training step on features of a frozen trunk (csrc/headtrain.hip, DESIGN.md §8): the reference's train-mode head
+ * (head.py:60-68), plcc_loss / rank_loss (trainer.py:337-354), the gradients of the four head parameters, torch's AdamW and the EMA copy
+ * (trainer.py:163-172).  All fp32 (fp32 MFMA, fp32 sums), no atomics: two runs are bit-equal.
+ *
+ *   bank     the features, channels-last; bank.L == L and bank.C == C
+ *   index    device pointer to B int32 values, 4-byte aligned, never NULL: sample b of the batch is the bank row index[b], clamped into
+ *            [0, n_rows) on the device
+ *   params   one flat fp32 vector, 16-byte aligned: W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]  (hidden * C + 2 hidden + 1
+ *            floats); grads, exp_avg, exp_avg_sq and ema have the same layout
+ *   p_drop   probability of both dropouts (head.py:63, :65), 0 <= p < 1.  The mask of element idx of dropout `which` (0: the features, idx
+ *            in [b][l][c] order of the batch position b, not of the bank row; 1: the GELU output, idx in [b][l][hidden] order) at
+ *            (seed, step) is the counter-based hash of csrc/headtrain.hpp; kept values are multiplied by 1 / (1 - p); p == 0 is the
+ *            identity.  No mask tensor is stored.
+ *   score    forward: out [B], the train-mode scores;  dscore: backward: in [B], d loss / d score;  grads: backward: out
+ *
+ * A caller with a dense fp32 [B][L][C] tensor passes bank = {rows = tensor, dtype = KVQ_DT_FP32, L, C, n_rows = B} and, as index, the
+ * values 0 .. B-1 on the device.
+ *
+ * Shapes: hidden == 64, C a multiple of 64, p_drop in [0, 1), a dtype code of the bank, alignment (rows, params, workspace, grads 16
+ * bytes; index 4): otherwise KVQ_ERR_UNSUPPORTED.  B >= 2, L >= 1, n_rows >= 1, B * L * C < 2^32, L and C equal to the bank's: otherwise
+ * KVQ_ERR_SHAPE.  A workspace below kvq_headtrain_workspace_bytes(B, L, C, hidden) (0 for a shape that is not built):
+ * KVQ_ERR_WORKSPACE.  NULL (rows and index included): KVQ_ERR_NULL.  All of it is checked on the host before the first launch.  The
+ * forward leaves the pre-activations in the workspace; the backward of the same (seed, step, p_drop) reads them, so the two calls share
+ * one workspace. */
 typedef struct KvqHeadTrainBankArgs {
   KvqFeatureBank bank;
   const int32_t* index;
@@ -1292,8 +1250,37 @@ typedef struct KvqHeadTrainBankArgs {
   const float* dscore;
   float* grads;
 } KvqHeadTrainBankArgs;
+size_t kvq_headtrain_workspace_bytes(int B, int L, int C, int hidden);
 int kvq_headtrain_bank_forward(const KvqHeadTrainBankArgs* host_args, void* stream);
 int kvq_headtrain_bank_backward(const KvqHeadTrainBankArgs* host_args, void* stream);
+/* out[i] = 1 if element i of dropout `which` (0 | 1) is kept at (seed, step) under probability p, else 0; 1 <= n <= 2^32 */
+int kvq_headtrain_mask(uint32_t seed, uint32_t step, int which, float p, int64_t n, uint8_t* out, void* stream);
+/* One launch: out3 = {plcc + rank_weight * rank, plcc, rank} and dscore [B] = d out3[0] / d score, the gradient through the rank loss's
+ * 1 + max included.  2 <= B <= 1024 or KVQ_ERR_SHAPE.  Ties of the maximum and scores on the relu kink: deterministic, the first in
+ * row-major order carries the maximum and a zero difference has zero gradient. */
+int kvq_headtrain_loss(const float* score, const float* label, int B, float rank_weight, float* out3, float* dscore, void* stream);
+/* torch.optim.AdamW (betas 0.9 / 0.999, eps 1e-8, decoupled decay p *= 1 - lr * wd on every element) on n elements, optimiser step
+ * `step` >= 1 (bias corrections computed on the host in double), then ema = 0.999 ema + 0.001 params unless ema is NULL. */
+int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float wd,
+                        int step, void* stream);
+
+/* ---- simpleVQAHead training step on features of a frozen trunk (csrc/simple_headtrain.hip, DESIGN.md §8): the reference's head
+ * (head.py:10-31: Linear(C -> 128), Linear(128 -> 1) per frame, mean over the frames; no activation, no dropout) and the gradients of its
+ * four parameters.  The loss and the optimiser are the kvq_headtrain_loss and kvq_headtrain_adamw entries above.  All fp32, no atomics:
+ * two runs are bit-equal.  The entries take KvqHeadTrainBankArgs as the VQAHead step does (a dense fp32 [B][T][C] tensor likewise), with
+ *
+ *   bank     rows of [T][C]; L carries T, the frames of a video
+ *   params   W1 [128][C] | b1 [128] | w2 [128] | b2 [1], 16-byte aligned; grads has the same layout and is written in full
+ *   p_drop   0 (the head has no dropout); seed and step are not read
+ *
+ * Shapes: hidden == 128, C a multiple of 64, p_drop == 0, the bank's dtype code and the alignments of the VQAHead step: otherwise
+ * KVQ_ERR_UNSUPPORTED.  2 <= B <= 1024, T >= 1, B * T <= 2^24, and the bank's shape checks of the VQAHead step: otherwise KVQ_ERR_SHAPE.
+ * A workspace below the workspace_bytes entry's answer (0 for a shape that is not built): KVQ_ERR_WORKSPACE.  NULL: KVQ_ERR_NULL.  All
+ * of it is checked on the host before the first launch.  The backward reads the rows, params and dscore only: it needs no forward before
+ * it, and the two calls may share one workspace.
+ * Workspace, in floats: 2 C + ceil4(B T nseg) + nchunks C, with nseg = ceil(C / 1024), chunk = max(32, ceil8(ceil(B T / 32))),
+ * nchunks = ceil(B T / chunk). */
+size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int hidden);
 int kvq_simple_headtrain_bank_forward(const KvqHeadTrainBankArgs* host_args, void* stream);
 int kvq_simple_headtrain_bank_backward(const KvqHeadTrainBankArgs* host_args, void* stream);
 

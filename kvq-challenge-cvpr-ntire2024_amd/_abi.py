@@ -19,7 +19,7 @@ K_COUNT = len(K_NAMES)
 
 EPI_BIAS_BF16, EPI_GELU_BF16, EPI_QKV_BF16, EPI_RESID_F32, EPI_STORE_F32, EPI_RELU_BF16, EPI_QGELU_BF16, EPI_RESID_SCALE_F32 = range(8)
 DT_BF16, DT_FP16 = 0, 1
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 def dtype_code(dt) -> int:
@@ -205,12 +205,6 @@ class KvqJpegTables(C.Structure):
 JPEG_TABLES_BYTES = C.sizeof(KvqJpegTables)      # 8196: one table set of kvq_jpeg_index / kvq_jpeg_entropy
 
 
-class KvqHeadTrainArgs(C.Structure):
-    _fields_ = [("feat", p_void), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32), ("params", p_void),
-                ("p_drop", C.c_float), ("seed", C.c_uint32), ("step", C.c_uint32), ("workspace", p_void), ("workspace_bytes", C.c_size_t),
-                ("score", p_void), ("dscore", p_void), ("grads", p_void)]
-
-
 class KvqFeatureBank(C.Structure):
     _fields_ = [("rows", p_void), ("dtype", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("n_rows", C.c_int64)]
 
@@ -393,14 +387,10 @@ SYMBOLS = {
     "kvq_fragment_gather": (i32, [p_void, i32, i32, i32, i32, i32, p_void, p_void, i32, i32, i32, i32, i32,
                                   C.POINTER(f32), C.POINTER(f32), p_void, p_void]),
     "kvq_headtrain_workspace_bytes": (sz, [i32] * 4),
-    "kvq_headtrain_forward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
-    "kvq_headtrain_backward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
     "kvq_headtrain_mask": (i32, [C.c_uint32, C.c_uint32, i32, f32, i64, p_void, p_void]),
     "kvq_headtrain_loss": (i32, [p_void, p_void, i32, f32, p_void, p_void, p_void]),
     "kvq_headtrain_adamw": (i32, [p_void, p_void, p_void, p_void, p_void, i64, f32, f32, i32, p_void]),
     "kvq_simple_headtrain_workspace_bytes": (sz, [i32] * 4),
-    "kvq_simple_headtrain_forward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
-    "kvq_simple_headtrain_backward": (i32, [C.POINTER(KvqHeadTrainArgs), p_void]),
     "kvq_feature_bank_store": (i32, [p_void, i64, i64, i64, C.POINTER(KvqFeatureBank), i64, p_void, p_void]),
     "kvq_feature_bank_rows": (i32, [C.POINTER(KvqFeatureBank), p_void, i64, p_void, p_void]),
     "kvq_headtrain_bank_forward": (i32, [C.POINTER(KvqHeadTrainBankArgs), p_void]),

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void feature_bank_rows_kernel(const E* __restr
   const int c = (int)(q - tok * cq) * 4;
   const long b = tok / L;
   const long l = tok - b * L;
-  const size_t src = ((size_t)bank_row<true>(index, n_rows, b) * L + l) * C + c;
+  const size_t src = ((size_t)bank_row(index, n_rows, b) * L + l) * C + c;
   *reinterpret_cast<f32x4*>(out + (size_t)tok * C + c) = bank_load4(rows + src);
 }
 
@@ -73,6 +73,8 @@ int headtrain_bank_check(const KvqHeadTrainBankArgs* a, const char* who) {
   KVQ_REQUIRE(a && a->index, KVQ_ERR_NULL, "%s: NULL pointer", who);
   if (int rc = bank_check(&a->bank, who)) return rc;
   KVQ_REQUIRE(((uintptr_t)a->index & 3) == 0, KVQ_ERR_UNSUPPORTED, "%s: index must be 4-byte aligned", who);
+  // a step's L (simpleVQAHead: T) below 1 cannot be the bank's, which is at least 1: refused by its own name, with the mismatch's status
+  KVQ_REQUIRE(a->L >= 1, KVQ_ERR_SHAPE, "%s: the step's L | T %d below 1", who, a->L);
   KVQ_REQUIRE(a->bank.L == a->L && a->bank.C == a->C, KVQ_ERR_SHAPE, "%s: the bank's rows are (L %d, C %d), the step's (L %d, C %d)", who,
               a->bank.L, a->bank.C, a->L, a->C);
   KVQ_REQUIRE((double)a->B * a->L * a->C < 4294967296.0, KVQ_ERR_SHAPE, "%s: B*L*C = %g elements exceed the 32-bit batch position", who,

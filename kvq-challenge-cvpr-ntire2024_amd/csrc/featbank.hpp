@@ -1,8 +1,6 @@
 // What csrc/featbank.hip, csrc/headtrain.hip and csrc/simple_headtrain.hip share: the element types of a feature bank, the widening
-// quad load, the index clamp, and the one argument form behind the dense and the bank entries of the two training steps.
+// quad load, the index clamp, the workgroup sum, and the host checks of a step's bank.
 #pragma once
-#include <type_traits>
-
 #include "common.hpp"
 
 namespace kvq {
@@ -22,16 +20,26 @@ __device__ __forceinline__ f32x4 bank_load4(const __bf16* p) {
                  __uint_as_float(v[1] & 0xffff0000u)};
 }
 
-// The bank row of batch position b.  IDX = false: the dense entries, row b.  IDX = true: index[b] clamped into [0, n_rows), so that no
-// index value can cause a read outside the bank.
-template <bool IDX>
+// The bank row of batch position b: index[b] clamped into [0, n_rows), so that no index value can cause a read outside the bank.
 __device__ __forceinline__ long bank_row(const int32_t* __restrict__ index, long n_rows, long b) {
-  if constexpr (!IDX) {
-    return b;
-  } else {
-    const long r = index[b];
-    return r < 0 ? 0 : (r < n_rows ? r : n_rows - 1);
-  }
+  const long r = index[b];
+  return r < 0 ? 0 : (r < n_rows ? r : n_rows - 1);
+}
+
+// ---- sums the two training steps share
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// Workgroup-wide sum of one float per thread (256 threads), the same value in every thread: wave butterflies, then the four wave sums
+// in a fixed order.  wsum: 4 floats of LDS, reusable after the call returns in every thread.
+__device__ __forceinline__ float block_sum(float v, float* wsum) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
 static inline bool bank_dtype_ok(int dtype) { return dtype == KVQ_DT_FP32 || dtype == KVQ_DT_FP16 || dtype == KVQ_DT_BF16; }
@@ -45,45 +53,18 @@ int with_bank_elem(int dtype, F&& f) {
   return dtype == KVQ_DT_FP16 ? f(_Float16{}) : f(__bf16{});
 }
 
-// ---- the features of one training step as its launches see them: dense fp32 [B][L][C] (index == NULL: KvqHeadTrainArgs), or B rows of a
-// bank picked by a device index (KvqHeadTrainBankArgs)
-struct HeadTrainFeat {
-  const void* rows;
-  int dtype;
-  const int32_t* index;
-  long n_rows;
-};
-struct HeadTrainCall {
-  HeadTrainFeat feat;
-  int B, L, C, hidden;
-  const float* params;
-  float p_drop;
-  uint32_t seed, step;
-  void* workspace;
-  size_t workspace_bytes;
-  float* score;
-  const float* dscore;
-  float* grads;
-};
-
-inline HeadTrainCall headtrain_call(const KvqHeadTrainArgs* a) {
-  return {{a->feat, KVQ_DT_FP32, nullptr, a->B}, a->B, a->L, a->C, a->hidden, a->params, a->p_drop, a->seed, a->step, a->workspace,
-          a->workspace_bytes, a->score, a->dscore, a->grads};
-}
-inline HeadTrainCall headtrain_call(const KvqHeadTrainBankArgs* a) {
-  return {{a->bank.rows, a->bank.dtype, a->index, (long)a->bank.n_rows}, a->B, a->L, a->C, a->hidden, a->params, a->p_drop, a->seed,
-          a->step, a->workspace, a->workspace_bytes, a->score, a->dscore, a->grads};
-}
-
-// The host checks a bank entry makes before the checks it shares with its dense entry (which then see the bank's rows as `feat`).
+// ---- what the two training steps share on the host
+// The checks of a step's bank and index, made before the head's own: NULL args, rows or index; the bank's dtype, alignment and shape; the
+// index's alignment; (L, C) of the bank against the step's; the 32-bit batch position.
 int headtrain_bank_check(const KvqHeadTrainBankArgs* a, const char* who);
 
-// f(elem, std::true_type / std::false_type) for the element type and for whether the call has an index; the dense entries are
-// (float, false)
-template <class F>
-int with_headtrain_feat(const HeadTrainFeat& ft, F&& f) {
-  if (!ft.index) return f(float{}, std::false_type{});
-  return with_bank_elem(ft.dtype, [&](auto e) { return f(e, std::true_type{}); });
+// The flat parameter (or gradient) vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]
+struct HeadParams {
+  const float *w1, *b1, *w2, *b2;
+};
+inline HeadParams head_params(const float* flat, int hidden, int C) {
+  const float* b1 = flat + (size_t)hidden * C;
+  return {flat, b1, b1 + hidden, b1 + 2 * hidden};
 }
 
 }  // namespace kvq

@@ -1,10 +1,9 @@
 // One optimisation step of VQAHead on features of a frozen trunk (gfx950): the reference's train-mode head (head.py:60-68), its losses
 // (trainer.py:337-354), the gradients of the four head parameters and torch's AdamW with the EMA copy (trainer.py:163-172).
 //
-//   features  fp32 channels-last [B][L][C], C % 64 == 0, hidden == 64, one class, no pre-pool, B >= 2; or (the bank entries) B rows of a
-//             feature bank [n_rows][L][C] in fp32, fp16 or bf16, picked by a device index and widened to fp32 in registers
-//             (featbank.hpp): the two launches that read features are templates over the element type and over whether an index is
-//             given, the dense entries are their (float, no index) form
+//   features  B rows of a feature bank [n_rows][L][C], channels-last, in fp32, fp16 or bf16, picked by a device index and widened to
+//             fp32 in registers (featbank.hpp): the two launches that read features are templates over the element type.  C % 64 == 0,
+//             hidden == 64, one class, no pre-pool, B >= 2.  A dense fp32 batch is an fp32 bank of B rows with the index 0 .. B-1
 //   params    one flat fp32 vector: W1 [64][C] | b1 [64] | w2 [64] | b2 [1]; the gradients and the AdamW state have the same layout
 //   score[b]  = mean_l( w2 . (m2 * gelu(W1 (m1 * f) + b1)) ) + b2,   m1, m2 the scaled dropout masks of headtrain.hpp
 //
@@ -29,25 +28,14 @@ namespace kvq {
 
 constexpr int HT_HID = 64;
 
-// Workgroup-wide sum of one float per thread (256 threads), the same value in every thread: wave butterflies, then the four wave sums
-// in a fixed order.  wsum: 4 floats of LDS, reusable after the call returns in every thread.
-__device__ __forceinline__ float ht_block_sum(float v, float* wsum) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
 __global__ __launch_bounds__(256) void headtrain_mask_kernel(uint32_t key, uint32_t thr, long n, uint8_t* __restrict__ out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = ht_bits(key, (uint32_t)i) >= thr ? 1 : 0;
 }
 
 // grid ceil(B*L / 16), 256 threads.  vqa_head_mfma_kernel with the two masks and the pre-activations kept.  Token tk = (b, l) reads
-// row bank_row(b) of feat (IDX = false: row b, the dense batch); the masks are indexed by the batch position tk either way.
-template <typename E, bool IDX>
+// row bank_row(b) of feat; the masks are indexed by the batch position tk.
+template <typename E>
 __global__ __launch_bounds__(256) void headtrain_fwd_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
                                                             int L, long total, int C, const float* __restrict__ w1,
                                                             const float* __restrict__ b1, const float* __restrict__ w2, uint32_t key1,
@@ -59,11 +47,8 @@ __global__ __launch_bounds__(256) void headtrain_fwd_kernel(const E* __restrict_
   const int tok = lane & 15, kq = lane >> 4;
   const long tk = min((long)blockIdx.x * 16 + tok, total - 1);
   const int cw = C / 4, c0 = wave * cw;
-  long tsrc = tk;                                                // the token's place in feat, in tokens
-  if constexpr (IDX) {
-    const long b = tk / L;
-    tsrc = bank_row<IDX>(index, n_rows, b) * L + (tk - b * L);
-  }
+  const long b = tk / L;
+  const long tsrc = bank_row(index, n_rows, b) * L + (tk - b * L);   // the token's place in feat, in tokens
   const E* xr = feat + (size_t)tsrc * C + c0 + 4 * kq;
   const uint32_t e0 = (uint32_t)((size_t)tk * C) + (uint32_t)(c0 + 4 * kq);      // element index of xr[0]
   const float* wr = w1 + (size_t)tok * C + c0 + 4 * kq;          // + 16 hb rows
@@ -126,7 +111,7 @@ __global__ __launch_bounds__(256) void headtrain_score_kernel(const float* __res
   const int b = blockIdx.x;
   float s = 0.f;
   for (int l = threadIdx.x; l < L; l += 256) s += tok[(size_t)b * L + l];
-  const float t = ht_block_sum(s, wsum);
+  const float t = block_sum(s, wsum);
   if (threadIdx.x == 0) score[b] = t / (float)L + b2[0];
 }
 
@@ -156,8 +141,8 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
       sy[i] = y[k];
     }
   }
-  const float mp = ht_block_sum((p[0] + p[1]) + (p[2] + p[3]), wsum) / n;
-  const float my = ht_block_sum((y[0] + y[1]) + (y[2] + y[3]), wsum) / n;
+  const float mp = block_sum((p[0] + p[1]) + (p[2] + p[3]), wsum) / n;
+  const float my = block_sum((y[0] + y[1]) + (y[2] + y[3]), wsum) / n;
   float dp[4], dy[4], qp = 0.f, qy = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -167,7 +152,7 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
     qp = fmaf(dp[k], dp[k], qp);
     qy = fmaf(dy[k], dy[k], qy);
   }
-  const float sdp = sqrtf(ht_block_sum(qp, wsum) / n), sdy = sqrtf(ht_block_sum(qy, wsum) / n);
+  const float sdp = sqrtf(block_sum(qp, wsum) / n), sdy = sqrtf(block_sum(qy, wsum) / n);
   const float ip = 1.0f / (sdp + 1e-8f), iy = 1.0f / (sdy + 1e-8f);
   float a[4], t[4], s_at = 0.f, s0 = 0.f;
 #pragma unroll
@@ -177,8 +162,8 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
     s_at = fmaf(a[k], t[k], s_at);
     s0 = fmaf(a[k] - t[k], a[k] - t[k], s0);
   }
-  const float rho = ht_block_sum(s_at, wsum) / n;
-  const float loss0 = ht_block_sum(s0, wsum) / n * 0.25f;
+  const float rho = block_sum(s_at, wsum) / n;
+  const float loss0 = block_sum(s0, wsum) / n * 0.25f;
   float s1 = 0.f, sS = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -186,8 +171,8 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
     s1 = fmaf(e, e, s1);
     sS = fmaf(e, a[k], sS);
   }
-  const float loss1 = ht_block_sum(s1, wsum) / n * 0.25f;
-  const float S = ht_block_sum(sS, wsum);
+  const float loss1 = block_sum(s1, wsum) / n * 0.25f;
+  const float S = block_sum(sS, wsum);
   const float plcc = (loss0 + loss1) * 0.5f;
   // d plcc / d a, then through a = (p - mean) / (std + eps)
   float ga[4], sgd = 0.f;
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
     ga[k] = in ? ((a[k] - t[k]) + fmaf(rho, e, S * t[k] / n)) / (4.0f * n) : 0.f;
     sgd = fmaf(ga[k], dp[k], sgd);
   }
-  const float G = ht_block_sum(sgd, wsum);
+  const float G = block_sum(sgd, wsum);
   const float cstd = sdp > 0.f ? G * ip * ip / (n * sdp) : 0.f;
   // the gradient to d = p - mean (through the quotient and through the std), centred LAST as autograd does for the mean: the loss does not
   // move when every score moves by the same amount, and the centring keeps sum_b dscore = db2 at the rounding of this one subtraction
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
     gpl[k] = tid + 256 * k < B ? fmaf(-dp[k], cstd, ga[k] * ip) : 0.f;
     sgp += gpl[k];
   }
-  const float mgp = ht_block_sum(sgp, wsum) / n;
+  const float mgp = block_sum(sgp, wsum) / n;
 #pragma unroll
   for (int k = 0; k < 4; ++k) gpl[k] -= mgp;
 
@@ -237,7 +222,7 @@ __global__ __launch_bounds__(256) void headtrain_loss_kernel(const float* __rest
       rsum += rs;
     }
   }
-  const float Rsum = ht_block_sum(rsum, wsum);
+  const float Rsum = block_sum(rsum, wsum);
   mval[tid] = best;
   midx[tid] = besti;
   __syncthreads();
@@ -346,7 +331,7 @@ __global__ __launch_bounds__(1024) void headtrain_bwd_sum_small_kernel(const flo
 // hold four consecutive channels again.  The four waves take the k-steps in turn (wave w: steps w, w + 4, ...) and meet in LDS, added as
 // (w0 + w1) + (w2 + w3); wave w then stores the hidden units 16 w .. 16 w + 15.
 // Token t = (b, l) reads row bank_row(b) of feat, as in the forward; dz and the mask are indexed by t.
-template <typename E, bool IDX>
+template <typename E>
 __global__ __launch_bounds__(256) void headtrain_bwd_w1_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
                                                                int L, const float* __restrict__ dz, long total, int C, int chunk,
                                                                uint32_t key1, uint32_t thr, float scale, float* __restrict__ part) {
@@ -373,11 +358,8 @@ __global__ __launch_bounds__(256) void headtrain_bwd_w1_kernel(const E* __restri
     const long t = ts + kq;
     o.in = t < t1;
     const long tc = o.in ? t : t1 - 1;
-    long tsrc = tc;
-    if constexpr (IDX) {
-      const long b = tc / L;
-      tsrc = bank_row<IDX>(index, n_rows, b) * L + (tc - b * L);
-    }
+    const long b = tc / L;
+    const long tsrc = bank_row(index, n_rows, b) * L + (tc - b * L);
     o.x = bank_load4(feat + (size_t)tsrc * C + c0 + 4 * j);
     o.e0 = (uint32_t)((size_t)tc * C) + (uint32_t)(c0 + 4 * j);
 #pragma unroll
@@ -483,15 +465,15 @@ __global__ __launch_bounds__(256) void headtrain_adamw_kernel(float* __restrict_
   if (ema) ema[i] = fmaf(0.001f, pi, ema[i] * 0.999f);
 }
 
-static int headtrain_check(const HeadTrainCall* a, const char* who, HeadTrainPlan* plan) {
-  KVQ_REQUIRE(a->feat.rows && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
+// Every host check of a step but those of its outputs.  The bank part has refused misaligned rows and B * L * C past the 32-bit mask index.
+static int headtrain_check(const KvqHeadTrainBankArgs* a, const char* who, HeadTrainPlan* plan) {
+  if (int rc = headtrain_bank_check(a, who)) return rc;
+  KVQ_REQUIRE(a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
   KVQ_REQUIRE(a->hidden == HT_HID, KVQ_ERR_UNSUPPORTED, "%s: hidden %d (64 is built)", who, a->hidden);
   KVQ_REQUIRE(a->C >= 64 && a->C % 64 == 0, KVQ_ERR_UNSUPPORTED, "%s: C %d is not a multiple of 64", who, a->C);
   KVQ_REQUIRE(a->p_drop >= 0.f && a->p_drop < 1.f, KVQ_ERR_UNSUPPORTED, "%s: dropout probability %g outside [0, 1)", who, (double)a->p_drop);
   KVQ_REQUIRE(a->B >= 2 && a->L >= 1, KVQ_ERR_SHAPE, "%s: B %d (at least 2 clips: the loss of one is constant), L %d", who, a->B, a->L);
-  KVQ_REQUIRE((double)a->B * a->L * a->C < 4294967296.0, KVQ_ERR_SHAPE, "%s: B*L*C = %g elements exceed the 32-bit mask index", who,
-              (double)a->B * a->L * a->C);
-  KVQ_REQUIRE((((uintptr_t)a->feat.rows | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
+  KVQ_REQUIRE((((uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
               "%s: feat, params and workspace must be 16-byte aligned", who);
   *plan = headtrain_plan(a->B, a->L, a->C, a->hidden);
   KVQ_REQUIRE(a->workspace_bytes >= plan->total * sizeof(float), KVQ_ERR_WORKSPACE, "%s: workspace %zu bytes, %zu needed", who,
@@ -517,32 +499,30 @@ extern "C" int kvq_headtrain_mask(uint32_t seed, uint32_t step, int which, float
 
 namespace kvq {
 
-static int headtrain_forward_call(const HeadTrainCall* a, const char* who, void* stream) {
+static int headtrain_forward_call(const KvqHeadTrainBankArgs* a, const char* who, void* stream) {
   HeadTrainPlan pl;
   if (int rc = headtrain_check(a, who, &pl)) return rc;
   KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "%s: NULL pointer", who);
   float* ws = static_cast<float*>(a->workspace);
-  const float* w1 = a->params;
-  const float* b1 = w1 + (size_t)HT_HID * a->C;
-  const float* w2 = b1 + HT_HID;
-  const float* b2 = w2 + HT_HID;
+  const HeadParams p = head_params(a->params, HT_HID, a->C);
   const uint32_t thr = ht_threshold(a->p_drop);
-  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+  if (int rc = with_bank_elem(a->bank.dtype, [&](auto e) {
         using E = decltype(e);
-        return launch("headtrain_fwd_kernel", headtrain_fwd_kernel<E, decltype(idx)::value>, grid_1d(pl.T, 16), dim3(256), 0, stream,
-                      static_cast<const E*>(a->feat.rows), a->feat.index, a->feat.n_rows, a->L, pl.T, a->C, w1, b1, w2,
+        return launch("headtrain_fwd_kernel", headtrain_fwd_kernel<E>, grid_1d(pl.T, 16), dim3(256), 0, stream,
+                      static_cast<const E*>(a->bank.rows), a->index, (long)a->bank.n_rows, a->L, pl.T, a->C, p.w1, p.b1, p.w2,
                       ht_key(a->seed, a->step, 0), ht_key(a->seed, a->step, 1), thr, ht_scale(a->p_drop), ws + pl.z, ws + pl.tok);
       }))
     return rc;
-  return launch("headtrain_score_kernel", headtrain_score_kernel, dim3((unsigned)a->B), dim3(256), 0, stream, ws + pl.tok, a->L, b2, a->score);
+  return launch("headtrain_score_kernel", headtrain_score_kernel, dim3((unsigned)a->B), dim3(256), 0, stream, ws + pl.tok, a->L, p.b2,
+                a->score);
 }
 
-static int headtrain_backward_call(const HeadTrainCall* a, const char* who, void* stream) {
+static int headtrain_backward_call(const KvqHeadTrainBankArgs* a, const char* who, void* stream) {
   HeadTrainPlan pl;
   if (int rc = headtrain_check(a, who, &pl)) return rc;
   KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "%s: NULL pointer", who);
   float* ws = static_cast<float*>(a->workspace);
-  const float* w2 = a->params + (size_t)HT_HID * a->C + HT_HID;
+  const float* w2 = head_params(a->params, HT_HID, a->C).w2;
   const uint32_t thr = ht_threshold(a->p_drop);
   const float scale = ht_scale(a->p_drop);
   KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "%s: grads must be 16-byte aligned", who);
@@ -554,12 +534,11 @@ static int headtrain_backward_call(const HeadTrainCall* a, const char* who, void
   if (int rc = launch("headtrain_bwd_sum_small_kernel", headtrain_bwd_sum_small_kernel, dim3(1), dim3(1024), 0, stream, ws + pl.part_b1,
                       ws + pl.part_w2, pl.nsub, a->grads + nw1))
     return rc;
-  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+  if (int rc = with_bank_elem(a->bank.dtype, [&](auto e) {
         using E = decltype(e);
-        return launch("headtrain_bwd_w1_kernel", headtrain_bwd_w1_kernel<E, decltype(idx)::value>,
-                      dim3((unsigned)(a->C / 64), (unsigned)pl.nchunks), dim3(256), 0, stream, static_cast<const E*>(a->feat.rows),
-                      a->feat.index, a->feat.n_rows, a->L, ws + pl.dz, pl.T, a->C, pl.chunk, ht_key(a->seed, a->step, 0), thr, scale,
-                      ws + pl.part_w1);
+        return launch("headtrain_bwd_w1_kernel", headtrain_bwd_w1_kernel<E>, dim3((unsigned)(a->C / 64), (unsigned)pl.nchunks), dim3(256), 0,
+                      stream, static_cast<const E*>(a->bank.rows), a->index, (long)a->bank.n_rows, a->L, ws + pl.dz, pl.T, a->C, pl.chunk,
+                      ht_key(a->seed, a->step, 0), thr, scale, ws + pl.part_w1);
       }))
     return rc;
   const long quads = (long)nw1 / 4;
@@ -569,18 +548,8 @@ static int headtrain_backward_call(const HeadTrainCall* a, const char* who, void
 
 }  // namespace kvq
 
-extern "C" int kvq_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
-  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_headtrain_forward: NULL pointer");
-  const HeadTrainCall c = headtrain_call(a);
-  return headtrain_forward_call(&c, "kvq_headtrain_forward", stream);
-}
-
 extern "C" int kvq_headtrain_bank_forward(const KvqHeadTrainBankArgs* a, void* stream) {
-  using namespace kvq;
-  if (int rc = headtrain_bank_check(a, "kvq_headtrain_bank_forward")) return rc;
-  const HeadTrainCall c = headtrain_call(a);
-  return headtrain_forward_call(&c, "kvq_headtrain_bank_forward", stream);
+  return kvq::headtrain_forward_call(a, "kvq_headtrain_bank_forward", stream);
 }
 
 extern "C" int kvq_headtrain_loss(const float* score, const float* label, int B, float rank_weight, float* out3, float* dscore,
@@ -591,18 +560,8 @@ extern "C" int kvq_headtrain_loss(const float* score, const float* label, int B,
   return launch("headtrain_loss_kernel", headtrain_loss_kernel, dim3(1), dim3(256), 0, stream, score, label, B, rank_weight, out3, dscore);
 }
 
-extern "C" int kvq_headtrain_backward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
-  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_headtrain_backward: NULL pointer");
-  const HeadTrainCall c = headtrain_call(a);
-  return headtrain_backward_call(&c, "kvq_headtrain_backward", stream);
-}
-
 extern "C" int kvq_headtrain_bank_backward(const KvqHeadTrainBankArgs* a, void* stream) {
-  using namespace kvq;
-  if (int rc = headtrain_bank_check(a, "kvq_headtrain_bank_backward")) return rc;
-  const HeadTrainCall c = headtrain_call(a);
-  return headtrain_backward_call(&c, "kvq_headtrain_bank_backward", stream);
+  return kvq::headtrain_backward_call(a, "kvq_headtrain_bank_backward", stream);
 }
 
 extern "C" int kvq_headtrain_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,

@@ -2,10 +2,9 @@
 // Linear(128 -> 1) per frame, no activation, no dropout, then the mean over the frames), the gradients of its four parameters; the losses
 // and AdamW + EMA are the launches of headtrain.hip, unchanged.
 //
-//   features  fp32 [B][T][C], C % 64 == 0, hidden == 128, 2 <= B <= 1024; or (the bank entries) B rows of a feature bank [n_rows][T][C] in
-//             fp32, fp16 or bf16, picked by a device index and widened to fp32 in registers (featbank.hpp): simple_fwd_rows and
-//             simple_bwd_g are templates over the element type and over whether an index is given, the dense entries their
-//             (float, no index) form
+//   features  B rows of a feature bank [n_rows][T][C] in fp32, fp16 or bf16, picked by a device index and widened to fp32 in registers
+//             (featbank.hpp): simple_fwd_rows and simple_bwd_g are templates over the element type.  C % 64 == 0, hidden == 128,
+//             2 <= B <= 1024.  A dense fp32 batch is an fp32 bank of B rows with the index 0 .. B-1
 //   params    one flat fp32 vector: W1 [128][C] | b1 [128] | w2 [128] | b2 [1]; the gradients and the AdamW state have the same layout
 //
 // The head is linear, so both directions collapse:
@@ -39,20 +38,6 @@ __device__ __forceinline__ f32x4 sh_fma4(float a, f32x4 x, f32x4 acc) {
 __device__ __forceinline__ f32x4 sh_fma4(f32x4 a, f32x4 x, f32x4 acc) {
   return (f32x4){fmaf(a[0], x[0], acc[0]), fmaf(a[1], x[1], acc[1]), fmaf(a[2], x[2], acc[2]), fmaf(a[3], x[3], acc[3])};
 }
-__device__ __forceinline__ float sh_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// Workgroup-wide sum of one float per thread (256 threads), the same value in every thread: wave butterflies, then the four wave sums
-// in a fixed order.  wsum: 4 floats of LDS, reusable after the call returns in every thread.
-__device__ __forceinline__ float sh_block_sum(float v, float* wsum) {
-  v = sh_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
 
 // grid C / 64, 256 threads: thread = (channel quad tid & 15, row group tid >> 4).  u[c] = sum_j w2[j] W1[j][c]: a thread adds its rows
 // 8 jg .. 8 jg + 7 in ascending order (eight 16-byte loads in flight), the sixteen groups meet in LDS in a balanced tree.
@@ -83,8 +68,8 @@ __global__ __launch_bounds__(256) void simple_fwd_u_kernel(const float* __restri
 
 // grid ceil(N * nseg / 4), 256 threads: wave = one (row n, segment sg) of the [N][nseg] partials.  A lane multiplies up to four channel
 // quads (c = 1024 sg + 256 k + 4 lane) into four running sums, adds them as (0 + 1) + (2 + 3); the lanes meet in a butterfly.
-// Row n = (b, t) reads row bank_row(b) of feat (IDX = false: row b, the dense batch).
-template <typename E, bool IDX>
+// Row n = (b, t) reads row bank_row(b) of feat.
+template <typename E>
 __global__ __launch_bounds__(256) void simple_fwd_rows_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
                                                               int T, const float* __restrict__ u, long N, int C, int nseg,
                                                               float* __restrict__ part) {
@@ -93,11 +78,8 @@ __global__ __launch_bounds__(256) void simple_fwd_rows_kernel(const E* __restric
   if (item >= N * nseg) return;                                   // a whole wave; no barrier follows
   const long n = item / nseg;
   const int sg = (int)(item % nseg);
-  long nsrc = n;
-  if constexpr (IDX) {
-    const long b = n / T;
-    nsrc = bank_row<IDX>(index, n_rows, b) * T + (n - b * T);
-  }
+  const long b = n / T;
+  const long nsrc = bank_row(index, n_rows, b) * T + (n - b * T);
   const E* xr = feat + (size_t)nsrc * C;
   f32x4 x[4], w[4];
 #pragma unroll
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(256) void simple_fwd_rows_kernel(const E* __restric
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) acc = sh_fma4(x[k], w[k], acc);
-  const float s = sh_wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  const float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
   if (lane == 0) part[item] = s;
 }
 
@@ -124,8 +106,8 @@ __global__ __launch_bounds__(64) void simple_fwd_score_kernel(const float* __res
   const float* src = part + (size_t)blockIdx.x * per;
   float s = 0.f;
   for (int i = lane; i < per; i += 64) s += src[i];
-  s = sh_wave_sum(s);
-  const float c0 = sh_wave_sum(fmaf(w2[lane], b1[lane], w2[lane + 64] * b1[lane + 64]));
+  s = wave_sum(s);
+  const float c0 = wave_sum(fmaf(w2[lane], b1[lane], w2[lane + 64] * b1[lane + 64]));
   if (lane == 0) score[blockIdx.x] = s / (float)T + (c0 + b2[0]);
 }
 
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(64) void simple_fwd_score_kernel(const float* __res
 // g[c] = sum_n dscore[n / T] / T * X[n][c]: a thread adds its rows r0 + ph, r0 + ph + 8, ... in ascending order, the eight phases meet in
 // LDS as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).
 // Row r = (b, t) reads row bank_row(b) of feat, as in the forward.
-template <typename E, bool IDX>
+template <typename E>
 __global__ __launch_bounds__(256) void simple_bwd_g_kernel(const E* __restrict__ feat, const int32_t* __restrict__ index, long n_rows,
                                                            const float* __restrict__ dscore, long N, int T, int C, int chunk,
                                                            float* __restrict__ gpart) {
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(256) void simple_bwd_g_kernel(const E* __restrict__
     for (long r = r0 + ph; r < r1; r += 8) {
       const long b = r / T;
       const float d = dscore[b] / (float)T;
-      const long rsrc = IDX ? bank_row<IDX>(index, n_rows, b) * T + (r - b * T) : r;
+      const long rsrc = bank_row(index, n_rows, b) * T + (r - b * T);
       acc = sh_fma4(d, bank_load4(feat + (size_t)rsrc * C + c), acc);
     }
   }
@@ -203,13 +185,13 @@ __global__ __launch_bounds__(256) void simple_bwd_small_kernel(const float* __re
   float d[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) d[k] = tid + 256 * k < B ? dscore[tid + 256 * k] : 0.f;
-  const float S = sh_block_sum((d[0] + d[1]) + (d[2] + d[3]), wsum);
+  const float S = block_sum((d[0] + d[1]) + (d[2] + d[3]), wsum);
   const float* wr = w1 + (size_t)j * C;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
   for (int c = 4 * tid; c < C; c += 1024)
     acc = sh_fma4(*reinterpret_cast<const f32x4*>(wr + c), *reinterpret_cast<const f32x4*>(g + c), acc);
-  const float dot = sh_block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), wsum);
+  const float dot = block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), wsum);
   if (tid == 0) {
     out[j] = w2[j] * S;
     out[SH_HID + j] = fmaf(b1[j], S, dot);
@@ -217,14 +199,16 @@ __global__ __launch_bounds__(256) void simple_bwd_small_kernel(const float* __re
   }
 }
 
-static int simple_headtrain_check(const HeadTrainCall* a, const char* who, SimpleHeadTrainPlan* plan) {
-  KVQ_REQUIRE(a->feat.rows && a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
+// Every host check of a step but those of its outputs.  The bank part has refused misaligned rows.
+static int simple_headtrain_check(const KvqHeadTrainBankArgs* a, const char* who, SimpleHeadTrainPlan* plan) {
+  if (int rc = headtrain_bank_check(a, who)) return rc;
+  KVQ_REQUIRE(a->params && a->workspace, KVQ_ERR_NULL, "%s: NULL pointer", who);
   KVQ_REQUIRE(a->B >= 2 && a->B <= 1024 && a->L >= 1, KVQ_ERR_SHAPE, "%s: B %d outside 2 .. 1024 or T %d below 1", who, a->B, a->L);
   KVQ_REQUIRE((long)a->B * a->L <= (1L << 24), KVQ_ERR_SHAPE, "%s: B*T = %ld rows exceed 2^24", who, (long)a->B * a->L);
   KVQ_REQUIRE(a->hidden == SH_HID, KVQ_ERR_UNSUPPORTED, "%s: hidden %d (128 is built)", who, a->hidden);
   KVQ_REQUIRE(a->C >= 64 && a->C % 64 == 0, KVQ_ERR_UNSUPPORTED, "%s: C %d is not a multiple of 64", who, a->C);
   KVQ_REQUIRE(a->p_drop == 0.f, KVQ_ERR_UNSUPPORTED, "%s: p_drop %g (simpleVQAHead has no dropout: 0)", who, (double)a->p_drop);
-  KVQ_REQUIRE((((uintptr_t)a->feat.rows | (uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
+  KVQ_REQUIRE((((uintptr_t)a->params | (uintptr_t)a->workspace) & 15) == 0, KVQ_ERR_UNSUPPORTED,
               "%s: feat, params and workspace must be 16-byte aligned", who);
   *plan = simple_headtrain_plan(a->B, a->L, a->C);
   KVQ_REQUIRE(a->workspace_bytes >= plan->total * sizeof(float), KVQ_ERR_WORKSPACE, "%s: workspace %zu bytes, %zu needed", who,
@@ -241,77 +225,52 @@ extern "C" size_t kvq_simple_headtrain_workspace_bytes(int B, int T, int C, int 
 
 namespace kvq {
 
-static int simple_headtrain_forward_call(const HeadTrainCall* a, const char* who, void* stream) {
+static int simple_headtrain_forward_call(const KvqHeadTrainBankArgs* a, const char* who, void* stream) {
   SimpleHeadTrainPlan pl;
   if (int rc = simple_headtrain_check(a, who, &pl)) return rc;
   KVQ_REQUIRE(a->score, KVQ_ERR_NULL, "%s: NULL pointer", who);
   float* ws = static_cast<float*>(a->workspace);
-  const float* w1 = a->params;
-  const float* b1 = w1 + (size_t)SH_HID * a->C;
-  const float* w2 = b1 + SH_HID;
-  const float* b2 = w2 + SH_HID;
-  if (int rc = launch("simple_fwd_u_kernel", simple_fwd_u_kernel, dim3((unsigned)(a->C / 64)), dim3(256), 0, stream, w1, w2, a->C, ws + pl.u))
+  const HeadParams p = head_params(a->params, SH_HID, a->C);
+  if (int rc = launch("simple_fwd_u_kernel", simple_fwd_u_kernel, dim3((unsigned)(a->C / 64)), dim3(256), 0, stream, p.w1, p.w2, a->C,
+                      ws + pl.u))
     return rc;
-  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+  if (int rc = with_bank_elem(a->bank.dtype, [&](auto e) {
         using E = decltype(e);
-        return launch("simple_fwd_rows_kernel", simple_fwd_rows_kernel<E, decltype(idx)::value>, grid_1d(pl.N * pl.nseg, 4), dim3(256), 0,
-                      stream, static_cast<const E*>(a->feat.rows), a->feat.index, a->feat.n_rows, a->L, ws + pl.u, pl.N, a->C, pl.nseg,
-                      ws + pl.part);
+        return launch("simple_fwd_rows_kernel", simple_fwd_rows_kernel<E>, grid_1d(pl.N * pl.nseg, 4), dim3(256), 0, stream,
+                      static_cast<const E*>(a->bank.rows), a->index, (long)a->bank.n_rows, a->L, ws + pl.u, pl.N, a->C, pl.nseg, ws + pl.part);
       }))
     return rc;
   return launch("simple_fwd_score_kernel", simple_fwd_score_kernel, dim3((unsigned)a->B), dim3(64), 0, stream, ws + pl.part, a->L * pl.nseg,
-                a->L, b1, w2, b2, a->score);
+                a->L, p.b1, p.w2, p.b2, a->score);
 }
 
-static int simple_headtrain_backward_call(const HeadTrainCall* a, const char* who, void* stream) {
+static int simple_headtrain_backward_call(const KvqHeadTrainBankArgs* a, const char* who, void* stream) {
   SimpleHeadTrainPlan pl;
   if (int rc = simple_headtrain_check(a, who, &pl)) return rc;
   KVQ_REQUIRE(a->dscore && a->grads, KVQ_ERR_NULL, "%s: NULL pointer", who);
   KVQ_REQUIRE(((uintptr_t)a->grads & 15) == 0, KVQ_ERR_UNSUPPORTED, "%s: grads must be 16-byte aligned", who);
   float* ws = static_cast<float*>(a->workspace);
-  const float* w1 = a->params;
-  const float* b1 = w1 + (size_t)SH_HID * a->C;
-  const float* w2 = b1 + SH_HID;
-  if (int rc = with_headtrain_feat(a->feat, [&](auto e, auto idx) {
+  const HeadParams p = head_params(a->params, SH_HID, a->C);
+  if (int rc = with_bank_elem(a->bank.dtype, [&](auto e) {
         using E = decltype(e);
-        return launch("simple_bwd_g_kernel", simple_bwd_g_kernel<E, decltype(idx)::value>,
-                      dim3((unsigned)((a->C + 127) / 128), (unsigned)pl.nchunks), dim3(256), 0, stream, static_cast<const E*>(a->feat.rows),
-                      a->feat.index, a->feat.n_rows, a->dscore, pl.N, a->L, a->C, pl.chunk, ws + pl.gpart);
+        return launch("simple_bwd_g_kernel", simple_bwd_g_kernel<E>, dim3((unsigned)((a->C + 127) / 128), (unsigned)pl.nchunks), dim3(256), 0,
+                      stream, static_cast<const E*>(a->bank.rows), a->index, (long)a->bank.n_rows, a->dscore, pl.N, a->L, a->C, pl.chunk,
+                      ws + pl.gpart);
       }))
     return rc;
   if (int rc = launch("simple_bwd_w1_kernel", simple_bwd_w1_kernel, dim3((unsigned)((a->C + 255) / 256), 8u), dim3(256), 0, stream, ws + pl.gpart,
-                      w2, a->C, pl.nchunks, ws + pl.g, a->grads))
+                      p.w2, a->C, pl.nchunks, ws + pl.g, a->grads))
     return rc;
-  return launch("simple_bwd_small_kernel", simple_bwd_small_kernel, dim3((unsigned)SH_HID), dim3(256), 0, stream, w1, b1, w2, ws + pl.g, a->dscore,
-                a->B, a->C, a->grads + (size_t)SH_HID * a->C);
+  return launch("simple_bwd_small_kernel", simple_bwd_small_kernel, dim3((unsigned)SH_HID), dim3(256), 0, stream, p.w1, p.b1, p.w2, ws + pl.g,
+                a->dscore, a->B, a->C, a->grads + (size_t)SH_HID * a->C);
 }
 
 }  // namespace kvq
 
-extern "C" int kvq_simple_headtrain_forward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
-  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_simple_headtrain_forward: NULL pointer");
-  const HeadTrainCall c = headtrain_call(a);
-  return simple_headtrain_forward_call(&c, "kvq_simple_headtrain_forward", stream);
-}
-
 extern "C" int kvq_simple_headtrain_bank_forward(const KvqHeadTrainBankArgs* a, void* stream) {
-  using namespace kvq;
-  if (int rc = headtrain_bank_check(a, "kvq_simple_headtrain_bank_forward")) return rc;
-  const HeadTrainCall c = headtrain_call(a);
-  return simple_headtrain_forward_call(&c, "kvq_simple_headtrain_bank_forward", stream);
-}
-
-extern "C" int kvq_simple_headtrain_backward(const KvqHeadTrainArgs* a, void* stream) {
-  using namespace kvq;
-  KVQ_REQUIRE(a, KVQ_ERR_NULL, "kvq_simple_headtrain_backward: NULL pointer");
-  const HeadTrainCall c = headtrain_call(a);
-  return simple_headtrain_backward_call(&c, "kvq_simple_headtrain_backward", stream);
+  return kvq::simple_headtrain_forward_call(a, "kvq_simple_headtrain_bank_forward", stream);
 }
 
 extern "C" int kvq_simple_headtrain_bank_backward(const KvqHeadTrainBankArgs* a, void* stream) {
-  using namespace kvq;
-  if (int rc = headtrain_bank_check(a, "kvq_simple_headtrain_bank_backward")) return rc;
-  const HeadTrainCall c = headtrain_call(a);
-  return simple_headtrain_backward_call(&c, "kvq_simple_headtrain_bank_backward", stream);
+  return kvq::simple_headtrain_backward_call(a, "kvq_simple_headtrain_bank_backward", stream);
 }

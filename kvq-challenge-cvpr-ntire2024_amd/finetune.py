@@ -53,8 +53,8 @@ class _Finetuner:
     """What the finetuners of the two head types share: the flat parameter vector with its AdamW state and EMA copy, the schedule, the
     feature cache, the step around the head's own launches, the epochs and the write-back.  A subclass sets ``hidden`` and gives
     ``_check_head`` (refusals; -> in_channels), ``_head_params`` (the head's four nn.Parameters in flat order), ``_clip_features``
-    (the backbone's output of one video -> [samples][L][C]), ``_forward`` / ``_backward`` (the launches on a dense batch),
-    ``_bank_forward`` / ``_bank_backward`` (the same on bank rows) and ``predict``."""
+    (the backbone's output of one video -> [samples][L][C]), ``_forward(bank, index, ws)`` / ``_backward(bank, index, ws, dscore)``
+    (the head's launches on the rows ``index`` of a bank) and ``predict``."""
     hidden = None
 
     def __init__(self, model, key, lr, wd, warmup_iters, max_iters, ema=True, seed=0, rank_weight=0.0):
@@ -168,6 +168,18 @@ class _Finetuner:
     def current_lr(self) -> float:
         return self.lr * lr_factor(self.it, self.warmup_iters, self.max_iters)
 
+    def _step(self, bank, index, labels):
+        """one step on the rows ``index`` (int32 on the device) of ``bank``"""
+        ws = self._workspace(index.numel(), bank.L)
+        score = self._forward(bank, index, ws)
+        out3, dscore = kernels.headtrain_loss(score, labels, self.rank_weight)
+        self._backward(bank, index, ws, dscore)
+        lr = self.current_lr()
+        kernels.headtrain_adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.ema, lr, self.wd, self.it + 1)
+        self.it += 1
+        loss, plcc, rank = out3.tolist()
+        return {"loss": loss, "plcc_loss": plcc, "rank_loss": rank, "lr": lr}
+
     def step(self, feats, labels):
         """forward, loss, backward, AdamW, scheduler, EMA on one batch: feats fp32 [B][L][C] on the device, labels [B].
         -> dict(loss, plcc_loss, rank_loss, lr), the learning rate being the one this step applied"""
@@ -176,15 +188,10 @@ class _Finetuner:
         B, L, C = feats.shape
         if C != self.C or labels.numel() != B:
             raise ValueError(f"step(): features {tuple(feats.shape)} / {labels.numel()} labels do not fit a {self.C}-channel head")
-        ws = self._workspace(B, L)
-        score = self._forward(feats, ws)
-        out3, dscore = kernels.headtrain_loss(score, labels, self.rank_weight)
-        self._backward(feats, ws, dscore)
-        lr = self.current_lr()
-        kernels.headtrain_adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.ema, lr, self.wd, self.it + 1)
-        self.it += 1
-        loss, plcc, rank = out3.tolist()
-        return {"loss": loss, "plcc_loss": plcc, "rank_loss": rank, "lr": lr}
+        ident = self._ws.get(B)                      # the batch as a bank: its own rows under the index 0 .. B-1, made once per B
+        if ident is None:
+            ident = self._ws[B] = torch.arange(B, dtype=torch.int32, device=self.device)
+        return self._step(kernels.FeatureBank.of(feats), ident, labels)
 
     def step_indexed(self, index, labels):
         """``step`` on the bank rows ``index`` (int32 on the device, or a CPU tensor, which is checked against the bank and uploaded),
@@ -197,15 +204,7 @@ class _Finetuner:
         if self.bank.C != self.C or labels.numel() != B:
             raise ValueError(f"step_indexed(): {B} rows of a bank {tuple(self.bank.tensor.shape)} / {labels.numel()} labels do not fit a "
                              f"{self.C}-channel head")
-        ws = self._workspace(B, self.bank.L)
-        score = self._bank_forward(index, ws)
-        out3, dscore = kernels.headtrain_loss(score, labels, self.rank_weight)
-        self._bank_backward(index, ws, dscore)
-        lr = self.current_lr()
-        kernels.headtrain_adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.ema, lr, self.wd, self.it + 1)
-        self.it += 1
-        loss, plcc, rank = out3.tolist()
-        return {"loss": loss, "plcc_loss": plcc, "rank_loss": rank, "lr": lr}
+        return self._step(self.bank, index, labels)
 
     def fit(self, epochs, batch_size):
         """``epochs`` passes over the cached samples: pass e (counted across calls) trains on draw ``e % draws``; a seeded permutation of
@@ -277,17 +276,11 @@ class HeadFinetuner(_Finetuner):
     def _new_workspace(self, B, L):
         return kernels.headtrain_workspace(B, L, self.C, HIDDEN, device=self.device)
 
-    def _forward(self, feats, ws):
-        return kernels.headtrain_forward(feats, self.params, self.p_drop, self.seed, self.it, ws)
+    def _forward(self, bank, index, ws):
+        return kernels.headtrain_bank_forward(bank, index, self.params, self.p_drop, self.seed, self.it, ws)
 
-    def _backward(self, feats, ws, dscore):
-        kernels.headtrain_backward(feats, self.params, self.p_drop, self.seed, self.it, ws, dscore, self.grads)
-
-    def _bank_forward(self, index, ws):
-        return kernels.headtrain_bank_forward(self.bank, index, self.params, self.p_drop, self.seed, self.it, ws)
-
-    def _bank_backward(self, index, ws, dscore):
-        kernels.headtrain_bank_backward(self.bank, index, self.params, self.p_drop, self.seed, self.it, ws, dscore, self.grads)
+    def _backward(self, bank, index, ws, dscore):
+        kernels.headtrain_bank_backward(bank, index, self.params, self.p_drop, self.seed, self.it, ws, dscore, self.grads)
 
     def predict(self, feats, ema=False):
         """eval-mode scores [B] of features [B][L][C] (fp32, or the 16-bit rows of a bank, widened here) with the current weights
@@ -324,17 +317,11 @@ class SimpleHeadFinetuner(_Finetuner):
     def _new_workspace(self, B, L):
         return kernels.simple_headtrain_workspace(B, L, self.C, SIMPLE_HIDDEN, device=self.device)
 
-    def _forward(self, feats, ws):
-        return kernels.simple_headtrain_forward(feats, self.params, ws)
+    def _forward(self, bank, index, ws):
+        return kernels.simple_headtrain_bank_forward(bank, index, self.params, ws)
 
-    def _backward(self, feats, ws, dscore):
-        kernels.simple_headtrain_backward(feats, self.params, ws, dscore, self.grads)
-
-    def _bank_forward(self, index, ws):
-        return kernels.simple_headtrain_bank_forward(self.bank, index, self.params, ws)
-
-    def _bank_backward(self, index, ws, dscore):
-        kernels.simple_headtrain_bank_backward(self.bank, index, self.params, ws, dscore, self.grads)
+    def _backward(self, bank, index, ws, dscore):
+        kernels.simple_headtrain_bank_backward(bank, index, self.params, ws, dscore, self.grads)
 
     def predict(self, feats, ema=False):
         """scores [B] of features [B][T][C] with the current weights (``ema``: the EMA copy), by the inference launch"""

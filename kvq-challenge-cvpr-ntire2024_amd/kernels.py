@@ -1705,9 +1705,10 @@ def conv_stem_direct(x: torch.Tensor, w_kc: torch.Tensor, bias: torch.Tensor, ke
     return out
 
 
-# ---- VQAHead training step (csrc/headtrain.hip): thin wrappers; kvq_amd/finetune.py drives them ---------------------------------
+# ---- VQAHead training step (csrc/headtrain.hip): thin wrappers; kvq_amd/finetune.py drives them.  The forward and the backward read
+# bank rows: they follow the feature bank below ----------------------------------------------------------------------------------------
 def headtrain_param_count(C_in: int, hidden: int = 64) -> int:
-    """length of the flat parameter vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]"""
+    """length of the flat parameter vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1] of either head (simpleVQAHead: hidden 128)"""
     return hidden * C_in + 2 * hidden + 1
 
 
@@ -1728,28 +1729,6 @@ def headtrain_mask(seed: int, step: int, which: int, p: float, n: int, device=No
     return out
 
 
-def _headtrain_args(feat, params, p, seed, step, ws, score=None, dscore=None, grads=None, hidden=64):
-    _need_gpu(feat, params, ws, score, dscore, grads)
-    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous(), "features: dense fp32 [B][L][C]"
-    B, L, Cc = feat.shape
-    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == headtrain_param_count(Cc, hidden)
-    a = _abi.KvqHeadTrainArgs()
-    a.feat, a.B, a.L, a.C, a.hidden, a.params = ptr(feat), B, L, Cc, hidden, ptr(params)
-    a.p_drop, a.seed, a.step = float(p), seed & 0xFFFFFFFF, step & 0xFFFFFFFF
-    a.workspace, a.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
-    a.score, a.dscore, a.grads = ptr(score), ptr(dscore), ptr(grads)
-    return a
-
-
-def headtrain_forward(feat, params, p, seed, step, ws, score=None):
-    """train-mode scores fp32 [B] of channels-last features [B][L][C] under the flat parameters; the pre-activations stay in ``ws``"""
-    if score is None:
-        score = torch.empty(feat.shape[0], dtype=torch.float32, device=feat.device)
-    a = _headtrain_args(feat, params, p, seed, step, ws, score=score)
-    check(lib().kvq_headtrain_forward(C.byref(a), stream_of(feat)), "kvq_headtrain_forward")
-    return score
-
-
 def headtrain_loss(score, label, rank_weight=0.0, out3=None, dscore=None):
     """-> (out3 = [loss, plcc_loss, rank_loss], dscore [B]) of trainer.py:337-354, one launch"""
     _need_gpu(score, label)
@@ -1763,16 +1742,6 @@ def headtrain_loss(score, label, rank_weight=0.0, out3=None, dscore=None):
     return out3, dscore
 
 
-def headtrain_backward(feat, params, p, seed, step, ws, dscore, grads=None):
-    """the flat gradient (layout of ``params``) from ``dscore`` [B]; reads the pre-activations the forward of the same
-    (seed, step, p) left in ``ws``"""
-    if grads is None:
-        grads = torch.empty_like(params)
-    a = _headtrain_args(feat, params, p, seed, step, ws, dscore=dscore, grads=grads)
-    check(lib().kvq_headtrain_backward(C.byref(a), stream_of(feat)), "kvq_headtrain_backward")
-    return grads
-
-
 def headtrain_adamw(params, grads, exp_avg, exp_avg_sq, ema, lr, wd, step):
     """torch.optim.AdamW's update of the flat vector in place (optimiser step ``step`` >= 1), then the EMA copy (``ema`` None: skipped)"""
     _need_gpu(params, grads, exp_avg, exp_avg_sq, ema)
@@ -1783,13 +1752,7 @@ def headtrain_adamw(params, grads, exp_avg, exp_avg_sq, ema, lr, wd, step):
                                     stream_of(params)), "kvq_headtrain_adamw")
 
 
-# ---- simpleVQAHead training step (csrc/simple_headtrain.hip): thin wrappers; kvq_amd/finetune.py drives them; the loss and the optimiser
-# are headtrain_loss and headtrain_adamw above ---------------------------------------------------------------------------------------------
-def simple_headtrain_param_count(C_in: int, hidden: int = 128) -> int:
-    """length of the flat parameter vector W1 [hidden][C] | b1 [hidden] | w2 [hidden] | b2 [1]"""
-    return hidden * C_in + 2 * hidden + 1
-
-
+# ---- simpleVQAHead training step (csrc/simple_headtrain.hip): the loss and the optimiser are headtrain_loss and headtrain_adamw above ----
 def simple_headtrain_workspace(B: int, T: int, C_in: int, hidden: int = 128, device=None) -> torch.Tensor:
     """the workspace the forward and the backward of one (B, T, C) share; raises for a shape that is not built"""
     n = int(lib().kvq_simple_headtrain_workspace_bytes(B, T, C_in, hidden))
@@ -1797,40 +1760,6 @@ def simple_headtrain_workspace(B: int, T: int, C_in: int, hidden: int = 128, dev
         raise _abi.KvqError(f"kvq_simple_headtrain: shape B={B} T={T} C={C_in} hidden={hidden} is not built "
                             "(2 <= B <= 1024, C a multiple of 64, hidden 128)")
     return torch.empty(n // 4, dtype=torch.float32, device=device if device is not None else "cuda")
-
-
-def _simple_headtrain_args(feat, params, ws, score=None, dscore=None, grads=None, hidden=128):
-    _need_gpu(feat, params, ws, score, dscore, grads)
-    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous(), "features: dense fp32 [B][T][C]"
-    B, T, Cc = feat.shape
-    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == simple_headtrain_param_count(Cc, hidden)
-    a = _abi.KvqHeadTrainArgs()
-    a.feat, a.B, a.L, a.C, a.hidden, a.params = ptr(feat), B, T, Cc, hidden, ptr(params)
-    a.p_drop, a.seed, a.step = 0.0, 0, 0
-    a.workspace, a.workspace_bytes = ptr(ws), ws.numel() * ws.element_size()
-    a.score, a.dscore, a.grads = ptr(score), ptr(dscore), ptr(grads)
-    return a
-
-
-def simple_headtrain_forward(feat, params, ws, score=None):
-    """scores fp32 [B] of features [B][T][C] under the flat parameters: the mean over the T frames of the two Linears"""
-    if score is None:
-        score = torch.empty(feat.shape[0], dtype=torch.float32, device=feat.device)
-    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == feat.shape[0]
-    a = _simple_headtrain_args(feat, params, ws, score=score)
-    check(lib().kvq_simple_headtrain_forward(C.byref(a), stream_of(feat)), "kvq_simple_headtrain_forward")
-    return score
-
-
-def simple_headtrain_backward(feat, params, ws, dscore, grads=None):
-    """the flat gradient (layout of ``params``, written in full) from ``dscore`` [B]; needs no forward before it"""
-    if grads is None:
-        grads = torch.empty_like(params)
-    assert dscore.dtype == torch.float32 and dscore.is_contiguous() and dscore.numel() == feat.shape[0]
-    assert grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == params.numel()
-    a = _simple_headtrain_args(feat, params, ws, dscore=dscore, grads=grads)
-    check(lib().kvq_simple_headtrain_backward(C.byref(a), stream_of(feat)), "kvq_simple_headtrain_backward")
-    return grads
 
 
 # ---- feature bank (csrc/featbank.hip) and the two training steps on its rows: thin wrappers; kvq_amd/finetune.py drives them ------------
@@ -1895,11 +1824,11 @@ def feature_bank_rows(bank: FeatureBank, index, out: Optional[torch.Tensor] = No
     return out
 
 
-def _headtrain_bank_args(bank, index, params, p, seed, step, ws, hidden, count, score=None, dscore=None, grads=None):
+def _headtrain_bank_args(bank, index, params, p, seed, step, ws, hidden, score=None, dscore=None, grads=None):
     idx = bank_index(index, bank)
     _need_gpu(bank.tensor, idx, params, ws, score, dscore, grads)
     B = idx.numel()
-    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == count(bank.C, hidden)
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == headtrain_param_count(bank.C, hidden)
     for t in (score, dscore):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B)
     assert grads is None or (grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == params.numel())
@@ -1912,36 +1841,61 @@ def _headtrain_bank_args(bank, index, params, p, seed, step, ws, hidden, count, 
 
 
 def headtrain_bank_forward(bank, index, params, p, seed, step, ws, score=None):
-    """``headtrain_forward`` on the bank rows ``index``, read in place: bit-equal to it on ``feature_bank_rows(bank, index)``"""
+    """train-mode scores fp32 [B] of the bank rows ``index`` (channels-last [L][C] each, read in place and widened in registers) under
+    the flat parameters; the pre-activations stay in ``ws``"""
     if score is None:
         score = torch.empty(len(index), dtype=torch.float32, device=bank.tensor.device)
-    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, headtrain_param_count, score=score)
+    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, score=score)
     check(lib().kvq_headtrain_bank_forward(C.byref(a), stream_of(bank.tensor)), "kvq_headtrain_bank_forward")
     return score
 
 
 def headtrain_bank_backward(bank, index, params, p, seed, step, ws, dscore, grads=None):
-    """``headtrain_backward`` on the bank rows ``index``, read in place"""
+    """the flat gradient (layout of ``params``) from ``dscore`` [B]; reads the pre-activations the forward of the same
+    (seed, step, p) left in ``ws``"""
     if grads is None:
         grads = torch.empty_like(params)
-    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, headtrain_param_count, dscore=dscore, grads=grads)
+    a, idx = _headtrain_bank_args(bank, index, params, p, seed, step, ws, 64, dscore=dscore, grads=grads)
     check(lib().kvq_headtrain_bank_backward(C.byref(a), stream_of(bank.tensor)), "kvq_headtrain_bank_backward")
     return grads
 
 
 def simple_headtrain_bank_forward(bank, index, params, ws, score=None):
-    """``simple_headtrain_forward`` on the bank rows ``index`` ([n_rows][T][C]), read in place"""
+    """scores fp32 [B] of the bank rows ``index`` ([T][C] each, read in place) under the flat parameters: the mean over the T frames of
+    the two Linears"""
     if score is None:
         score = torch.empty(len(index), dtype=torch.float32, device=bank.tensor.device)
-    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, simple_headtrain_param_count, score=score)
+    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, score=score)
     check(lib().kvq_simple_headtrain_bank_forward(C.byref(a), stream_of(bank.tensor)), "kvq_simple_headtrain_bank_forward")
     return score
 
 
 def simple_headtrain_bank_backward(bank, index, params, ws, dscore, grads=None):
-    """``simple_headtrain_backward`` on the bank rows ``index``, read in place"""
+    """the flat gradient (layout of ``params``, written in full) from ``dscore`` [B]; needs no forward before it"""
     if grads is None:
         grads = torch.empty_like(params)
-    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, simple_headtrain_param_count, dscore=dscore, grads=grads)
+    a, idx = _headtrain_bank_args(bank, index, params, 0.0, 0, 0, ws, 128, dscore=dscore, grads=grads)
     check(lib().kvq_simple_headtrain_bank_backward(C.byref(a), stream_of(bank.tensor)), "kvq_simple_headtrain_bank_backward")
     return grads
+
+
+# ---- the two steps on a dense fp32 batch [B][L][C]: an fp32 bank of its B rows under the index 0 .. B-1 --------------------------------
+def _dense_bank(feat):
+    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous(), "features: dense fp32 [B][L][C]"
+    return FeatureBank.of(feat), torch.arange(feat.shape[0], dtype=torch.int32, device=feat.device)
+
+
+def headtrain_forward(feat, params, p, seed, step, ws, score=None):
+    return headtrain_bank_forward(*_dense_bank(feat), params, p, seed, step, ws, score)
+
+
+def headtrain_backward(feat, params, p, seed, step, ws, dscore, grads=None):
+    return headtrain_bank_backward(*_dense_bank(feat), params, p, seed, step, ws, dscore, grads)
+
+
+def simple_headtrain_forward(feat, params, ws, score=None):
+    return simple_headtrain_bank_forward(*_dense_bank(feat), params, ws, score)
+
+
+def simple_headtrain_backward(feat, params, ws, dscore, grads=None):
+    return simple_headtrain_bank_backward(*_dense_bank(feat), params, ws, dscore, grads)

@@ -24,7 +24,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(handle, name), f"{name} declared in kvq_hip.h but not exported"
     assert declared == set(_abi.SYMBOLS), declared ^ set(_abi.SYMBOLS)
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
 
 
 def test_library_reads_only_the_documented_environment_switches():

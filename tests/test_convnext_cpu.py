@@ -128,7 +128,7 @@ def test_new_symbols_are_declared_and_exported():
         assert re.search(r"\b%s\(" % name, header) and name in _abi.SYMBOLS
         assert getattr(lib, name) is not None
     assert "KVQ_EPI_RESID_SCALE_F32 = 7" in header and _abi.EPI_RESID_SCALE_F32 == 7
-    assert lib.kvq_abi_version() == 31 and C.sizeof(_abi.KvqGemmArgs) == 144
+    assert lib.kvq_abi_version() == 32 and C.sizeof(_abi.KvqGemmArgs) == 144
     assert C.sizeof(_abi.KvqDwconvLnArgs) == 88
 
 

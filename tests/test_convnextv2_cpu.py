@@ -164,7 +164,7 @@ def test_new_symbols_are_declared_and_exported():
     for name in ("kvq_grn_supported", "kvq_grn_workspace_bytes", "kvq_grn_stats", "kvq_grn_apply"):
         assert re.search(r"\b%s\(" % name, header) and name in _abi.SYMBOLS
         assert getattr(lib, name) is not None
-    assert lib.kvq_abi_version() == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert lib.kvq_abi_version() == 32 and "#define KVQ_ABI_VERSION 32" in header
     assert C.sizeof(_abi.KvqGrnArgs) == 5 * 8 + 7 * 4 + 4
 
 

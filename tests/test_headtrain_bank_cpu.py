@@ -6,6 +6,7 @@ import os
 import random
 import re
 import shutil
+import subprocess
 import sys
 
 import numpy as np
@@ -20,6 +21,7 @@ from kvq_amd.datasets import fusion_datasets as fd
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["kvq_feature_bank_store", "kvq_feature_bank_rows", "kvq_headtrain_bank_forward", "kvq_headtrain_bank_backward",
        "kvq_simple_headtrain_bank_forward", "kvq_simple_headtrain_bank_backward"]
+GONE = ["kvq_headtrain_forward", "kvq_headtrain_backward", "kvq_simple_headtrain_forward", "kvq_simple_headtrain_backward"]
 NULL, SHAPE, UNSUPPORTED, WORKSPACE = -1, -2, -3, -4
 
 _HOST = (C.c_char * 4112)()
@@ -33,10 +35,16 @@ def test_symbols_declared_bound_and_sized():
     for name in NEW:
         assert name in declared and name in _abi.SYMBOLS and hasattr(handle, name), name
     assert "typedef struct KvqFeatureBank {" in header and "typedef struct KvqHeadTrainBankArgs {" in header
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
-    # {void*, int32 x 3, (pad), int64}; the bank, the index pointer, then KvqHeadTrainArgs without its feat pointer
+    exported = subprocess.run(["nm", "-D", "--defined-only", handle._name], capture_output=True, text=True, check=True).stdout.split()
+    for name in GONE:                              # the dense entries of ABI 31 and their struct are gone from every layer
+        assert name not in declared and name not in _abi.SYMBOLS and name not in exported and not hasattr(handle, name), name
+    assert set(re.findall(r"KvqHeadTrain\w*", header)) == {"KvqHeadTrainBankArgs"}      # one args struct, in the header and in _abi
+    assert [n for n in dir(_abi) if n.startswith("KvqHeadTrain")] == ["KvqHeadTrainBankArgs"]
+    assert set(NEW) <= set(exported)
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
+    # {void*, int32 x 3, (pad), int64}; the bank, the index pointer, int32 x 4, params, float + uint32 x 2 (+ pad), five 8-byte fields
     assert C.sizeof(_abi.KvqFeatureBank) == 32
-    assert C.sizeof(_abi.KvqHeadTrainArgs) == 88 and C.sizeof(_abi.KvqHeadTrainBankArgs) == 32 + 8 + (88 - 8) == 120
+    assert C.sizeof(_abi.KvqHeadTrainBankArgs) == 32 + 8 + 16 + 8 + 16 + 5 * 8 == 120
     assert (_abi.DT_BF16, _abi.DT_FP16, _abi.DT_FP32) == (0, 1, 2) and "KVQ_DT_FP32 = 2" in header
     assert _abi.bank_dtype_code(torch.float32) == 2 and _abi.bank_dtype_code("bf16") == 0 and _abi.bank_dtype_code(torch.float16) == 1
     with pytest.raises(ValueError, match="fp32, fp16 or bf16"):
@@ -260,6 +268,20 @@ def test_the_bank_ymls_are_their_parents_plus_the_bank(yml, parent, draws, dtype
 
 
 # ---- the compiler's own resource remarks (tools/kres_units.py: the library's flags, device code only, no GPU) --------------------------
+# vgpr + agpr and waves per SIMD of commit acb37f7, the last with a dense (float, no index) form of the four step kernels, by
+# tools/kres_units.py.  DENSE: that form, the bound of every instantiation; PARENT: the indexed instantiation of each element type.
+DENSE = {"headtrain_fwd_kernel": (80, 6), "headtrain_bwd_w1_kernel": (184, 2), "simple_fwd_rows_kernel": (39, 8), "simple_bwd_g_kernel": (57, 8)}
+PARENT = {"headtrain_fwd_kernel": {"fp32": (80, 6), "fp16": (80, 6), "bf16": (80, 6)},
+          "headtrain_bwd_w1_kernel": {"fp32": (184, 2), "fp16": (184, 2), "bf16": (184, 2)},
+          "simple_fwd_rows_kernel": {"fp32": (39, 8), "fp16": (38, 8), "bf16": (38, 8)},
+          "simple_bwd_g_kernel": {"fp32": (48, 8), "fp16": (46, 8), "bf16": (46, 8)}}
+
+
+def _elem(name):
+    """the element type of an instantiation from its (where c++filt knows the type, demangled) name"""
+    return "fp32" if "<float>" in name else "bf16" if "IDF16bE" in name else "fp16" if "IDF16_E" in name else name
+
+
 @pytest.mark.slow
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_no_instantiation_uses_scratch_and_none_outgrows_its_dense_form():
@@ -271,15 +293,13 @@ def test_no_instantiation_uses_scratch_and_none_outgrows_its_dense_form():
         for name, vgpr, agpr, scratch, occ in unit:
             print(name, vgpr, agpr, scratch, occ)
             assert scratch == 0, name
-            for stem in ("headtrain_fwd_kernel", "headtrain_bwd_w1_kernel", "simple_fwd_rows_kernel", "simple_bwd_g_kernel",
-                         "feature_bank_store_kernel", "feature_bank_rows_kernel"):
+            for stem in list(DENSE) + ["feature_bank_store_kernel", "feature_bank_rows_kernel"]:
                 if stem in name:
-                    seen.setdefault(stem, []).append((name, vgpr + agpr, occ))
-    # (float, no index), (float | _Float16 | __bf16, index) of the four step kernels; the three element types of the bank's own two
-    assert {k: len(v) for k, v in seen.items()} == {"headtrain_fwd_kernel": 4, "headtrain_bwd_w1_kernel": 4, "simple_fwd_rows_kernel": 4,
-                                                   "simple_bwd_g_kernel": 4, "feature_bank_store_kernel": 3, "feature_bank_rows_kernel": 3}
-    for stem in ("headtrain_fwd_kernel", "headtrain_bwd_w1_kernel", "simple_fwd_rows_kernel", "simple_bwd_g_kernel"):
-        dense = [r for r in seen[stem] if r[0].endswith("<float, false>")]
-        assert len(dense) == 1, seen[stem]
-        for name, regs, occ in seen[stem]:
-            assert regs <= dense[0][1] and occ >= dense[0][2], (name, regs, occ, dense[0])
+                    seen.setdefault(stem, {})[_elem(name)] = (vgpr + agpr, occ)
+    # float | _Float16 | __bf16 of the four step kernels and of the bank's own two
+    assert {k: sorted(v) for k, v in seen.items()} == {k: ["bf16", "fp16", "fp32"] for k in list(DENSE) + ["feature_bank_store_kernel",
+                                                                                                        "feature_bank_rows_kernel"]}
+    for stem, dense in DENSE.items():
+        for elem, (regs, occ) in seen[stem].items():
+            assert regs <= dense[0] and occ >= dense[1], (stem, elem, regs, occ, dense)
+            assert (regs, occ) == PARENT[stem][elem], (stem, elem, regs, occ, PARENT[stem][elem])     # no template parameter moved codegen

@@ -22,8 +22,8 @@ import headtrain_ref as R  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {"a": (4, 2, 3, 3, 768, 0.5, 0.0), "b": (5, 4, 7, 7, 768, 0.5, 0.0), "c": (6, 3, 7, 7, 768, 0.0, 0.0),
          "d": (7, 1, 7, 7, 768, 0.5, 0.0), "e": (4, 2, 3, 3, 128, 0.5, 0.0), "e_rank": (4, 2, 3, 3, 128, 0.5, 0.3)}
-NEW = ["kvq_headtrain_workspace_bytes", "kvq_headtrain_forward", "kvq_headtrain_backward", "kvq_headtrain_mask", "kvq_headtrain_loss",
-       "kvq_headtrain_adamw"]
+NEW = ["kvq_headtrain_workspace_bytes", "kvq_headtrain_mask", "kvq_headtrain_loss", "kvq_headtrain_adamw"]
+GONE = ["kvq_headtrain_forward", "kvq_headtrain_backward"]         # the dense entries: the step is the bank entries' (ABI 32)
 HID = 64
 
 
@@ -114,8 +114,12 @@ def test_symbols_declared_exported_and_listed():
     handle = _abi.lib()
     for name in NEW:
         assert name in declared and name in _abi.SYMBOLS and hasattr(handle, name), name
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
-    assert C.sizeof(_abi.KvqHeadTrainArgs) == 88
+    for name in GONE:
+        assert name not in declared and name not in _abi.SYMBOLS and not hasattr(handle, name), name
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
+    assert set(re.findall(r"KvqHeadTrain\w*", header)) == {"KvqHeadTrainBankArgs"}      # one args struct, in the header and in _abi
+    assert [n for n in dir(_abi) if n.startswith("KvqHeadTrain")] == ["KvqHeadTrainBankArgs"]
+    assert C.sizeof(_abi.KvqHeadTrainBankArgs) == 120 and C.sizeof(_abi.KvqFeatureBank) == 32
     src = open(os.path.join(ROOT, "kvq-challenge-cvpr-ntire2024_amd", "csrc", "headtrain.hip")).read()
     assert "getenv" not in src and "atomic" not in src.replace("No atomics", "")
 
@@ -129,16 +133,18 @@ def test_host_checks_refuse_before_any_launch():
     h = _abi.lib()
     P = C.c_void_p((C.addressof(_HOST) + 15) & ~15)
 
-    def args(**kw):
-        a = _abi.KvqHeadTrainArgs()
-        base = dict(feat=P, B=4, L=18, C=768, hidden=64, params=P, p_drop=0.5, seed=1, step=0, workspace=P, workspace_bytes=1 << 30,
+    def args(feat=P, **kw):
+        """the step on an fp32 bank of 7 rows of the step's own (L, C), ``feat`` its rows, under a valid index"""
+        a = _abi.KvqHeadTrainBankArgs()
+        base = dict(index=P, B=4, L=18, C=768, hidden=64, params=P, p_drop=0.5, seed=1, step=0, workspace=P, workspace_bytes=1 << 30,
                     score=P, dscore=P, grads=P)
         base.update(kw)
+        a.bank = _abi.KvqFeatureBank(feat, _abi.DT_FP32, base["L"], base["C"], 7)
         for k, v in base.items():
             setattr(a, k, v)
         return a
 
-    for fn in (h.kvq_headtrain_forward, h.kvq_headtrain_backward):
+    for fn in (h.kvq_headtrain_bank_forward, h.kvq_headtrain_bank_backward):
         assert fn(None, None) == -1 and b"NULL" in h.kvq_last_error()
         assert fn(C.byref(args(feat=None)), None) == -1
         assert fn(C.byref(args(params=None)), None) == -1
@@ -151,8 +157,9 @@ def test_host_checks_refuse_before_any_launch():
         assert fn(C.byref(args(B=1024, L=8192, C=768)), None) == -2 and b"32-bit" in h.kvq_last_error()
         assert fn(C.byref(args(feat=C.c_void_p(P.value + 4))), None) == -3 and b"aligned" in h.kvq_last_error()
         assert fn(C.byref(args(workspace_bytes=1024)), None) == -4
-    assert h.kvq_headtrain_forward(C.byref(args(score=None)), None) == -1
-    assert h.kvq_headtrain_backward(C.byref(args(dscore=None)), None) == -1 and h.kvq_headtrain_backward(C.byref(args(grads=None)), None) == -1
+    assert h.kvq_headtrain_bank_forward(C.byref(args(score=None)), None) == -1
+    assert h.kvq_headtrain_bank_backward(C.byref(args(dscore=None)), None) == -1
+    assert h.kvq_headtrain_bank_backward(C.byref(args(grads=None)), None) == -1
     ws = h.kvq_headtrain_workspace_bytes
     assert ws(1, 18, 768, 64) == 0 and ws(4, 18, 100, 64) == 0 and ws(4, 18, 768, 32) == 0 and ws(4, 0, 768, 64) == 0
     # z and dz [72][64], 72 token scores, one chunk (80 tokens) of dW1 partials [64][768], two 64-token runs of db1 and dw2 partials

@@ -327,7 +327,7 @@ def test_abi_surface():
     for name in ("kvq_jpeg_coef_bytes", "kvq_jpeg_probe", "kvq_jpeg_coeffs", "kvq_jpeg_idct_i420_host", "kvq_jpeg_idct_i420"):
         assert re.search(r"\b" + name + r"\s*\(", header) and name in _abi.SYMBOLS and hasattr(handle, name)
     assert "typedef struct KvqJpegInfo" in header and C.sizeof(_abi.KvqJpegInfo) == 64
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32 and "#define KVQ_ABI_VERSION 32" in header
     assert handle.kvq_jpeg_coef_bytes(16, 16) == 768 and handle.kvq_jpeg_coef_bytes(0, 16) == 0
     buf = np.zeros(16, np.uint8)
     assert handle.kvq_jpeg_idct_i420(None, None, 1, 16, 16, None, None) == -1

@@ -376,7 +376,7 @@ def test_abi_surface():
     for name in ("kvq_jpeg_index", "kvq_jpeg_entropy_host", "kvq_jpeg_entropy"):
         assert re.search(r"\b" + name + r"\s*\(", header) and name in _abi.SYMBOLS and hasattr(handle, name)
     assert "typedef struct KvqJpegTables" in header and C.sizeof(_abi.KvqJpegHuffTable) == 1364 and C.sizeof(_abi.KvqJpegTables) == 8196
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
     assert handle.kvq_jpeg_entropy(None, 0, None, None, 0, None, 0, 1, 16, 16, None, None, None) == -1
 
 

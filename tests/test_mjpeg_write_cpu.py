@@ -401,6 +401,6 @@ def test_new_entries_are_declared_listed_and_exported():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _abi.SYMBOLS and hasattr(handle, name), name
     assert "KVQ_JPEG_NO_DHT = 1" in header and _abi.JPEG_NO_DHT == 1
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32 and "#define KVQ_ABI_VERSION 32" in header
     from kvq_amd import _build
     assert {"jpeg_enc.cpp", "jpeg_enc.hip"} <= set(_build.SOURCES)

@@ -191,7 +191,7 @@ def test_new_entries_are_declared_listed_and_exported():
     handle = _abi.lib()
     for name in NEW_SYMBOLS:
         assert name in declared and name in _abi.SYMBOLS and hasattr(handle, name), name
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32 and "#define KVQ_ABI_VERSION 32" in header
     from kvq_amd import _build
     assert "jpeg_enc_entropy.hip" in _build.SOURCES and os.path.exists(os.path.join(_build.CSRC, "jpeg_enc_huff.hpp"))
 

@@ -28,7 +28,7 @@ def test_entry_points_are_declared_and_exported():
     for name in NEW:
         assert name in declared and name in _abi.SYMBOLS
         assert hasattr(handle, name)
-    assert handle.kvq_abi_version() == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert handle.kvq_abi_version() == 32 and "#define KVQ_ABI_VERSION 32" in header
     # NULL arguments: an error code, never a crash
     assert handle.kvq_vqa_head_map(None, 1, 4, 8, 0, 0, 0, None, None, None, 8, None, None, 2, None, None, None, None) == -1
     assert handle.kvq_quality_paint(None, None) == -1

@@ -39,7 +39,7 @@ def test_entry_points_are_declared_and_exported():
         assert name in declared and name in _abi.SYMBOLS
         assert hasattr(handle, name)
     assert "KvqQualityPaintRegionArgs" in header
-    assert handle.kvq_abi_version() == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert handle.kvq_abi_version() == 32 and "#define KVQ_ABI_VERSION 32" in header
     # the structs the existing entry points take keep their sizes; the new one is the old one plus its five fields
     assert C.sizeof(_abi.KvqQualityPaintRegionArgs) == C.sizeof(_abi.KvqQualityPaintArgs) + 8 + 4 * 4
     # NULL arguments: an error code, never a crash

@@ -23,7 +23,7 @@ def test_entry_points_are_declared_and_exported():
     for name in NEW:
         assert name in declared and name in _abi.SYMBOLS
         assert hasattr(handle, name)
-    assert handle.kvq_abi_version() == 31
+    assert handle.kvq_abi_version() == 32
     # NULL plan: an error code, never a crash
     assert handle.kvq_swin3d_set_range_flags(None, None) != 0
     assert handle.kvq_swin3d_plan_set_resid16(None, 0) != 0

@@ -71,7 +71,7 @@ def test_abi_declares_the_entries_and_keeps_its_version():
     handle = _abi.lib()
     for name in ("kvq_resize_pil", "kvq_resize_pil_taps", "kvq_resize_pil_supported"):
         assert name + "(" in header and name in _abi.SYMBOLS and hasattr(handle, name)
-    assert _abi.ABI_VERSION == 31 and handle.kvq_abi_version() == 31 and "#define KVQ_ABI_VERSION 31" in header
+    assert _abi.ABI_VERSION == 32 and handle.kvq_abi_version() == 32 and "#define KVQ_ABI_VERSION 32" in header
 
 
 def test_entry_checks_on_the_host_before_any_launch():

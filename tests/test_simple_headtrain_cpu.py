@@ -22,7 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the 32-row minimum (30 runs of 40 rows), added in segments of 8, 8, 8 and 6
 CASES = {"a": (4, 8, 9472, 0.0), "b": (5, 3, 9472, 0.0), "c": (7, 1, 192, 0.0), "d": (33, 8, 704, 0.0), "c_rank": (7, 1, 192, 0.3),
          "e": (300, 4, 192, 0.0)}
-NEW = ["kvq_simple_headtrain_workspace_bytes", "kvq_simple_headtrain_forward", "kvq_simple_headtrain_backward"]
+NEW = ["kvq_simple_headtrain_workspace_bytes"]
+GONE = ["kvq_simple_headtrain_forward", "kvq_simple_headtrain_backward"]   # the dense entries: the step is the bank entries' (ABI 32)
 HID = 128
 SUB = (slice(3, None, 16), slice(5, None, 64))
 
@@ -102,8 +103,12 @@ def test_symbols_declared_exported_and_listed():
     handle = _abi.lib()
     for name in NEW:
         assert name in declared and name in _abi.SYMBOLS and hasattr(handle, name), name
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
-    assert C.sizeof(_abi.KvqHeadTrainArgs) == 88
+    for name in GONE:
+        assert name not in declared and name not in _abi.SYMBOLS and not hasattr(handle, name), name
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
+    assert set(re.findall(r"KvqHeadTrain\w*", header)) == {"KvqHeadTrainBankArgs"}      # one args struct, in the header and in _abi
+    assert [n for n in dir(_abi) if n.startswith("KvqHeadTrain")] == ["KvqHeadTrainBankArgs"]
+    assert C.sizeof(_abi.KvqHeadTrainBankArgs) == 120 and C.sizeof(_abi.KvqFeatureBank) == 32
     src = open(os.path.join(ROOT, "kvq-challenge-cvpr-ntire2024_amd", "csrc", "simple_headtrain.hip")).read()
     assert "getenv" not in src and "atomic" not in src.replace("No\n// atomics", "").replace("No atomics", "")
 
@@ -128,17 +133,19 @@ def test_host_checks_refuse_before_any_launch():
     P = C.c_void_p((C.addressof(_HOST) + 15) & ~15)
     off = C.c_void_p(P.value + 4)
 
-    def args(**kw):
-        a = _abi.KvqHeadTrainArgs()
-        base = dict(feat=P, B=4, L=8, C=9472, hidden=128, params=P, p_drop=0.0, seed=0, step=0, workspace=P, workspace_bytes=1 << 30,
+    def args(feat=P, **kw):
+        """the step on an fp32 bank of 7 rows of [8][the step's C], ``feat`` its rows, under a valid index"""
+        a = _abi.KvqHeadTrainBankArgs()
+        base = dict(index=P, B=4, L=8, C=9472, hidden=128, params=P, p_drop=0.0, seed=0, step=0, workspace=P, workspace_bytes=1 << 30,
                     score=P, dscore=P, grads=P)
         base.update(kw)
+        a.bank = _abi.KvqFeatureBank(feat, _abi.DT_FP32, 8, base["C"], 7)
         for k, v in base.items():
             setattr(a, k, v)
         return a
 
-    for fn, who in ((h.kvq_simple_headtrain_forward, b"kvq_simple_headtrain_forward"),
-                    (h.kvq_simple_headtrain_backward, b"kvq_simple_headtrain_backward")):
+    for fn, who in ((h.kvq_simple_headtrain_bank_forward, b"kvq_simple_headtrain_bank_forward"),
+                    (h.kvq_simple_headtrain_bank_backward, b"kvq_simple_headtrain_bank_backward")):
         assert fn(None, None) == -1 and b"NULL" in h.kvq_last_error() and who in h.kvq_last_error()
         assert fn(C.byref(args(feat=None)), None) == -1
         assert fn(C.byref(args(params=None)), None) == -1
@@ -153,12 +160,12 @@ def test_host_checks_refuse_before_any_launch():
         for k in ("feat", "params", "workspace"):
             assert fn(C.byref(args(**{k: off})), None) == -3 and b"aligned" in h.kvq_last_error(), k
         assert fn(C.byref(args(workspace_bytes=4 * ws_floats(4, 8, 9472) - 4)), None) == -4 and b"workspace" in h.kvq_last_error()
-    assert h.kvq_simple_headtrain_forward(C.byref(args(score=None)), None) == -1
-    assert h.kvq_simple_headtrain_backward(C.byref(args(dscore=None)), None) == -1
-    assert h.kvq_simple_headtrain_backward(C.byref(args(grads=None)), None) == -1
-    assert h.kvq_simple_headtrain_backward(C.byref(args(grads=off)), None) == -3 and b"grads" in h.kvq_last_error()
+    assert h.kvq_simple_headtrain_bank_forward(C.byref(args(score=None)), None) == -1
+    assert h.kvq_simple_headtrain_bank_backward(C.byref(args(dscore=None)), None) == -1
+    assert h.kvq_simple_headtrain_bank_backward(C.byref(args(grads=None)), None) == -1
+    assert h.kvq_simple_headtrain_bank_backward(C.byref(args(grads=off)), None) == -3 and b"grads" in h.kvq_last_error()
     # the VQAHead entries keep their own width
-    assert h.kvq_headtrain_forward(C.byref(args(hidden=128, C=768)), None) == -3 and b"hidden 128" in h.kvq_last_error()
+    assert h.kvq_headtrain_bank_forward(C.byref(args(hidden=128, C=768)), None) == -3 and b"hidden 128" in h.kvq_last_error()
 
 
 def test_workspace_bytes_equal_the_documented_formula():

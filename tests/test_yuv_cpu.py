@@ -128,7 +128,7 @@ def _write(tmp_path, frames, H, W):
 
 def test_abi_surface_is_additive():
     handle = _abi.lib()
-    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 31
+    assert handle.kvq_abi_version() == _abi.ABI_VERSION == 32
     assert C.sizeof(_abi.KvqFragmentSource) == 3 * 16 * 8 + 8 + 10 * 4 + 2 * 16 + 8
     for name in ("kvq_yuv420_coeffs", "kvq_yuv420_to_rgb"):
         assert hasattr(handle, name) and name in _abi.SYMBOLS

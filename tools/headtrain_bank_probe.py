@@ -7,8 +7,9 @@ card at 16 bits) and the training regime, not speed.
 
   - VQAHead step at B = 16 and 256 clips of L = 16 x 7 x 7 tokens, C = 768, dropout 0.5; simpleVQAHead step at B = 16 and 256 videos of
     T = 8 rows, C = 9472.  The bank holds 4 B rows, the batch is a shuffled index into it.
-  - 'index_select + step': feats.index_select(0, idx) on the fp32 rows, then forward, loss, backward, AdamW + EMA of the dense entries;
-    'indexed': the same launches through the bank entries, no gathered copy.  Both include the three scalars read back per step.
+  - 'index_select + step': feats.index_select(0, idx) on the fp32 rows, then forward, loss, backward, AdamW + EMA through the dense wrappers
+    (the bank step on the gathered batch under an identity index); 'indexed': the same launches on the bank itself, no gathered copy.
+    Both include the three scalars read back per step.
   - store: the store launch from a channels-last trunk output view into the bank, beside feat.to(dtype) plus the copy into the bank's rows
     (for fp32: the .contiguous() layout copy plus the torch.cat share of one video).
 

@@ -70,7 +70,7 @@ def main():
         with open(args.out, "w") as f:             # rewritten line by line: a run cut short keeps what it measured
             f.write("\n".join(lines) + "\n")
 
-    n = kernels.simple_headtrain_param_count(C)
+    n = kernels.headtrain_param_count(C, HID)
     floor_opt = 9.0 * n * 4 / HBM_BPS * 1e6
     say(f"device: {kernels.device_name()}   times: median of 3 windows of {args.iters} steps between hipEvents, us per step")
     say(f"T = {T} rows per video, C = {C}, hidden {HID}, fp32, {n} parameters; floors at 6.3 TB/s, derived from the shape, not measured:")
