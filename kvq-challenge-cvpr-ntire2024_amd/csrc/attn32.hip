@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 #ifndef A32_ABL
 #define A32_ABL 0           // diagnostic builds (tools/ubench/attn32_loop.hip), bit mask: 1 no bias stream, 2 no exponentials, 4 no P V MFMAs,
@@ -67,7 +68,6 @@ constexpr float A32_OFF = -60000.0f;               // padding keys: exp2 underfl
 
 typedef __attribute__((ext_vector_type(4))) short a32_s4;
 typedef __attribute__((address_space(3))) a32_s4* a32_tr_t;
-typedef __attribute__((address_space(3))) void* a32_lds_t;
 
 // A 32-query block keeps a row in lanes q and q + 32: v_permlane32_swap hands each half the other's value without an LDS round
 // trip (new vdst = {own low half, partner's low half}, new vsrc = {partner's high half, own high half}: every lane sees both values)
@@ -422,17 +422,17 @@ __global__ __launch_bounds__(A32_WAVES * 64, 3) __attribute__((amdgpu_waves_per_
     // K | V by buffer-resource LDS-DMA (rows past N read zeros): K with its 16-B chunks XOR-swizzled by (row >> 2) & 3, V as it lies
     const uint16_t* Kg = p.qkv + ((size_t)(1 * p.nH + h) * Mtot + (size_t)bw * N) * 32;
     const uint16_t* Vg = p.qkv + ((size_t)(2 * p.nH + h) * Mtot + (size_t)bw * N) * 32;
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Kg), 0, N * 64, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Vg), 0, N * 64, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kg, (unsigned)(N * 64));
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(Vg, (unsigned)(N * 64));
     const unsigned vo_k = (unsigned)(lane >> 2) * 64u + (unsigned)((lane & 3) ^ ((lane >> 4) & 3)) * 16u, vo_v = (unsigned)lane * 16u;
     for (int it = wave; it < A32_ROWS / 16; it += A32_WAVES) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (a32_lds_t)(smem + it * 1024), 16, vo_k, it * 1024, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (a32_lds_t)(smem + A32_K_BYTES + it * 1024), 16, vo_v, it * 1024, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(smem + it * 1024), 16, vo_k, it * 1024, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(smem + A32_K_BYTES + it * 1024), 16, vo_v, it * 1024, 0, 0);
     }
   }
   const int q_lo = part * nqb / p.qsplit, q_hi = (part + 1) * nqb / p.qsplit;
   if (tid == 0) *ticket = q_lo;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
   if (!FUSED && p.pad_mask) {
     // padded partition: the padding rows of the window are keys with k | v = qkv(0) = the bias (swin_backbone.py:416-449); their rows of

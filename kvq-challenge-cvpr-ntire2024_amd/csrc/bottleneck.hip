@@ -20,11 +20,9 @@
 //      or one more MFMA over the input channels), ReLU, 16-byte stores through the same exchange.
 // Rounding points are those of the unfused launches (16-bit a, b and block output; fp32 accumulation and shortcut add).
 #include "common.hpp"
+#include "rows.hpp"
 
 namespace kvq {
-
-typedef __attribute__((address_space(3))) void* bn_lds_t;
-typedef __attribute__((address_space(1))) const void* bn_gbl_t;
 
 constexpr int BN_HALO = 16;
 __host__ __device__ constexpr int bn_tile(int stride) { return stride == 1 ? 14 : 7; }     // outputs per tile edge: halo (T - 1) s + 3 <= 16
@@ -69,8 +67,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void fast_bottleneck_kern
   const uint16_t* xb = p.x + (size_t)b * p.T * frame * CIN;
 
   // weights + biases -> LDS (LDS-DMA, 1 KB per wave-load)
-  for (int q = wave; q < L::PACK_BYTES / 1024; q += NW)
-    __builtin_amdgcn_global_load_lds((bn_gbl_t)(p.pack + q * 1024 + lane * 16), (bn_lds_t)(lds + q * 1024), 16, 0, 0);
+  lds_dma_image<NW>(lds, p.pack, wave, L::PACK_BYTES / 1024, lane);
   const float* s_ba = reinterpret_cast<const float*>(lds + L::OFF_BIAS);
   const float* s_bb = s_ba + 32;
   const float* s_bc = s_ba + 64;
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void fast_bottleneck_kern
   load_tile(0, bx[0], inside[0], ap[0]);
   if (NLOAD == 2) load_tile(1, bx[1], inside[1], ap[1]);
   // the weight image has landed and is visible to all
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
 #pragma unroll
   for (int c2 = 0; c2 < TPW; ++c2) {
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void fast_bottleneck_kern
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
           const int q = 2 * u + w;
-          const f32x4 bc = *reinterpret_cast<const f32x4*>(s_bc + 32 * rt + 8 * q + 4 * h);
+          const f32x4 bc = acc_piece(s_bc, rt, q, h);
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = acc[4 * q + e] + bc[e];

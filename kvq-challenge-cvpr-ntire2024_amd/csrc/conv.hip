@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(256) void mean_std_pool_vec8_kernel(const uint16_t*
   const uint16_t* xr = x + (size_t)row * HW * C + c0;
   auto block_sum8 = [&](float (&v)[8]) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
+    for (int e = 0; e < 8; ++e) {      // written out, not wave_sum: through it mean_std_pool_vec8_kernel<Fp16> gains an instruction
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) v[e] += __shfl_xor(v[e], o);
     }
@@ -706,8 +707,6 @@ __global__ __launch_bounds__(S6_THREADS) void conv_stem64_pool_kernel(Stem64Para
   fp16_saturate_mode();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using v8 = typename E::v8;
-  typedef __attribute__((address_space(3))) void* s6_lds_t;
-  typedef const __attribute__((address_space(1))) void* s6_gbl_t;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 15, kg = lane >> 4;
   const int PXP = p.W + 8;
   uint16_t* rows = reinterpret_cast<uint16_t*>(smem);              // [S6_NR][PXP][4]
@@ -741,14 +740,14 @@ __global__ __launch_bounds__(S6_THREADS) void conv_stem64_pool_kernel(Stem64Para
         const float* src = x0 + (size_t)y * p.W + src_col[j];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-          __builtin_amdgcn_global_load_lds((s6_gbl_t)(src + c * plane), (s6_lds_t)(raw + ((size_t)(c * S6_ITEMS + j) * S6_THREADS + wave * 64) * 4), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + c * plane), (lds_ptr_t)(raw + ((size_t)(c * S6_ITEMS + j) * S6_THREADS + wave * 64) * 4), 16, 0, 0);
       }
     }
   };
   const int kx = (lane >> 2) & 3;                                  // store pixel e ^ kx in pass e: conflict-free ds_write_b64 (see conv_stem_pool_kernel)
   auto commit = [&](int it) {                                      // raw -> 4-channel 16-bit pixels in `rows` (zero rows outside the image)
     const int yb = 2 * (2 * (it % nrb) * S6_PR - 1) - 3;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // a wave reads back the raw slots its own lanes loaded: no barrier
+    wait_vmcnt<0>();                                               // a wave reads back the raw slots its own lanes loaded: no barrier
 #pragma unroll
     for (int j = 0; j < S6_ITEMS; ++j)
       if (dst_off[j] >= 0) {

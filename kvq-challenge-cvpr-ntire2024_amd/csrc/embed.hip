@@ -54,9 +54,6 @@ struct EmbedParams {
 
 KVQ_NEXT_ROWS_ALIGNED(EmbedParams);
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((address_space(1))) const void* gbl_ptr_t;
-
 // image: CM panels [KS frag rows][64 lanes][8 x 16-bit] with W[32i+m][16s + 8h + e] (k in Conv3d weight order
 // c, kd, kh, kw), then fp32 [bias E][ln_w E][ln_b E]
 __global__ void embed_pack_kernel(const uint16_t* w, const float* bias, const float* lnw, const float* lnb, int E, int K,
@@ -105,8 +102,7 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   f32x4 nn_reg = {0.f, 0.f, 0.f, 0.f};
   if (EMIT && tid < E / 2) nn_reg = *next_norm_piece<E>(p.nr, tid);
   constexpr int NQ = (WBYTES + 3 * E * 4 + 1023) / 1024;     // weights + parameters, 1 KB wave-loads
-  for (int q = wave; q < NQ; q += 4)
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + q * 1024 + lane * 16), (lds_ptr_t)(lds + q * 1024), 16, 0, 0);
+  lds_dma_image<4>(lds, p.pack, wave, NQ, lane);
 
   // a workgroup walks tiles of 128 tokens blockIdx.x, + gridDim.x, ... (round 5: a launch of fewer, longer-lived workgroups — the weights
   // reach LDS once per workgroup, and in the multi-lane mix the launch holds fewer CU slots while it streams its 200 MB).  The launch gives
@@ -202,7 +198,7 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   }
   if (first_tile) {
     if (EMIT && tid < E / 2) *reinterpret_cast<f32x4*>(s_nn + 4 * tid) = nn_reg;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
   }
   if constexpr (FRAG) {
@@ -222,7 +218,7 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   for (int i = 0; i < CM; ++i) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 bq = *reinterpret_cast<const f32x4*>(prm + 32 * i + 8 * q + 4 * h);
+      const f32x4 bq = acc_piece(prm, i, q, h);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[i][4 * q + e] = bq[e];
     }
@@ -233,37 +229,15 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
     }
   }
 
-  // LayerNorm over the E channels of a token: in-lane sums + one exchange with lane^32 (two-pass, as ln.hip)
-  auto stats = [&](float& mean, float& rstd) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; r += 4) s += (acc[i][r] + acc[i][r + 1]) + (acc[i][r + 2] + acc[i][r + 3]);
-    s += __shfl_xor(s, 32);
-    mean = s / (float)E;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float dd = acc[i][r] - mean;
-        sq += dd * dd;
-      }
-    sq += __shfl_xor(sq, 32);
-    rstd = rsqrtf(sq / (float)E + p.eps);
-    asm volatile("" : "+v"(mean));     // opaque: no CSE of (acc - mean) between the variance and the normalise pass
-  };
   uint32_t rmax = 0;                   // out16: range detector, packed magnitude max of the stored halves
   if (p.has_ln) {
     float mean, rstd;
-    stats(mean, rstd);
+    token_row_stats<CM>(acc, p.eps, mean, rstd);      // LayerNorm over the E channels of a token
 #pragma unroll
     for (int i = 0; i < CM; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(prm + E + 32 * i + 8 * q + 4 * h);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(prm + 2 * E + 32 * i + 8 * q + 4 * h);
+        const f32x4 g = acc_piece(prm + E, i, q, h), be = acc_piece(prm + 2 * E, i, q, h);
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][4 * q + e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
       }
@@ -299,19 +273,16 @@ __device__ __forceinline__ void patch_embed_body(const EmbedParams& p) {
   if (p.out16 && p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   if (EMIT) {
     float mean, rstd;
-    stats(mean, rstd);
+    token_row_stats<CM>(acc, p.eps, mean, rstd);      // LayerNorm over the E channels of a token
     const long drow = (long)b * p.nr.next_rows + p.nr.next_dst[tl];
     uint16_t* o = p.nr.next_ln + (size_t)drow * E;
+    norm_rows_store<E_, false, CM>(o, h, live, [&](int i, int q) __attribute__((always_inline)) -> f32x4 {
+      const f32x4 g = acc_piece(s_nn, i, q, h), be = acc_piece(s_nn + E, i, q, h);
+      f32x4 y;
 #pragma unroll
-    for (int i = 0; i < CM; ++i)
-      tile_store16_pairswap<E_, false>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + E + 32 * i + 8 * q + 4 * h);
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
-        return y;
-      });
+      for (int e = 0; e < 4; ++e) y[e] = (acc[i][4 * q + e] - mean) * rstd * g[e] + be[e];
+      return y;
+    });
   }
   }      // tiles
 }

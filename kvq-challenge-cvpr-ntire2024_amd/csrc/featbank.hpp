@@ -1,7 +1,8 @@
 // What csrc/featbank.hip, csrc/headtrain.hip and csrc/simple_headtrain.hip share: the element types of a feature bank, the widening
-// quad load, the index clamp, the workgroup sum, and the host checks of a step's bank.
+// quad load, the index clamp, and the host checks of a step's bank.
 #pragma once
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 
@@ -24,22 +25,6 @@ __device__ __forceinline__ f32x4 bank_load4(const __bf16* p) {
 __device__ __forceinline__ long bank_row(const int32_t* __restrict__ index, long n_rows, long b) {
   const long r = index[b];
   return r < 0 ? 0 : (r < n_rows ? r : n_rows - 1);
-}
-
-// ---- sums the two training steps share
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// Workgroup-wide sum of one float per thread (256 threads), the same value in every thread: wave butterflies, then the four wave sums
-// in a fixed order.  wsum: 4 floats of LDS, reusable after the call returns in every thread.
-__device__ __forceinline__ float block_sum(float v, float* wsum) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
 static inline bool bank_dtype_ok(int dtype) { return dtype == KVQ_DT_FP32 || dtype == KVQ_DT_FP16 || dtype == KVQ_DT_BF16; }

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "gemm_common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 
@@ -25,17 +26,10 @@ __device__ __attribute__((aligned(16))) const uint32_t kvq_zero_chunk[4] = {0u, 
 #define KVQ_GEMM_NST 3      // slices in the LDS ring: 48 KB per 128x128 block -> 3 blocks/CU (measured: 4 -> 3.66 ms,
                             // 3 -> 3.53 ms, 2 -> 3.50 ms per step: co-residency beats DMA depth)
 #endif
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((address_space(1))) const void* gbl_ptr_t;
 
 template <typename V>
 __device__ __forceinline__ void lds_read_b128(V& dst, unsigned lds_addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_addr) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void gemm_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // K loop: an NST-deep LDS ring of BK=32 slices filled by LDS-DMA (global_load_lds_dwordx4: 16 B per lane,
@@ -230,13 +224,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
   auto wait_landed = [&](int kt, auto depth_tag) {
     constexpr int DEPTH = decltype(depth_tag)::value;
     const int younger = nk - 1 - kt;
-    if (DEPTH >= 1 && younger >= DEPTH) gemm_wait_vmcnt<DEPTH * PER>();
-    else if (DEPTH > 5 && younger == 5) gemm_wait_vmcnt<5 * PER>();
-    else if (DEPTH > 4 && younger == 4) gemm_wait_vmcnt<4 * PER>();
-    else if (DEPTH > 3 && younger == 3) gemm_wait_vmcnt<3 * PER>();
-    else if (DEPTH > 2 && younger == 2) gemm_wait_vmcnt<2 * PER>();
-    else if (DEPTH > 1 && younger == 1) gemm_wait_vmcnt<PER>();
-    else gemm_wait_vmcnt<0>();
+    if (DEPTH >= 1 && younger >= DEPTH) wait_vmcnt<DEPTH * PER>();
+    else if (DEPTH > 5 && younger == 5) wait_vmcnt<5 * PER>();
+    else if (DEPTH > 4 && younger == 4) wait_vmcnt<4 * PER>();
+    else if (DEPTH > 3 && younger == 3) wait_vmcnt<3 * PER>();
+    else if (DEPTH > 2 && younger == 2) wait_vmcnt<2 * PER>();
+    else if (DEPTH > 1 && younger == 1) wait_vmcnt<PER>();
+    else wait_vmcnt<0>();
   };
   for (int kt = 0; kt < nk; ++kt) {
     // slice kt must have landed; up to two younger slices stay in flight

@@ -28,11 +28,10 @@
 //        B0 one phase after, which is why P0 issues its 4 B reads first and waits lgkmcnt(8) before its barrier.
 #pragma once
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 namespace g8 {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int HALF_BYTES = 128 * BK * 2;          // 16 KB
@@ -40,20 +39,9 @@ constexpr int LDS_BYTES = 8 * HALF_BYTES;         // two K-tiles
 // slot of a half-tile inside a K-tile buffer
 constexpr int SLOT_B0 = 0, SLOT_A0 = 1, SLOT_B1 = 2, SLOT_A1 = 3;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <typename V>
 __device__ __forceinline__ void ds_read16(V& dst, unsigned addr, int off) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory");
-}
-
-// buffer resource over [base, base + bytes): raw (stride 0), out-of-range reads return 0
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes) {
-  const unsigned nr = bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)nr, 0x00020000);
 }
 
 // Operand source of the main loop.  Plain row-major [rows][K] operands: voffset = row * K * 2 + chunk * 16, the K position

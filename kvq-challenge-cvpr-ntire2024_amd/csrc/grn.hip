@@ -23,6 +23,7 @@
 // kvq_grn_stats enqueues all but the last, kvq_grn_apply the last.  Every sum has one fixed order: two runs are bit-equal, and a sample's
 // result does not depend on the batch it is in.  An all-zero column has Gx = 0 and, if the whole (b, w) slab is zero, Nx = 0 / 1e-6 = 0.
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 
@@ -141,9 +142,9 @@ __device__ __forceinline__ f32x4 grn_sum_chunks(const float* p, size_t stride, i
 }
 
 // Workgroup-wide sum of one float per thread, the same value in every thread: wave butterflies, then the four wave sums in a fixed order.
+// Not wave.hpp's block_sum: no barrier in front (wsum is written once per launch) and the wave sums are added left to right.
 __device__ __forceinline__ float grn_block_sum(float v, float* wsum) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];

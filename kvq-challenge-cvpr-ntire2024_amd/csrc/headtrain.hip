@@ -422,8 +422,7 @@ __global__ __launch_bounds__(256) void headtrain_bwd_sum_kernel(const float* __r
     if (threadIdx.x >= 64) return;
     float s = 0.f;
     for (int b = threadIdx.x; b < B; b += 64) s += dscore[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) grads[nw1 + 2 * HT_HID] = s;
     return;
   }

@@ -34,9 +34,6 @@ struct MergeParams {
 
 KVQ_NEXT_ROWS_ALIGNED(MergeParams);
 
-typedef __attribute__((address_space(3))) void* mg_lds_t;
-typedef __attribute__((address_space(1))) const void* mg_gbl_t;
-
 // geometry by width.  The weight image is cut into chunks of KC k-steps (all 2C / 32 row tiles of those k-steps: <= 72 KB) that
 // stream through two LDS buffers; at C = 96 the two chunks ARE the matrix (both requested at the start, nothing refilled).
 #ifndef KVQ_MERGE96_SMALL
@@ -99,13 +96,13 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+  // written out, not lds_dma_image: through it the kernels without EMIT and X16 take 42 SGPRs for 34
   auto issue_chunk = [&](int c) __attribute__((always_inline)) {         // chunk c -> buffer c & 1, 1 KB wave-loads
     for (int q = wave; q < CHUNK / 1024; q += WAVES)
-      __builtin_amdgcn_global_load_lds((mg_gbl_t)(p.pack + (size_t)c * CHUNK + q * 1024 + lane * 16),
-                                       (mg_lds_t)(lds + (c & 1) * CHUNK + q * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + (size_t)c * CHUNK + q * 1024 + lane * 16),
+                                       (lds_ptr_t)(lds + (c & 1) * CHUNK + q * 1024), 16, 0, 0);
   };
-  for (int q = wave; q < G::TAIL / 1024; q += WAVES)
-    __builtin_amdgcn_global_load_lds((mg_gbl_t)(p.pack + G::WBYTES + q * 1024 + lane * 16), (mg_lds_t)(lds + 2 * CHUNK + q * 1024), 16, 0, 0);
+  lds_dma_image<WAVES>(lds + 2 * CHUNK, p.pack + G::WBYTES, wave, G::TAIL / 1024, lane);
   issue_chunk(0);
   if (NCH > 1) issue_chunk(1);
   if (EMIT && tid < 2 * N / 4) *reinterpret_cast<f32x4*>(s_nn + 4 * tid) = *next_norm_piece<N>(p.nr, tid);
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
   };
 #pragma unroll
   for (int s = 0; s < PF; ++s) piece(s, ring[s]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the first two weight chunks, and the first row pieces behind them
+  wait_vmcnt<0>();       // the first two weight chunks, and the first row pieces behind them
   __syncthreads();
   // K: the mean of the token's first PF k-steps (PF x 8 values in each lane of the pair = 96 channels of neighbour 0).  A single
   // value (channel 0, rounds 4's choice) is not robust: one massive-activation channel there puts every one of the 4C operands near
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
     if (NCH > 2 && s > 0 && s % KC == 0) {
       // chunk s / KC - 1 is done: once every wave is past it, its buffer takes chunk s / KC + 1.  The chunk about to be used
       // was requested a whole chunk ago; the wait also drains the row pieces in flight (a bubble per chunk at C >= 128).
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
       if (s / KC + 1 < NCH) issue_chunk(s / KC + 1);
     }
@@ -211,8 +208,7 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
   // The accumulator tiles are only READ from here on (as in tail.hip: element-wise updates of a 16-register MFMA tuple make
   // the allocator copy whole tuples around and spill): every pass below recomputes the two fma of a value it needs.
   auto outv = [&](int i, int q) __attribute__((always_inline)) -> f32x4 {
-    const f32x4 wbv = *reinterpret_cast<const f32x4*>(wbeta + 32 * i + 8 * q + 4 * h);
-    const f32x4 ws = *reinterpret_cast<const f32x4*>(wbeta + N + 32 * i + 8 * q + 4 * h);
+    const f32x4 wbv = acc_piece(wbeta, i, q, h), ws = acc_piece(wbeta + N, i, q, h);
     f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaf(fmaf(-md, ws[e], acc[i][4 * q + e]), rstd, wbv[e]);
@@ -262,8 +258,7 @@ __global__ __launch_bounds__(64 * MGc<C_>::WAVES, (2 * MGc<C_>::LDS <= 163840 ? 
     for (int i = 0; i < CM; ++i)
       tile_store16_pairswap<E, true>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
         const f32x4 v = outv(i, q);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + N + 32 * i + 8 * q + 4 * h);
+        const f32x4 g = acc_piece(s_nn, i, q, h), be = acc_piece(s_nn + N, i, q, h);
         f32x4 y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = (v[e] - m2) * r2 * g[e] + be[e];

@@ -1,5 +1,6 @@
 // HBM-bound helpers around the trunk: patch-embed im2col, the two score heads, the fragment sampler.
 #include "common.hpp"
+#include "wave.hpp"
 #include "yuv.hpp"
 
 namespace kvq {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void vqa_head_token_kernel(const float* __rest
   }
   if (wave != 0) return;
 #pragma unroll
-  for (int t = 0; t < HEAD_TOK; ++t) {
+  for (int t = 0; t < HEAD_TOK; ++t) {      // written out, not wave_sum: through it the butterflies are scheduled another way (a wait becomes a nop)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc[t] += __shfl_xor(acc[t], o);
   }
@@ -286,8 +287,7 @@ __global__ __launch_bounds__(256) void simple_head_frame_kernel(const float* __r
   for (int j = wave; j < hidden; j += 4) {
     float d = 0.f;
     for (int c = lane; c < Cin; c += 64) d = fmaf(f[c], w1[(size_t)j * Cin + c], d);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    d = wave_sum(d);
     acc = fmaf(w2[j], d + b1[j], acc);
   }
   if (lane == 0) red[wave] = acc;
@@ -608,8 +608,7 @@ __global__ __launch_bounds__(64) void vqa_head_classes_kernel(const float* __res
     const float h = live ? gelu_erf(d + b1[jc]) : 0.f;
     for (int k = 0; k < K; ++k) {
       float v = live ? w2[(size_t)k * hidden + jc] * h : 0.f;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      v = wave_sum(v);
       if (lane == 0) logit[k] += v;
     }
   }

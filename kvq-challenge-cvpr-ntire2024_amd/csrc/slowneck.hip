@@ -21,11 +21,9 @@
 // s_waitcnt / barriers (profiles/r03_slowneck_pmc.txt) — one workgroup per CU leaves each tile's load -> a -> b -> c chain uncovered.
 // Rounding points are those of the unfused launches (16-bit a, b and block output; fp32 accumulation and identity add).
 #include "common.hpp"
+#include "rows.hpp"
 
 namespace kvq {
-
-typedef __attribute__((address_space(3))) void* sn_lds_t;
-typedef __attribute__((address_space(1))) const void* sn_gbl_t;
 
 constexpr int SN_CIN = 256, SN_CI = 64, SN_COUT = 256, SN_T = 14, SN_HALO = 16, SN_WAVES = 8;
 constexpr int SN_KSA = SN_CIN / 16, SN_KSB = 9 * SN_CI / 16, SN_KSC = SN_CI / 16, SN_RTC = SN_COUT / 32;
@@ -66,11 +64,10 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
   uint16_t* of = p.out + (size_t)bt * frame * p.out_C;
 
   // conv_a / conv_b weights + biases -> LDS (LDS-DMA, 1 KB per wave-load)
-  for (int q = wave; q < (SN_A_BYTES + SN_B_BYTES) / 1024; q += SN_WAVES)
-    __builtin_amdgcn_global_load_lds((sn_gbl_t)(p.pack + q * 1024 + lane * 16), (sn_lds_t)(lds + q * 1024), 16, 0, 0);
+  lds_dma_image<SN_WAVES>(lds, p.pack, wave, (SN_A_BYTES + SN_B_BYTES) / 1024, lane);
   if (wave < SN_BIAS_BYTES / 1024)
-    __builtin_amdgcn_global_load_lds((sn_gbl_t)(p.pack + SN_A_BYTES + SN_B_BYTES + SN_C_BYTES + wave * 1024 + lane * 16),
-                                     (sn_lds_t)(lds + SN_OFF_BIAS + wave * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + SN_A_BYTES + SN_B_BYTES + SN_C_BYTES + wave * 1024 + lane * 16),
+                                     (lds_ptr_t)(lds + SN_OFF_BIAS + wave * 1024), 16, 0, 0);
   const float* s_ba = reinterpret_cast<const float*>(lds + SN_OFF_BIAS);
   const float* s_bb = s_ba + 64;
   const float* s_bc = s_ba + 128;
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
       if (inside) v = *reinterpret_cast<const u32x4*>(px + 16 * s);
       bx[s] = __builtin_bit_cast(V8, v);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the weight image has landed ...
+    wait_vmcnt<0>();                                       // the weight image has landed ...
     __syncthreads();                                       // ... and is visible to all
     f32x16 acc[2];
 #pragma unroll
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 ba = *reinterpret_cast<const f32x4*>(s_ba + 32 * rt + 8 * q + 4 * h);
+        const f32x4 ba = acc_piece(s_ba, rt, q, h);
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = inside ? fmaxf(acc[rt][4 * q + e] + ba[e], 0.f) : 0.f;
@@ -114,9 +111,10 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
   }
   __syncthreads();                                       // a_tile complete; conv_a's weights dead
   // conv_c's weights over conv_a's, under conv_b
+  // (written out, not lds_dma_image: through it the has_tile branch behind the loop takes a second compare for its saved mask)
   for (int q = wave; q < SN_C_BYTES / 1024; q += SN_WAVES)
-    __builtin_amdgcn_global_load_lds((sn_gbl_t)(p.pack + SN_A_BYTES + SN_B_BYTES + q * 1024 + lane * 16),
-                                     (sn_lds_t)(lds + SN_OFF_AC + q * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.pack + SN_A_BYTES + SN_B_BYTES + q * 1024 + lane * 16),
+                                     (lds_ptr_t)(lds + SN_OFF_AC + q * 1024), 16, 0, 0);
 
   // ---- conv_b on the 14 x 14 outputs: column tile `wave` (7 tiles: the eighth wave only keeps the barriers) ----------------------------
   constexpr int NOUT = SN_T * SN_T;
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
       hb[s] = __builtin_bit_cast(V8, w);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // conv_c's weights have landed ...
+  wait_vmcnt<0>();                                       // conv_c's weights have landed ...
   __syncthreads();                                       // ... for every wave
   if (!has_tile) return;
 
@@ -204,7 +202,7 @@ __global__ __launch_bounds__(512, 1) void slow_bottleneck_kernel(SlowneckParams 
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 bc = *reinterpret_cast<const f32x4*>(s_bc + 32 * rt + 8 * q + 4 * h);
+      const f32x4 bc = acc_piece(s_bc, rt, q, h);
       float v[4];
       v[0] = acc[4 * q + 0] + bc[0] + E::to_f32((uint16_t)(d[q][0] & 0xffffu));
       v[1] = acc[4 * q + 1] + bc[1] + E::to_f32((uint16_t)(d[q][0] >> 16));

@@ -31,15 +31,6 @@
 
 namespace kvq {
 
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((address_space(1))) const void* gbl_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 __host__ __device__ constexpr int tail_slot_bytes(int C) { return 128 * C; }            // 2 panels of 32 x C 16-bit
 __host__ __device__ constexpr int tail_proj_items(int C) { return (C / 32 + 1) / 2; }
 // workgroups per CU for NW waves of 32 tokens each: C=96 fits 3 waves per SIMD (<= 168 VGPRs), wider rows 2
@@ -154,6 +145,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   f32x4 nn_reg = {0.f, 0.f, 0.f, 0.f};
   if (EMIT && tid < C / 2) nn_reg = *next_norm_piece<C>(p.nr, tid);
   {
+    // written out, not lds_dma_image: the inlined call leaves the loop in front of the code behind it, and the kernel gains two instructions
     const unsigned char* src = p.pack + (size_t)NI * SLOT;
     for (int q = wave; q < NQ; q += NW)      // uneven per wave is fine: these are OLDER than every counted item
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + q * 1024 + lane * 16),
@@ -190,6 +182,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     // accumulator tiles are only READ element-wise (norm2) or written by MFMA: element-wise updates in between
     // would make the register allocator shuffle / spill the 16-register tuples.
     const float* xr = p.x + (size_t)orig * C + 4 * h;
+    // (pbg + 32 i + 8 q below stays written out, not acc_piece(.., h) on the bare pointer: that form costs <*, 3, 4, 2> 12 VGPRs)
     const float* pbg = reinterpret_cast<const float*>(p.pack + (size_t)NI * SLOT) + 4 * h;
     if (p.x16) {
       // fp16 residual stream (round 6): 8 bytes per lane and quad instead of 16; every piece requested before the first is widened
@@ -276,8 +269,8 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
           const int q = 2 * t + qq;
-          const f32x4 g = *reinterpret_cast<const f32x4*>(gam + 32 * i + 8 * q + 4 * h);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(bet + 32 * i + 8 * q + 4 * h);
+          const f32x4 g = acc_piece(gam, i, q, h);
+          const f32x4 be = acc_piece(bet, i, q, h);
           float y[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs_, nm_), g[e], be[e]);      // two fma per value: (x rstd - mean rstd) g + b
@@ -306,26 +299,9 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   __builtin_amdgcn_sched_barrier(0);
   // ---- norm2 in registers: two-pass statistics, biased variance, eps inside the rsqrt (as ln.hip) -----------
   {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; r += 4) s += (acc[i][r] + acc[i][r + 1]) + (acc[i][r + 2] + acc[i][r + 3]);
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = acc[i][r] - mean;
-        sq += d * d;
-      }
-    sq += __shfl_xor(sq, 32);
-    const float rstd = rsqrtf(sq / (float)C + p.eps);
-    float mean_n = mean;
-    asm volatile("" : "+v"(mean_n));   // an opaque copy: CSE with the variance pass would keep C/2 differences live (spills)
-    const float nmr = -mean_n * rstd;
+    float mean, rstd;
+    token_row_stats<CM>(acc, p.eps, mean, rstd);
+    const float nmr = -mean * rstd;
     // normalised row -> B operands of fc1 (k order = accumulator order, see tail_pack_kernel); x1 stays in acc
     norm_to_bx(rstd, nmr, s_g2, s_b2n);
   }
@@ -337,7 +313,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   auto h_init = [&](f32x16& ha, int j) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(s_fb1 + 32 * j + 8 * q + 4 * h);
+      const f32x4 b = acc_piece(s_fb1, j, q, h);
 #pragma unroll
       for (int e = 0; e < 4; ++e) ha[4 * q + e] = b[e];
     }
@@ -407,7 +383,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
   for (int i = 0; i < CM; ++i)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 fb = *reinterpret_cast<const f32x4*>(s_fb2 + 32 * i + 8 * q + 4 * h);
+      const f32x4 fb = acc_piece(s_fb2, i, q, h);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[i][4 * q + e] += fb[e];
       if (q & 1) __builtin_amdgcn_sched_barrier(0);
@@ -418,26 +394,9 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
     if (p.range.word) range_flush(rmax, p.range.word, p.range.bit);
   } else stream_row_store<false, CM>(p.x, (size_t)orig * C + 4 * h, live, 0, xv);
   if (EMIT) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; r += 4) s += (acc[i][r] + acc[i][r + 1]) + (acc[i][r + 2] + acc[i][r + 3]);
-    s += __shfl_xor(s, 32);
-    const float mu = s / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = acc[i][r] - mu;
-        sq += d * d;
-      }
-    sq += __shfl_xor(sq, 32);
-    const float rs = rsqrtf(sq / (float)C + p.eps);
-    float mu_n = mu;
-    asm volatile("" : "+v"(mu_n));
-    const float nmr2 = -mu_n * rs;
+    float mu, rs;
+    token_row_stats<CM>(acc, p.eps, mu, rs);
+    const float nmr2 = -mu * rs;
     const long drow = (long)tb * p.nr.next_rows + p.nr.next_dst[tloc];
     if (QKV) {
       // ---- the next block's q | k | v (swin_backbone.py:252-260 of block b + 1): its norm1 row becomes the B operand in registers (k order
@@ -454,7 +413,7 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
           f32x16 ha;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x4 b = *reinterpret_cast<const f32x4*>(p.qkv_b + 32 * pj + 8 * q + 4 * h);
+            const f32x4 b = acc_piece(p.qkv_b, pj, q, h);
 #pragma unroll
             for (int e = 0; e < 4; ++e) ha[4 * q + e] = b[e];
           }
@@ -472,16 +431,13 @@ __global__ __launch_bounds__(64 * NW, tail_bpc(32 * CM, NW)) void block_tail_ker
       }
     }
     uint16_t* o = p.nr.next_ln + (size_t)drow * C;
+    norm_rows_store<E, true, QKV ? 0 : CM>(o, h, live, [&](int i, int q) __attribute__((always_inline)) -> f32x4 {
+      const f32x4 g = acc_piece(s_nn, i, q, h), be = acc_piece(s_nn + C, i, q, h);
+      f32x4 y;
 #pragma unroll
-    for (int i = 0; i < (QKV ? 0 : CM); ++i)
-      tile_store16_pairswap<E, true>(o + 32 * i, h, live, [&](int q) __attribute__((always_inline)) -> f32x4 {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(s_nn + 32 * i + 8 * q + 4 * h);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(s_nn + C + 32 * i + 8 * q + 4 * h);
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs, nmr2), g[e], be[e]);
-        return y;
-      });
+      for (int e = 0; e < 4; ++e) y[e] = fmaf(fmaf(acc[i][4 * q + e], rs, nmr2), g[e], be[e]);
+      return y;
+    });
   }
 #ifdef KVQ_TAIL_TRACE
   __builtin_amdgcn_s_waitcnt(0);

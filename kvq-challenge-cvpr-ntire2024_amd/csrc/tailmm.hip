@@ -49,9 +49,6 @@
 
 namespace kvq {
 
-typedef __attribute__((address_space(3))) void* mm_lds_t;
-typedef __attribute__((address_space(1))) const void* mm_gbl_t;
-
 // Geometry by CF = C / 128 = 32-feature tiles per wave: 3 (C = 384: stage 2 of Swin-T / -S) or 4 (C = 512: stage 2 of Swin-B,
 // register ring only — its 64 KB activation tile leaves no room for an LDS weight ring), and by HC = hidden units per MLP chunk:
 //   HC = 256: a wave's fc1 slice is 64 units (two tiles): 512 VGPRs, 94 KB of LDS, ONE workgroup per CU (rounds 2-4);
@@ -316,10 +313,9 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
       long row = arow[0];
 #pragma unroll
       for (int u = 1; u < TT; ++u) row = tt == u ? arow[u] : row;
-      __builtin_amdgcn_global_load_lds((mm_gbl_t)(p.attn + (size_t)row * C + 16 * ks + 8 * half), (mm_lds_t)(lds + MM_OFF_X + fr * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(p.attn + (size_t)row * C + 16 * ks + 8 * half), (lds_ptr_t)(lds + MM_OFF_X + fr * 1024), 16, 0, 0);
     }
-    for (int q = wave; q < (MM_PRM_FLOATS * 4) / 1024; q += 4)      // b1 | g2 | b2n | proj_b | b2: 12 KB
-      __builtin_amdgcn_global_load_lds((mm_gbl_t)((const unsigned char*)gprm + q * 1024 + lane * 16), (mm_lds_t)(lds + MM_OFF_PRM + q * 1024), 16, 0, 0);
+    lds_dma_image<4>(lds + MM_OFF_PRM, (const unsigned char*)gprm, wave, (MM_PRM_FLOATS * 4) / 1024, lane);      // b1 | g2 | b2n | proj_b | b2: 12 KB
   }
 #pragma unroll
   for (int q = 0; q < VR_PF; ++q) vload(q);          // VR_PF fragments of the weight list in flight from here on
@@ -335,6 +331,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
         for (int q = 0; q < 4; ++q)
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt) {
+            // acc_piece's address in the 16-bit row: 8 bytes, not an f32x4
             const uint64_t u = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint16_t*>(p.x) + (size_t)orig[tt] * C + FW * wave + 32 * ft + 8 * q + 4 * half);
             xv[ft][q][tt][0] = __uint_as_float((uint32_t)u); xv[ft][q][tt][1] = __uint_as_float((uint32_t)(u >> 32));
           }
@@ -345,11 +342,11 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
         for (int q = 0; q < 4; ++q)
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt)
-            xv[ft][q][tt] = *reinterpret_cast<const f32x4*>(p.x + (size_t)orig[tt] * C + FW * wave + 32 * ft + 8 * q + 4 * half);
+            xv[ft][q][tt] = acc_piece(p.x + (size_t)orig[tt] * C + FW * wave, ft, q, half);
     }
     __builtin_amdgcn_sched_barrier(0);
     // everything requested so far has landed (the row loads were issued last: vmcnt(0) covers the DMA before them too)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     MM_STAMP(1);
     if (p.x16) {
@@ -368,7 +365,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
     for (int ft = 0; ft < CF; ++ft)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 pb = *reinterpret_cast<const f32x4*>(prm + MM_H + 2 * MM_C + FW * wave + 32 * ft + 8 * q + 4 * half);
+        const f32x4 pb = acc_piece(prm + MM_H + 2 * MM_C + FW * wave, ft, q, half);
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -488,7 +485,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
   for (int ft = 0; ft < CF; ++ft)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 b2 = *reinterpret_cast<const f32x4*>(prm + MM_H + 3 * MM_C + FW * wave + 32 * ft + 8 * q + 4 * half);
+      const f32x4 b2 = acc_piece(prm + MM_H + 3 * MM_C + FW * wave, ft, q, half);
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -507,7 +504,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
     for (int ft = 0; ft < HT; ++ft)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 b1 = *reinterpret_cast<const f32x4*>(prm + MM_HC * c + 32 * HT * wave + 32 * ft + 8 * q + 4 * half);
+        const f32x4 b1 = acc_piece(prm + MM_HC * c + 32 * HT * wave, ft, q, half);
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -608,7 +605,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
       for (int ft = 0; ft < CF; ++ft)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x4 qb = *reinterpret_cast<const f32x4*>(p.qkv_b + which * C + FW * wave + 32 * ft + 8 * q + 4 * half);
+          const f32x4 qb = acc_piece(p.qkv_b + which * C + FW * wave, ft, q, half);
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -654,6 +651,7 @@ __global__ __launch_bounds__(256, (MMc<CF, HC>::REG_WAVES)) void block_tailmm_ke
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             const int q = 2 * t + u;
+            // written out, not acc_piece: one index for both vectors (through the helper the EMIT kernels change length and scratch)
             const int f0 = FW * wave + 32 * ft + 8 * q + 4 * half;
             const f32x4 gm = *reinterpret_cast<const f32x4*>(p.nr.nn_w + f0), be = *reinterpret_cast<const f32x4*>(p.nr.nn_b + f0);
             float y[4];

@@ -5,6 +5,7 @@
 // adapter mix and the cosine map.  All HBM-trivial: written for clarity, fp32 arithmetic throughout.
 #include <algorithm>
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace kvq {
 
@@ -19,21 +20,20 @@ __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* __restri
   __shared__ float red[8];
   float s = 0.f;
   for (int c = tid; c < D; c += 256) s += src[c] + pr[c];
-  auto block_sum = [&](float v) -> float {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  auto sum256 = [&](float v) -> float {      // wave.hpp's block_sum pairs the wave sums; this one adds them left to right
+    v = wave_sum(v);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
   };
-  const float mean = block_sum(s) / (float)D;
+  const float mean = sum256(s) / (float)D;
   float q = 0.f;
   for (int c = tid; c < D; c += 256) {
     const float d = src[c] + pr[c] - mean;
     q += d * d;
   }
-  const float rstd = rsqrtf(block_sum(q) / (float)D + eps);
+  const float rstd = rsqrtf(sum256(q) / (float)D + eps);
   float* o = out + ((size_t)b * (G + 1) + l) * D;
   for (int c = tid; c < D; c += 256) o[c] = (src[c] + pr[c] - mean) * rstd * lw[c] + lb[c];
 }
@@ -479,8 +479,7 @@ __global__ __launch_bounds__(64) void l2_normalize_rows_kernel(const float* __re
   const float* xr = x + m * D;
   float s = 0.f;
   for (int c = lane; c < D; c += 64) s = fmaf(xr[c], xr[c], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   const float inv = 1.f / fmaxf(sqrtf(s), 1e-12f);
   for (int c = lane; c < D; c += 64) out[m * D + c] = E::cvt(xr[c] * inv);
 }
